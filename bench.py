@@ -6,14 +6,16 @@ over one batch: SMPL forward -> contact_fitting_loss (reprojection + GMM prior +
 push/pull terms with winding-number inside test and segment filter + region-to-region term)
 -> backward -> Adam step, on SMPL-sized synthetic bodies (V=6890, F=13776).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          # N > 1: spawns N ranks itself
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]   # N > 1: spawns N ranks itself
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 The batch dimension shards across ranks.  --gpus N > 1 defaults to STRONG scaling at the global batch of 64 that
 SURVEY 8(e) / north_star name (64/N bodies per GPU; the weak-scaling figure, 64 bodies per GPU, is timed in the same run and
 reported as `weak_scaling`; --weak makes it the headline, --global-batch G picks another total).  The fits of different bodies never exchange data, so there is no collective inside
 the loop: the two floats [sum of losses, body count] are all-reduced (RCCL) once per timed block of K steps.
-Rank 0 prints ONE JSON line (contract in the task description) including
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times ONE block of K
+steps and prints the headline (metric, value, unit, ms_per_step, ...); --dump-outputs DIR also writes what the timed step
+computed in its last step (DIR/<name>.npy).  --full adds everything else:
   roofline     -- dominant kernel of the step (the masked vertex-distance search, v2v_scan_kernel): `frac` = EXECUTED vector
                   work (SQ_INSTS_VALU of the committed PMC pass x 64 lanes x 2 / launch time measured here with HIP events /
                   FP32 vector peak); `equivalent_frac` = SURVEY 8(d)'s all-pairs figure (most pairs are pruned); valu_busy /
@@ -211,7 +213,14 @@ def parse(argv=None):
     ap.add_argument('--weak', action='store_true',
                     help='N > 1: weak scaling (--batch bodies per GPU) as the headline instead of strong scaling at '
                          'global batch 64')
-    ap.add_argument('--repeats', type=int, default=5, help='how many times the K-step block is timed')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check everything beyond the headline figure (repeated blocks, the other all-reduce '
+                         'form, weak scaling, self-check, kernel counts, rooflines, RCCL smoke, extra workloads, CPU '
+                         'baselines); a plain run sets up, warms up, times --steps steps once and prints the result line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the timed step computed in its last step as DIR/<name>.npy '
+                         '(float32 / float64; rank 0)')
+    ap.add_argument('--repeats', type=int, default=5, help='--full: how many times the K-step block is timed')
     ap.add_argument('--config', default='2', choices=['2', '3', '4-shard', '5-shard'],
                     help='which BASELINE config is the timed step (default 2 = the headline)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
@@ -324,6 +333,8 @@ def make_step(p):
         ops.backward_scalar(loss)                 # as SMPLifyDC._Stage._one does
         opt.step()
         return loss.detach(), count               # [loss sum, bodies]: stacked by the caller, once per timed block
+    # what the fit hands on after a step besides the loss: the parameters, updated in place
+    step.outputs = lambda: {'body_pose': body_pose.detach(), 'global_orient': global_orient.detach()}
 
     def objective():
         """The stage-2 objective at the CURRENT parameters, eager launches, no update; also the posed vertices."""
@@ -353,13 +364,18 @@ def make_fit(p, iters):
     init_pose = torch.cat([p['global_orient'], p['body_pose']], 1)
     stats = torch.zeros(2, device=dev)
     stats[1] = float(batch)
+    last = {}
 
     def fit():
         res = fitter(init_pose, p['betas'], p['cam_t'], p['cam_c'], kp, use_contact=True, contactlist=p['cdict'],
                      gt_contact=[p['gt'], None], ignore_idxs=p['ignore'], has_discrete_contact=p['has_dc'],
                      contact_loss_weight=2000.0, segments=p['segments'])
         stats[0] = res[5].sum()
+        last['res'] = res
         return stats
+    # the 7-tuple SMPLifyDC.__call__ returns (smplifydc.py:231-236)
+    fit.outputs = lambda: dict(zip(('vertices', 'joints', 'pose', 'betas', 'camera_translation', 'reprojection_loss',
+                                    'optiverts'), last['res']))
     return fit, fitter
 
 
@@ -466,14 +482,17 @@ def make_tuch_step(p, run_smplify, smplify_iters=10, seed=77):
     params = [q for q in module.model.parameters()]
     stats = torch.zeros(2, device=dev)
     stats[1] = float(batch)
+    last = {}
 
     def step():
         for q in params:
             q.grad = None
-        loss, _, _ = module.forward_train_step(input_batch)
+        loss, losses, output = module.forward_train_step(input_batch)
         loss.backward()
         stats[0] = loss.detach() * batch
+        last.update(losses=losses, output=output)
         return stats
+    step.outputs = lambda: dict(last)
     # fresh bodies: the images (what the regressor stand-in turns into poses and shapes), keypoints and pseudo ground truth of
     # FRESH_BATCHES different input batches, written into the step's input tensors in place between calls / replays (dataset
     # names, sample indices and the has_* flags stay: they steer the fits dictionary, not the contact path)
@@ -577,6 +596,7 @@ def capture(step, warmup):
         return out
     replay.objective = getattr(step, 'objective', None)
     replay.next_bodies = getattr(step, 'next_bodies', None)
+    replay.outputs = getattr(step, 'outputs', None)
     replay.graph = graph
     # the graph holds raw addresses of everything `step` owns (parameters, Adam state, ...): they must live as
     # long as the graph does.  (Round 1 dropped `step` here; its tensors were then recycled by the next regular
@@ -1158,6 +1178,49 @@ def cpu_torch_chain(p):
                       'torch CPU ops materialising the reference intermediates; no segments, no backward'}
 
 
+DUMP_MAX_BYTES = 64 * 2 ** 20
+
+
+def _flatten_outputs(name, obj, out):
+    """Tensors, arrays and numbers inside dicts / lists / tuples -> out['a.b.0'] as float32 (float64 for float64 and
+    integer data); strings and None are skipped."""
+    if isinstance(obj, dict):
+        for k, v in obj.items():
+            _flatten_outputs('%s.%s' % (name, k) if name else str(k), v, out)
+    elif isinstance(obj, (list, tuple)):
+        for i, v in enumerate(obj):
+            _flatten_outputs('%s.%d' % (name, i) if name else str(i), v, out)
+    elif isinstance(obj, (torch.Tensor, np.ndarray, np.number, bool, int, float)):
+        a = obj.detach().cpu().numpy() if isinstance(obj, torch.Tensor) else np.asarray(obj)
+        wide = a.dtype == np.float64 or a.dtype.kind in 'iu'
+        out[name] = np.array(a, dtype=np.float64 if wide else np.float32, order='C')
+
+
+def dump_outputs(directory, stats, step):
+    """What the timed step computed in its last step, as directory/<name>.npy: the step's return value (loss sum, bodies)
+    and what its caller receives besides (step.outputs()).  Above DUMP_MAX_BYTES in all, every array larger than 1 MiB is
+    replaced by a fixed, seeded sample of its elements (<name>.npy) and their flat indices (<name>.sample_index.npy)."""
+    arrays = {}
+    if isinstance(stats, tuple):
+        stats = torch.stack([t.to(torch.float32).reshape(()) for t in stats])
+    _flatten_outputs('', {'loss_sum': stats[0], 'bodies': stats[1]}, arrays)
+    if callable(getattr(step, 'outputs', None)):
+        _flatten_outputs('', step.outputs(), arrays)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        keep = DUMP_MAX_BYTES / (4.0 * total)        # sample + float64 index: at most 16 bytes per kept element
+        for name in [n for n, a in arrays.items() if a.nbytes > 2 ** 20]:
+            a = arrays[name].reshape(-1)
+            rng = np.random.Generator(np.random.PCG64(12345))
+            idx = np.sort(rng.choice(a.size, max(1, int(a.size * keep)), replace=False))
+            arrays[name] = a[idx]
+            arrays[name + '.sample_index'] = idx.astype(np.float64)
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + '.npy'), a)
+    return sorted(arrays)
+
+
 CONFIGS = {
     '2': dict(metric='SMPLify-DC fit iters/sec at batch 64', unit='body-fit iterations/s', iters_per_step=1,
               workload='configs[1] extended to the full stage-2 step: batch=%d/GPU SMPL forward + contact_fitting_loss '
@@ -1229,9 +1292,10 @@ def main():
         # a training loop: every step sees a NEW input batch (FRESH_BATCHES of them in turn, written in place)
         one = make_tuch_step(p, run_smplify=args.config == '5-shard', smplify_iters=10)
         step = lambda: (one.next_bodies(), one())[1]
+        step.outputs = one.outputs
         launch = 'eager; %d different input batches in turn' % FRESH_BATCHES
     weak_step = None
-    if default_strong and not args.eager:
+    if default_strong and not args.eager and args.full:
         # the weak-scaling twin (64 bodies on every rank), captured before the process group exists like the headline
         weak_step = capture(make_step(build_problem(BATCH_PER_GPU, device, seed=2002 + rank)), args.warmup)
     if world > 1:
@@ -1292,9 +1356,11 @@ def main():
     if last is not None:
         reduce(last)                                     # the collective's own first-call cost stays out of the timing
     dt, stats = block(args.steps)                        # the contract's measurement
-    repeats = [dt] + [block(args.steps)[0] for _ in range(max(args.repeats, 1) - 1)]
+    if args.dump_outputs and rank == 0:                  # before any further step changes the state
+        dump_outputs(args.dump_outputs, stats, step)
+    repeats = [dt] + [block(args.steps)[0] for _ in range(max(args.repeats, 1) - 1 if args.full else 0)]
     other_form = None
-    if world > 1:
+    if world > 1 and args.full:
         odt, _ = block(args.steps, per_step=not per_step)
         other_form = {'allreduce': 'per block' if per_step else 'per step', 'ms_per_step': round(odt / args.steps * 1e3, 4),
                       'value': round(batch * world * CONFIGS[args.config]['iters_per_step'] * args.steps / odt, 2)}
@@ -1324,61 +1390,62 @@ def main():
                                       % (world, 'step, inside the timed loop' if per_step else 'timed block'),
                        'batch_iterations_per_s': round(cfg['iters_per_step'] * args.steps / dt, 3),
                        'loss_sum': float(stats[0].item()), 'bodies': float(stats[1].item())},
-            'repeat_ms_per_step': {'n': len(per_step_ms), 'median': round(float(np.median(per_step_ms)), 4),
-                                   'min': round(min(per_step_ms), 4), 'max': round(max(per_step_ms), 4),
-                                   'note': 'the same %d-step block timed %d times; ms_per_step/value are block 1'
-                                           % (args.steps, len(per_step_ms))},
             'scaling_note': 'no multi-GPU node was available to the builder: N>1 values exist only when the driver '
                             'runs this script on one; --gpus N > 1 defaults to STRONG scaling at global batch 64 (SURVEY 8e) '
                             'and reports the weak-scaling figure (64 bodies per GPU) as `weak_scaling`' if world == 1 else
                             'global batch %d split over %d ranks (%s scaling)' % (bodies, world, scaling),
         }
-        if weak is not None:
-            line['weak_scaling'] = weak
-        if other_form is not None:
-            line['other_allreduce_form'] = other_form
-        if args.config == '2':
-            try:
-                line['selfcheck'] = selfcheck(p, step)
-            except Exception as exc:                     # the measurement stands; the check reports what went wrong
-                line['selfcheck'] = {'ok': False, 'error': repr(exc)}
-            line['kernels_per_step'] = kernels_per_step(step)
-            line['graph_timeline'] = timeline_constants()
-        roof, inside, verts, model = rooflines(p, batch)
-        line['roofline'], line['roofline_inside_test'] = roof, inside
-        if args.config == '2':
-            # the whole step priced in SURVEY 8(d)'s units (67 FLOP per (query, face) pair of the body and of every closed
-            # segment, 8 FLOP per ordered vertex pair) over the measured step time: a multiple of the vector PEAK, because
-            # the step does not do that pair work (exact pruning, crossings instead of solid angles)
-            from tuch_amd.ops import segment_faces
-            body = p['body']
-            seg_pairs = sum(len(sg['vidx']) * len(segment_faces(body.faces, sg['vidx'], list(sg['bands'].values()), body.num_verts))
-                            for sg in body.segments.values())
-            eq = (FLOP_PER_WINDING_PAIR * (body.num_verts * body.num_faces + seg_pairs)
-                  + FLOP_PER_V2V_PAIR * body.num_verts ** 2) * batch
-            line['step_equivalent_flop'] = eq
-            line['step_equivalent_x_peak'] = round(eq / (dt / args.steps) / 1e12 / PEAK_FP32_VECTOR_TFLOPS, 2)
         line['mfma_use'] = ('SMPL dense matmuls (blend / skin adjoint, exact f32 MFMA) as north_star asks; DEPARTURE from its '
                             '"MFMA only for the SMPL matmuls": the HD branch\'s nearest-point search (hd_search_kernel, '
                             'RegressorLoss use_hd=True) also runs on the matrix cores -- 502 -> 215 us at batch 64, option '
                             'hd_search=0 is the exact VALU kernel; the headline step (this line) uses MFMA for SMPL only')
-        if world == 1 and backend == 'nccl' and not args.no_rccl_smoke:
-            line['rccl_smoke'] = rccl_smoke()
-        if world == 1 and not args.no_extras:
-            line['contact_loss_eval'] = contact_loss_eval(p, batch, verts, model)
-            line['shard_sweep'] = shard_sweep(device, 1002)
-            line['workloads'] = workloads(device, 1002)
-            line['worst_case'] = worst_case(device, 1002, batch)
-            line['worst_case']['folded'] = worst_case(device, 1002, batch, folded=True)
-            from tuch_amd import ops as ops_mod
-            line['deterministic'] = bool(ops_mod.deterministic())
-            line['float_atomics_mode'] = float_atomics_cost(device, 1002, batch)
-            line['headline_without_hints'] = headline_without_hints(device, 1002, batch)
-            line['irregular_topology'] = irregular_topology(device, 1002, batch)
-        if world == 1 and not args.no_cpu_baseline:
-            line['cpu_baseline'] = cpu_baseline(p, args.cpu_seconds)
-            if not args.no_torch_chain:
-                line['cpu_baseline_torch_chain'] = cpu_torch_chain(p)
+        if args.full:
+            line['repeat_ms_per_step'] = {'n': len(per_step_ms), 'median': round(float(np.median(per_step_ms)), 4),
+                                          'min': round(min(per_step_ms), 4), 'max': round(max(per_step_ms), 4),
+                                          'note': 'the same %d-step block timed %d times; ms_per_step/value are block 1'
+                                                  % (args.steps, len(per_step_ms))}
+            if weak is not None:
+                line['weak_scaling'] = weak
+            if other_form is not None:
+                line['other_allreduce_form'] = other_form
+            if args.config == '2':
+                try:
+                    line['selfcheck'] = selfcheck(p, step)
+                except Exception as exc:                     # the measurement stands; the check reports what went wrong
+                    line['selfcheck'] = {'ok': False, 'error': repr(exc)}
+                line['kernels_per_step'] = kernels_per_step(step)
+                line['graph_timeline'] = timeline_constants()
+            roof, inside, verts, model = rooflines(p, batch)
+            line['roofline'], line['roofline_inside_test'] = roof, inside
+            if args.config == '2':
+                # the whole step priced in SURVEY 8(d)'s units (67 FLOP per (query, face) pair of the body and of every closed
+                # segment, 8 FLOP per ordered vertex pair) over the measured step time: a multiple of the vector PEAK, because
+                # the step does not do that pair work (exact pruning, crossings instead of solid angles)
+                from tuch_amd.ops import segment_faces
+                body = p['body']
+                seg_pairs = sum(len(sg['vidx']) * len(segment_faces(body.faces, sg['vidx'], list(sg['bands'].values()), body.num_verts))
+                                for sg in body.segments.values())
+                eq = (FLOP_PER_WINDING_PAIR * (body.num_verts * body.num_faces + seg_pairs)
+                      + FLOP_PER_V2V_PAIR * body.num_verts ** 2) * batch
+                line['step_equivalent_flop'] = eq
+                line['step_equivalent_x_peak'] = round(eq / (dt / args.steps) / 1e12 / PEAK_FP32_VECTOR_TFLOPS, 2)
+            if world == 1 and backend == 'nccl' and not args.no_rccl_smoke:
+                line['rccl_smoke'] = rccl_smoke()
+            if world == 1 and not args.no_extras:
+                line['contact_loss_eval'] = contact_loss_eval(p, batch, verts, model)
+                line['shard_sweep'] = shard_sweep(device, 1002)
+                line['workloads'] = workloads(device, 1002)
+                line['worst_case'] = worst_case(device, 1002, batch)
+                line['worst_case']['folded'] = worst_case(device, 1002, batch, folded=True)
+                from tuch_amd import ops as ops_mod
+                line['deterministic'] = bool(ops_mod.deterministic())
+                line['float_atomics_mode'] = float_atomics_cost(device, 1002, batch)
+                line['headline_without_hints'] = headline_without_hints(device, 1002, batch)
+                line['irregular_topology'] = irregular_topology(device, 1002, batch)
+            if world == 1 and not args.no_cpu_baseline:
+                line['cpu_baseline'] = cpu_baseline(p, args.cpu_seconds)
+                if not args.no_torch_chain:
+                    line['cpu_baseline_torch_chain'] = cpu_torch_chain(p)
         print(json.dumps(line), flush=True)
     if world > 1:
         torch.distributed.destroy_process_group()

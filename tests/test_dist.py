@@ -189,7 +189,7 @@ def test_bench_spawns_its_own_ranks():
         env.pop(k, None)
     def run(*extra):
         res = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1',
-                              '--repeats', '2', '--no-extras', '--no-cpu-baseline'] + list(extra),
+                              '--repeats', '2', '--full', '--no-extras', '--no-cpu-baseline'] + list(extra),
                              env=env, capture_output=True, text=True, timeout=900)
         assert res.returncode == 0, res.stderr[-3000:]
         lines = [l for l in res.stdout.splitlines() if l.startswith('{')]
@@ -231,7 +231,7 @@ def test_rccl_on_one_gpu_and_the_bench_selfcheck():
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'TUCH_BENCH_BACKEND'):
         env.pop(k, None)
     res = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '5', '--warmup', '2', '--repeats', '1',
-                          '--no-extras', '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=1200)
+                          '--full', '--no-extras', '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=1200)
     assert res.returncode == 0, res.stderr[-3000:]
     line = json.loads([l for l in res.stdout.splitlines() if l.startswith('{')][-1])
     sc = line['selfcheck']
