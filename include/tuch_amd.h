@@ -465,6 +465,28 @@ int tuch_estimate_translation(const float* joints3d, const float* keypoints2d, c
                               float focal_length, float img_size, float* trans, void* stream);
 int tuch_rotmat_to_angle_axis(const float* rotmat, int N, int row_stride, float* angle_axis, void* stream);
 
+/* ---- pose evaluation (csrc/pose_eval.hip) -----------------------------------------------------------
+ * tuch_procrustes: tuch/utils/pose_utils.py:28-92 (compute_similarity_transform, its _batch loop and
+ * reconstruction_error; eval.py:194 calls it once per batch on host copies).  S1, S2 [B,N,D] or, with coords_first,
+ * [B,D,N] (the reference reads a per-body matrix whose first axis is 2 or 3 as coordinates x points,
+ * pose_utils.py:35-39); D = 2 or 3; float (is_double = 0) or double (1).  S1_hat (optional, same layout and type) =
+ * scale R S1 + t with R = V Z U^T from the SVD of K = X1 X2^T; err [B] = reconstruction_error(S1, S2, None): the
+ * root of the sum over the LAST axis of the given layout, averaged over the other.  float64 inside; all points of S1
+ * equal -> NaN, as in the reference.
+ * tuch_pose_metrics: eval.py:158-195 and tuch/train/trainer.py:229-255 for one batch in one launch.
+ * pred_vertices [B,V,3]; exactly one of gt_vertices [B,V,3] (regressed like pred, pelvis subtracted) or gt_joints
+ * [B,J,3] (the mpi-inf-3dhp branch, eval.py:168-170: used as given); J_regressor [R,V] (R <= 24, every entry used);
+ * joint_map [J] (J <= 64; H36M_TO_J14 / _J17) into the R joints; the pelvis (row pelvis_index of the regressed
+ * joints) is taken before the map.  Per body: mpjpe [B], pa_mpjpe [B] (tuch_procrustes's error on the mapped
+ * joints), v2v [B] (optional; mean vertex distance, gt_vertices only) and joints [B,R,3] (optional; the regressed
+ * pred joints before the pelvis, eval.py:184).  Deterministic: no atomics; a body's outputs do not depend on the
+ * batch it is in.  A joint_map entry outside [0,R) gives NaN for that body (the binding checks before the launch). */
+int tuch_procrustes(const void* S1, const void* S2, int B, int N, int D, int coords_first, int is_double, void* S1_hat,
+                    void* err, void* stream);
+int tuch_pose_metrics(const float* pred_vertices, const float* gt_vertices, const float* gt_joints,
+                      const float* J_regressor, const int32_t* joint_map, int B, int V, int R, int J, int pelvis_index,
+                      float* mpjpe, float* pa_mpjpe, float* v2v, float* joints, void* stream);
+
 /* ---- the HD-mesh branch of RegressorLoss.contact_loss, tuch/train/loss.py:274-301, as one device pipeline ----
  * (csrc/hd_contact.hip).  tuch_hd_model holds the HD vertex regressor (loss.py:81-83) as its three non-zeros per
  * row -- hd_idx / hd_w [N,3] -- and faces_vert_is_sampled_from (loss.py:85-87) -- hd_face [N]; all host arrays, copied.

@@ -5,7 +5,7 @@
     from tuch.smplify.smplifydc import SMPLifyDC            # -> tuch_amd.smplify.smplifydc
     from tuch.train.trainer import Trainer                  # -> the reference checkout's own file
 
-Only the modules on the self-contact path are mapped.  Every other `tuch.*` module
+Only the modules on the self-contact path are mapped, plus `tuch.utils.pose_utils` (evaluation).  Every other `tuch.*` module
 (datasets, trainer, hmr, renderer, saver, ...) keeps coming from the reference checkout, wherever on
 sys.path it is and whether it was put there before or after install(): the reference's `tuch` is a
 namespace package (no __init__.py), and so are the packages install() registers -- their __path__ is
@@ -24,6 +24,7 @@ _MAP = {
     'tuch.utils.contact': 'tuch_amd.utils.contact',
     'tuch.utils.segmentation': 'tuch_amd.utils.segmentation',
     'tuch.utils.geometry': 'tuch_amd.utils.geometry',
+    'tuch.utils.pose_utils': 'tuch_amd.utils.pose_utils',
     'tuch.smplify.losses': 'tuch_amd.smplify.losses',
     'tuch.smplify.prior': 'tuch_amd.smplify.prior',
     'tuch.smplify.smplifydc': 'tuch_amd.smplify.smplifydc',
