@@ -83,7 +83,7 @@ def test_pose_prior_gradient_rides_with_the_body_model_within_one_backward_pass(
     """The fused stage-2 tail leaves the pose prior's gradient with the body model's autograd node (one add launch less
     per step).  Same gradients as autograd's own sum; and a gradient left behind by a backward pass that never reached
     the body model's node (only camera_t asked for) does not leak into a later pass through that node."""
-    from tuch_amd import ops
+    from tuch_amd import backward_pass
     from tuch_amd.smplify.losses import contact_fitting_loss
     batch = 3
     s = _setup(batch, 11)
@@ -107,9 +107,9 @@ def test_pose_prior_gradient_rides_with_the_body_model_within_one_backward_pass(
     node = out.vertices.grad_fn
     assert getattr(node, 'pose_ref', None) is not None and node.pose_ref() is bp   # the body model's node knows its pose tensor
     g_new = torch.autograd.grad(loss, [bp, go, cam], retain_graph=True)
-    assert node.pose_grad_extra is None                         # consumed
+    assert node.handover is None                                # consumed
     # autograd's own sum: the side channel off
-    monkeypatch.setattr(ops, '_graph_task_id', lambda: -1)
+    monkeypatch.setattr(backward_pass, 'pass_id', lambda: -1)   # (producer and consumer both ask this one function)
     bp2, go2, cam2, out2, loss2 = build()
     g_ref = torch.autograd.grad(loss2, [bp2, go2, cam2])
     monkeypatch.undo()
@@ -118,7 +118,7 @@ def test_pose_prior_gradient_rides_with_the_body_model_within_one_backward_pass(
         assert_close(a.cpu().numpy(), b.cpu().numpy(), 1e-5, 1e-6 * max(scale, float(b.abs().max())), 'grad ' + name)
     # a pass that stops in front of the body model leaves the prior's gradient with its node ...
     torch.autograd.grad(loss, [cam], retain_graph=True)
-    assert node.pose_grad_extra is not None
+    assert node.handover is not None and node.handover.pose_grad is not None
     # ... and a later pass through the node alone must not pick it up
     g_alone = torch.autograd.grad(out.vertices.sum(), [bp], retain_graph=True)[0]
     bp3, go3, cam3, out3, loss3 = build()
@@ -565,19 +565,14 @@ def test_stage1_objective_in_one_launch_vs_reference_and_torch_ops(shape_w):
             assert gb1 is None or not gb1.any()
 
 
-def test_fixed_point_vertex_gradient_reaches_every_kind_of_backward_pass():
-    """Deterministic mode (the default): the stage-2 node leaves its vertex gradient in 64-bit fixed-point accumulators and
-    the body model's skinning adjoint reads them there -- no conversion launch in a fit's `objective.backward()`.  Every
-    other way of asking gets the same numbers: loss.backward() (not through ops.backward_scalar), a scaled loss, the
-    gradient of the vertices themselves (torch.autograd.grad / retain_grad), a loss with a further term."""
-    from tuch_amd import ops
+def _deterministic_stage2_graph(seed=41):
+    """graph(): a fresh stage-2 graph (body model + objective) per call -> body_pose, global_orient, the body model's output, loss"""
     from tuch_amd.smplify.losses import contact_fitting_loss
     batch = 3
-    s = _setup(batch, 41)
+    s = _setup(batch, seed)
     body, t = s['body'], s['t']
     gm = t(body.geodesics > 0.3)
     face_tensor = t(body.faces)[None].repeat(batch, 1, 1)
-    assert ops.deterministic()
 
     def graph(retain=False):
         bp = t(s['bp']).requires_grad_(True)
@@ -592,6 +587,17 @@ def test_fixed_point_vertex_gradient_reaches_every_kind_of_backward_pass():
                                     torch.ones(batch, dtype=torch.bool, device=DEV), out.vertices,
                                     face_tensor=face_tensor, contact_loss_weight=2000.0, segments=s['segments'])
         return bp, go, out, loss
+    return graph
+
+
+def test_fixed_point_vertex_gradient_reaches_every_kind_of_backward_pass():
+    """Deterministic mode (the default): the stage-2 node leaves its vertex gradient in 64-bit fixed-point accumulators and
+    the body model's skinning adjoint reads them there -- no conversion launch in a fit's `objective.backward()`.  Every
+    other way of asking gets the same numbers: loss.backward() (not through ops.backward_scalar), a scaled loss, the
+    gradient of the vertices themselves (torch.autograd.grad / retain_grad), a loss with a further term."""
+    from tuch_amd import ops
+    assert ops.deterministic()
+    graph = _deterministic_stage2_graph()
     with ops.off_default_stream(DEV):
         bp, go, _, loss = graph()
         ops.backward_scalar(loss)                                   # the fit's pass: accumulators handed to the body model
@@ -625,3 +631,50 @@ def test_fixed_point_vertex_gradient_reaches_every_kind_of_backward_pass():
         bp4, go4, out4, _ = graph()
         (out4.vertices ** 2).sum().backward()
         assert_close(bp.grad.cpu().numpy(), (want_bp + bp4.grad).cpu().numpy(), 1e-5, 1e-6 * float(want_bp.abs().max()), 'with a further term')
+
+
+def test_second_pass_over_a_retained_graph_gives_the_first_pass_its_gradients():
+    """Deterministic mode: the fixed-point accumulators of the stage-2 node outlive its first backward (they are only read),
+    so a second pass over a retained graph finds the vertex gradient again -- not the carrier of zeros."""
+    from tuch_amd import ops
+    assert ops.deterministic()
+    graph = _deterministic_stage2_graph()
+    with ops.off_default_stream(DEV):
+        bp, go, _, loss = graph()
+        first = torch.autograd.grad(loss, [bp, go], retain_graph=True)
+        second = torch.autograd.grad(loss, [bp, go], retain_graph=True)
+        bp2, go2, _, loss2 = graph()
+        fresh = torch.autograd.grad(loss2, [bp2, go2])
+        torch.cuda.synchronize()
+    assert float(fresh[0].abs().max()) > 0 and float(fresh[1].abs().max()) > 0
+    for a, b, c, name in zip(first, second, fresh, ('body_pose', 'global_orient')):
+        assert torch.equal(a, c), 'first pass, ' + name
+        assert torch.equal(b, c), 'second pass, ' + name
+
+
+@pytest.mark.parametrize('how', ['retain_grad', 'hook'])
+def test_vertices_watched_after_the_loss_was_built_see_their_gradient(how):
+    """Deterministic mode: retain_grad() / register_hook() on the vertices AFTER the loss was built and before
+    ops.backward_scalar(loss): the watcher sees the vertex gradient, not the carrier of zeros, and the fit's pose
+    gradients are the plain fit's."""
+    from tuch_amd import ops
+    assert ops.deterministic()
+    graph = _deterministic_stage2_graph()
+    with ops.off_default_stream(DEV):
+        bp, go, _, loss = graph()
+        ops.backward_scalar(loss)                                   # the plain fit
+        want_bp, want_go = bp.grad.clone(), go.grad.clone()
+        bp, go, out, loss = graph()
+        want_gv, = torch.autograd.grad(loss, out.vertices)
+        assert float(want_gv.abs().max()) > 0
+        bp, go, out, loss = graph()
+        seen = []
+        if how == 'retain_grad':
+            out.vertices.retain_grad()
+        else:
+            out.vertices.register_hook(lambda g: seen.append(g.clone()))
+        ops.backward_scalar(loss)
+        torch.cuda.synchronize()
+    got = out.vertices.grad if how == 'retain_grad' else seen[0]
+    assert torch.equal(got, want_gv)
+    assert torch.equal(bp.grad, want_bp) and torch.equal(go.grad, want_go)

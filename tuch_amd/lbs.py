@@ -9,7 +9,7 @@ import weakref
 import numpy as np
 import torch
 
-from . import _C
+from . import _C, backward_pass
 
 
 class SmplDeviceModel:
@@ -79,14 +79,11 @@ class _SmplLBS(torch.autograd.Function):
         ctx.dm, ctx.pose2rot = dm, bool(pose2rot)
         ctx.shapes = (global_orient.shape, body_pose.shape)
         # A later node that holds ANOTHER gradient for the same body_pose (ops._Stage2Tail: the pose prior) may leave it in
-        # pose_grad_extra instead of returning it: backward() then adds it inside its last kernel and autograd has nothing
-        # left to sum (one add launch less per step).  pose_ref: how that node recognises the tensor -- by IDENTITY (the very
-        # tensor object this node will return a gradient for; an alias with the same address and shape is another leaf).
+        # `handover` (backward_pass) instead of returning it: backward() adds it inside its last kernel, one add launch less.
+        # pose_ref: how that node recognises the tensor -- by IDENTITY (an alias with the same address and shape is another leaf)
         ctx.pose_ref = weakref.ref(body_pose) if ctx.needs_input_grad[2] else None
         ctx.orient_ref = weakref.ref(global_orient) if ctx.needs_input_grad[1] else None
-        ctx.pose_grad_extra = None
-        ctx.verts_grad_fixed = None   # set by ops._Stage2Tail.backward (deterministic mode): (fixed-point vertex gradient, pass id)
-        ctx.root_pass = None          # set by ops._Stage2Tail.backward: the id of a backward pass whose ROOT is that node
+        ctx.handover = None
         ctx.save_for_backward(go, bp, ws)
         return verts, joints
 
@@ -94,8 +91,7 @@ class _SmplLBS(torch.autograd.Function):
     def backward(ctx, g_verts, g_joints):
         L = _C.lib()
         go, bp, ws = ctx.saved_tensors
-        b = go.shape[0]
-        w = go.shape[1]
+        b, w = go.shape
         if g_verts is None and g_joints is None:
             return None, None, None, None, None, None
         gv = g_verts.to(torch.float32).contiguous() if g_verts is not None else None
@@ -114,23 +110,17 @@ class _SmplLBS(torch.autograd.Function):
             return g_betas, None, None, None, None, g_full
         g_go = torch.empty(go.shape, dtype=torch.float32, device=go.device)
         g_bp = torch.empty(bp.shape, dtype=torch.float32, device=go.device)
-        tagged, ctx.pose_grad_extra = ctx.pose_grad_extra, None
-        extra = None
-        f = getattr(torch._C, '_current_graph_task_id', None)
-        task = int(f()) if f is not None else -1
-        if tagged is not None and task >= 0 and task == tagged[1]:          # left by a node of THIS backward pass
-            extra = tagged[0].to(torch.float32).reshape(b, 23 * w).contiguous()
-        # the stage-2 tail's vertex gradient as 64-bit fixed-point sums (deterministic mode, ops._Stage2Tail): read by the
+        # what ops._Stage2Tail left in THIS backward pass (backward_pass: the table of rules).  extra: the prior's gradient,
+        # added to g_bp.  fixed: that node's vertex gradient as 64-bit fixed-point sums (deterministic mode), read by the
         # skinning adjoint itself, added to g_verts (zeros from that node, plus whatever else flows into the vertices)
-        tagged_fixed, ctx.verts_grad_fixed = ctx.verts_grad_fixed, None
-        fixed = tagged_fixed[0] if tagged_fixed is not None and task >= 0 and task == tagged_fixed[1] else None
+        left = backward_pass.take(ctx)
+        extra, fixed = (left.pose_grad, left.verts_fixed) if left is not None else (None, None)
+        if extra is not None:
+            extra = extra.to(torch.float32).reshape(b, 23 * w).contiguous()
         # Adam inside the last backward kernel (optim.Adam(fuse_backward=True)): only when this pass's root is the stage-2
-        # objective node, which has routed the prior's gradient here -- then what this call computes IS the whole gradient
-        # of the two pose tensors
+        # objective node, which has routed the prior's gradient here -- this call then computes the WHOLE pose gradient
         adam = None
-        root_pass, ctx.root_pass = ctx.root_pass, None
-        if ctx.pose2rot and extra is not None and task >= 0 and root_pass == task and ctx.orient_ref is not None \
-                and not ctx.needs_input_grad[0]:
+        if ctx.pose2rot and extra is not None and left.root and ctx.orient_ref is not None and not ctx.needs_input_grad[0]:
             from . import optim
             go_t, bp_t = ctx.orient_ref(), ctx.pose_ref() if ctx.pose_ref is not None else None
             adam = optim.fusable_for(go_t, bp_t)
@@ -139,10 +129,8 @@ class _SmplLBS(torch.autograd.Function):
                                          and bp_t.data_ptr() == bp.data_ptr()):
                 adam = None
         if adam is not None and adam._applied:
-            # a second backward pass before step() / zero_grad(): the first pass has already moved the parameters; applying
-            # another update here would be a second optimiser step nobody asked for -- this pass only returns gradients.
-            # (Gradient ACCUMULATION over several backward passes is not what fuse_backward can do: the first pass has stepped
-            # with its own gradient alone; torch.optim.Adam would step once with the sum.)
+            # a second backward pass before step() / zero_grad(): another update here would be a second optimiser step nobody
+            # asked for -- this pass only returns gradients (torch.optim.Adam would step once, with the sum over the passes)
             import warnings
             warnings.warn('tuch_amd.optim.Adam(fuse_backward=True): a second backward pass before step() -- the parameters '
                           'were already updated with the first pass\'s gradient; use fuse_backward=False to accumulate '

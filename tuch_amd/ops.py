@@ -8,13 +8,15 @@ from __future__ import annotations
 import contextlib
 import ctypes
 import os
+import weakref
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import _C
+from . import _C, backward_pass
+from .backward_pass import backward_scalar          # noqa: F401 (the fitting loops and the bench call ops.backward_scalar)
 
 MODE_SMPLIFY = 0   # tuch/smplify/losses.py:96-105
 MODE_TRAIN = 1     # tuch/train/loss.py:303-315
@@ -27,8 +29,6 @@ def _f32(t: torch.Tensor) -> torch.Tensor:
 
 
 _SIDE_STREAMS = {}
-
-
 _STREAM_OBJECTS = {}
 
 
@@ -105,36 +105,6 @@ def set_deterministic(on: bool) -> None:
     bit for bit (stage-2 tail, SMPL adjoint, the training loss's plain term -- _ContactTerms -- and its HD term).
     Graphs captured before the switch keep the mode they were captured in."""
     _C.lib().tuch_set_deterministic(int(bool(on)))
-
-
-_ONES = {}
-_ROOT_NODES = {}     # id(node) -> node: the autograd nodes of the losses of the RUNNING backward_scalar() calls (a plain dict:
-                     # the engine runs a device's nodes on its own worker thread, a thread-local would be invisible there)
-
-
-def backward_scalar(loss: torch.Tensor) -> None:
-    """``loss.backward()`` for a scalar loss with the seed gradient (ones) taken from a cache: autograd otherwise fills a
-    fresh one per call, a launch of its own at the head of every backward chain.  The loss's own autograd node is
-    remembered for the duration of the pass: a node that finds ITSELF there is the root of the pass -- every gradient of
-    the pass flows through what it returns (what ops._Stage2Tail needs to know before it lets the body model's backward
-    kernel apply the optimiser's update; the seed's address alone does not say so: AddBackward hands the same tensor on)."""
-    key = (loss.device, loss.dtype, tuple(loss.shape))
-    seed = _ONES.get(key)
-    if seed is None:
-        seed = _ONES[key] = torch.ones(loss.shape, dtype=loss.dtype, device=loss.device)
-    node = loss.grad_fn
-    if node is not None:
-        _ROOT_NODES[id(node)] = node
-    try:
-        loss.backward(gradient=seed)
-    finally:
-        if node is not None:
-            _ROOT_NODES.pop(id(node), None)
-
-
-def is_root_of_backward_scalar(node) -> bool:
-    """True inside a backward pass started by backward_scalar() on the output of exactly this autograd node."""
-    return node is not None and _ROOT_NODES.get(id(node)) is node
 
 
 def _workspace(nbytes: int, device) -> torch.Tensor:
@@ -567,7 +537,7 @@ class _Stage1Objective(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, g):
         gj, gc, gb = ctx.saved_tensors
-        if not any(g.data_ptr() == seed.data_ptr() for seed in _ONES.values()):
+        if not backward_pass.is_unit_seed(g):
             g = g.reshape(()).to(torch.float32)
             gj, gc, gb = gj * g, gc * g, (gb * g if gb is not None else None)
         dj, dc, db = ctx.in_dtypes
@@ -583,12 +553,6 @@ def smplify_stage1_objective(joints, camera_t, betas, camera_t_est, camera_cente
                              depth_weight, shape_weight):
     return _Stage1Objective.apply(joints, camera_t, betas, camera_t_est, camera_center, joints_2d, joints_conf, focal, sigma,
                                   depth_weight, shape_weight)
-
-
-def _graph_task_id() -> int:
-    """id of the running autograd backward pass (-1 outside one, or where this torch build has no such query)"""
-    f = getattr(torch._C, '_current_graph_task_id', None)
-    return int(f()) if f is not None else -1
 
 
 class _Stage2Tail(torch.autograd.Function):
@@ -654,16 +618,15 @@ class _Stage2Tail(torch.autograd.Function):
                                              _C.ptr(_extra[7]), None, _C.ptr(out), _C.ptr(gv) if fixed is None else None,
                                              model._handle if p else None, _C.ptr(_extra[0]),
                                              _C.ptr(fixed), _C.stream()))
-        ctx.fixed = fixed
         if want_grad:
-            ctx.save_for_backward(gv, gj, gc, gp)
+            # (fixed: a view of gv's buffer, only read by backward() and the skinning adjoint; saved like the others, so a
+            # retained graph's next pass finds it again and a plain pass releases the buffer where it always did)
+            ctx.save_for_backward(gv, gj, gc, gp, fixed)
         ctx.in_dtypes = (verts.dtype, joints.dtype, camera_t.dtype, body_pose.dtype)
-        # body_pose also feeds the body model that made `verts`: that node's backward runs after this one (it waits for the
-        # vertex gradient) and can add the prior's pose gradient inside its own last kernel (lbs._SmplLBS: pose_grad_extra)
-        # instead of autograd summing two gradients in a launch of its own
+        # body_pose also feeds the body model that made `verts`: that node's backward runs after this one and can add the prior's
+        # pose gradient inside its own last kernel (backward_pass.Handover): autograd then has no two gradients to sum in a launch
         node = verts.grad_fn
-        # (somebody who retains / hooks the vertices' own gradient must see the real numbers, not the carrier of zeros)
-        ctx.verts_unwatched = not verts.retains_grad and not getattr(verts, '_backward_hooks', None)
+        ctx.verts_ref = weakref.ref(verts)          # backward() asks whether somebody watches the vertices' own gradient
         ref = getattr(node, 'pose_ref', None) if node is not None else None
         ctx.lbs_node = node if (want_grad and ctx.needs_input_grad[0] and ctx.needs_input_grad[3] and ref is not None
                                 and ref() is body_pose) else None
@@ -672,37 +635,28 @@ class _Stage2Tail(torch.autograd.Function):
     @staticmethod
     @once_differentiable          # the gradients were formed in forward(): constants of a second differentiation
     def backward(ctx, g):
-        gv, gj, gc, gp = ctx.saved_tensors
+        gv, gj, gc, gp, fixed = ctx.saved_tensors
         dv, dj, dc, dp = ctx.in_dtypes
-        # loss.backward() through ops.backward_scalar seeds the graph with a cached tensor of ones: recognised by its
-        # address (no device round trip).  Any other upstream gradient scales the unit gradients.
-        unit = any(g.data_ptr() == seed.data_ptr() for seed in _ONES.values())
-        fixed, ctx.fixed = ctx.fixed, None
-        hand_over = (fixed is not None and unit and ctx.lbs_node is not None and _graph_task_id() >= 0
-                     and is_root_of_backward_scalar(ctx) and ctx.verts_unwatched)
+        # (the rules of what follows: the table of backward_pass.  root: not a loss like `tail + other(body_pose)`, which
+        # reaches this node with the same unit seed, but whose pose gradient does not all flow through here)
+        task = backward_pass.pass_id()
+        unit = backward_pass.is_unit_seed(g)
+        root = unit and backward_pass.is_root(ctx)
+        leave = ctx.lbs_node is not None and task >= 0
+        # (somebody who retains / hooks the vertices' own gradient must see the real numbers, not the carrier of zeros;
+        # asked NOW: both can be added after the loss was built.  Nobody holds a tensor that is gone: no .grad to fill)
+        verts = ctx.verts_ref()
+        watched = verts is not None and (verts.retains_grad or bool(getattr(verts, '_backward_hooks', None)))
+        hand_over = fixed is not None and leave and root and not watched
         if fixed is not None and not hand_over:
-            # anything but the plain backward of a fit (a scaled upstream gradient, a gradient asked for the vertices
-            # themselves, a loss with further terms): the float gradient, by a conversion launch
+            # anything but the plain backward of a fit (scaled, watched vertices, further terms): the float gradient, converted
             gv = torch.empty_like(gv)
             _C.check(_C.lib().tuch_fixed_to_float(_C.ptr(fixed), fixed.numel(), _C.ptr(gv), _C.stream()))
         if not unit:
             g = g.reshape(()).to(torch.float32)
             gv, gj, gc, gp = gv * g, gj * g, gc * g, gp * g
-        # the ROOT of the pass: backward_scalar() was called on THIS node's output (a loss like `tail + other(body_pose)`
-        # reaches this node with the same unit seed -- AddBackward forwards it unchanged -- but then not every gradient of
-        # the parameters flows through here, and the optimiser's update must not be applied from this node's gradient alone)
-        root = unit and is_root_of_backward_scalar(ctx)
-        if ctx.lbs_node is not None and _graph_task_id() >= 0:
-            # tagged with THIS backward pass: the body model's node takes it only within the same pass (a gradient left by
-            # a pass that never reached that node must not leak into a later one)
-            ctx.lbs_node.pose_grad_extra = (gp, _graph_task_id())
-            if hand_over:
-                ctx.lbs_node.verts_grad_fixed = (fixed, _graph_task_id())
-            # this node is the ROOT of the pass (see above): every gradient of the fit's parameters flows through what it
-            # returns -- the body model's node may then apply the optimiser's update itself (lbs.py)
-            ctx.lbs_node.root_pass = _graph_task_id() if root else None
-            return gv.to(dv), gj.to(dj), gc.to(dc), None, None, None, None, None
-        return gv.to(dv), gj.to(dj), gc.to(dc), gp.to(dp), None, None, None, None
+        left = leave and backward_pass.leave(ctx.lbs_node, backward_pass.Handover(task, gp, fixed if hand_over else None, root))
+        return gv.to(dv), gj.to(dj), gc.to(dc), None if left else gp.to(dp), None, None, None, None
 
 
 def smplify_stage2_tail(verts, joints, camera_t, body_pose, model, valid_u8, select_u8, **const):
@@ -962,59 +916,39 @@ class ContactModel:
         inside after all are searched again, exhaustively, behind the inside test (v2v_fix).  For every other vertex min_d2
         is cap^2 and the partner some admissible vertex farther than cap.  Exact for what the caller uses; see
         include/tuch_amd.h: tuch_v2v_min_model_capped."""
-        zero = None
-        if zero_floats > 0:
-            zero = torch.empty((int(zero_floats) + 3) // 4 * 4, dtype=torch.float32, device=verts.device)
-            call_also = (lambda: also(zero)) if also is not None else None
-        else:
-            call_also = also
+        zero = torch.empty((int(zero_floats) + 3) // 4 * 4, dtype=torch.float32, device=verts.device) if zero_floats > 0 else None
+        call_also = (lambda: None) if also is None else also if zero is None else (lambda: also(zero))
         capped = cap is not None and verts.is_cuda and self.v2v_can_cap(verts.shape[0])
-        if not (verts.is_cuda and self._py_options['overlap']):
-            exterior = self.exterior_flags(verts, apply_segments=apply_segments)
-            if capped:
-                mn, partner, state = self.v2v_min(verts, zero=zero, iterative=iterative, cap=cap)
-                self.v2v_fix(exterior, mn, partner, state)
-            else:
-                mn, partner = self.v2v_min(verts, zero=zero, iterative=iterative)
-            return exterior, mn, partner, (call_also() if call_also is not None else None)
-        cur = _current_stream(verts.device)
-        side = _side_stream(verts.device)
-        side.wait_stream(cur)
-        if capped:
-            v = _f32(verts)
-            exterior = self.exterior_flags(v, apply_segments=apply_segments)     # (the inside test's chain first, as below)
-            with torch.cuda.stream(side):
-                if zero is not None:
-                    zero.record_stream(side)
-                mn, partner, state = self.v2v_min(v, leave_room=True, zero=zero, iterative=iterative, cap=cap)
-                extra = call_also() if call_also is not None else None
-            cur.wait_stream(side)
-            for t in (mn, partner, state[0]) + (tuple(extra) if isinstance(extra, (tuple, list)) else (extra,)):
-                if torch.is_tensor(t):
-                    t.record_stream(cur)
-            self.v2v_fix(exterior, mn, partner, state)       # behind both: the final flags, the capped search's keys
-            return exterior, mn, partner, extra
-        first = self._py_options.get('inside_first', 0)
-        if first:
-            # the inside test's chain FIRST (the side stream waits only for what was enqueued before its wait above).
-            # Launched -- or captured -- behind the search, the chain's small head kernels find every wave slot taken by
-            # the search's 55 k one-wave workgroups and only get going when it is done (eager: ray_leaf_bounds 119 us
-            # instead of 14; replayed graph at batch 8: 0.240 against 0.213 ms once tree_inner_bounds_kernel no longer
-            # delays the search's start)
-            exterior = self.exterior_flags(verts, apply_segments=apply_segments)
-        with torch.cuda.stream(side):
-            if zero is not None:
+        overlap = bool(verts.is_cuda and self._py_options['overlap'])
+        if overlap:
+            cur, side = _current_stream(verts.device), _side_stream(verts.device)
+            side.wait_stream(cur)       # BEFORE the inside test is enqueued: the search does not wait for it
+        # the inside test's chain FIRST (the side stream waits only for what was enqueued before its wait above).
+        # Launched -- or captured -- behind the search, the chain's small head kernels find every wave slot taken by
+        # the search's 55 k one-wave workgroups and only get going when it is done (eager: ray_leaf_bounds 119 us
+        # instead of 14; replayed graph at batch 8: 0.240 against 0.213 ms once tree_inner_bounds_kernel no longer
+        # delays the search's start).  (v2v_fix needs the flags: a capped search has the inside test first in any case)
+        first = not overlap or capped or self._py_options.get('inside_first', 0)
+        exterior = self.exterior_flags(verts, apply_segments=apply_segments) if first else None
+        with (torch.cuda.stream(side) if overlap else contextlib.nullcontext()):
+            if overlap and zero is not None:
                 zero.record_stream(side)
-            mn, partner = self.v2v_min(verts, leave_room=True, zero=zero, iterative=iterative)
+            mn, partner, *state = self.v2v_min(verts, leave_room=overlap, zero=zero, iterative=iterative,
+                                               cap=cap if capped else None)         # state: [(workspace, ...)] if capped
+            if capped and not overlap:
+                self.v2v_fix(exterior, mn, partner, state[0])
             # (the caller's extra work -- region pairs, reprojection + prior -- FIRST, beside the short head of the inside
             # test's chain, was measured: 0.587 against 0.552 ms per step; it delays the search, which the chain waits for)
-            extra = call_also() if call_also is not None else None
+            extra = call_also()
         if not first:
             exterior = self.exterior_flags(verts, apply_segments=apply_segments)
-        cur.wait_stream(side)
-        for t in (mn, partner) + (tuple(extra) if isinstance(extra, (tuple, list)) else (extra,)):
-            if torch.is_tensor(t):
-                t.record_stream(cur)
+        if overlap:
+            cur.wait_stream(side)
+            for t in (mn, partner, *(st[0] for st in state), *(extra if isinstance(extra, (tuple, list)) else (extra,))):
+                if torch.is_tensor(t):
+                    t.record_stream(cur)
+            if capped:
+                self.v2v_fix(exterior, mn, partner, state[0])       # behind both: the final flags, the capped search's keys
         return exterior, mn, partner, extra
 
     def winding_tree_work(self, verts: torch.Tensor) -> dict:

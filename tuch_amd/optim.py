@@ -66,10 +66,9 @@ class Adam:
         self._v = ptrs([self.state[p]['exp_avg_sq'] for p in self.params])
         self.param_groups = [{'params': self.params, 'lr': self.lr, 'betas': tuple(betas), 'eps': self.eps}]
         # fuse_backward (opt-in, SMPLify-DC stage 2): when the parameters are exactly the body model's two pose tensors and
-        # the WHOLE gradient of the objective reaches them through one _SmplLBS node (ops._Stage2Tail is the root of the graph
-        # and routes the pose prior's gradient through that node), the node's last backward kernel applies this update itself
-        # (tuch_smpl_backward_split_adam) and the following step() is a no-op: one launch less at the end of every iteration.
-        # NOTE the consequence: with fuse_backward the parameters move during loss.backward(), not during step().
+        # the WHOLE gradient of the objective reaches them through one _SmplLBS node (the rules: backward_pass), the node's last
+        # backward kernel applies this update itself (tuch_smpl_backward_split_adam) and the following step() is a no-op: one
+        # launch less per iteration.  NOTE: with fuse_backward the parameters move during loss.backward(), not during step().
         self._applied = False
         self._ticket = torch.zeros(1, dtype=torch.int32, device=dev)
         self.fuse_backward = bool(fuse_backward)
