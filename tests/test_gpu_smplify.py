@@ -678,3 +678,165 @@ def test_vertices_watched_after_the_loss_was_built_see_their_gradient(how):
     got = out.vertices.grad if how == 'retain_grad' else seen[0]
     assert torch.equal(got, want_gv)
     assert torch.equal(bp.grad, want_bp) and torch.equal(go.grad, want_go)
+
+
+# ---- one fit driver, one loop runner: the options are properties of one flow, not a choice between two implementations
+_MERGED = {}
+
+
+def _merged_case(monkeypatch):
+    """Clears the fitter's environment switches (a test sets what it needs afterwards).  Inputs shared by the tests below (built once, never written): batch 3, contact with segments and region pairs, one
+    ignored body, has_gt_keypoints mixed; 'kept' = the outputs of a fresh default fitter (sessions kept, graphs on, 6 + 6)."""
+    monkeypatch.delenv('TUCH_SMPLIFY_SESSIONS', raising=False)
+    monkeypatch.delenv('TUCH_GRAPH_STRICT', raising=False)
+    if not _MERGED:
+        from tuch_amd.utils.geometry import perspective_projection
+        batch = 3
+        s = _setup(batch, 37)
+        t = s['t']
+        with torch.no_grad():
+            tgt = s['smpl'](global_orient=t(s['go']), body_pose=t(s['bp']) + 0.1, betas=t(s['be']))
+            j2d = perspective_projection(tgt.joints, torch.eye(3, device=DEV)[None].expand(batch, -1, -1),
+                                         t(s['cam_t']), 5000., torch.zeros(batch, 2, device=DEV))
+        _MERGED.update(
+            s=s, geod=t(s['body'].geodesics),
+            args=(torch.cat([t(s['go']), t(s['bp'])], 1), t(s['be']), t(s['cam_t']), torch.zeros(batch, 2, device=DEV),
+                  torch.cat([j2d, t(s['kp'][:, :, 2:])], 2)),
+            kwargs=dict(use_contact=True, contactlist=s['cdict'], gt_contact=[t(s['gt']), None],
+                        ignore_idxs=torch.tensor([False, True, False], device=DEV),
+                        has_discrete_contact=torch.ones(batch, dtype=torch.bool, device=DEV),
+                        has_gt_keypoints=torch.tensor([True, False, False], device=DEV),
+                        contact_loss_weight=2000.0, segments=s['segments']))
+        torch.cuda.synchronize()
+        fitter = _merged_fitter()
+        assert fitter.keep_sessions and not fitter.graph_strict
+        _MERGED['kept'] = _merged_fit(fitter)
+        assert fitter.graph_replayed == {'stage1': 3, 'stage2': 3} and len(fitter._sessions) == 1
+    return _MERGED
+
+
+def _merged_fitter(num_iters=6, **extra):
+    from tuch_amd.smplify.smplifydc import SMPLifyDC
+    s = _MERGED['s']
+    return SMPLifyDC(step_size=1e-2, batch_size=3, num_iters=num_iters, focal_length=5000., geodistssmpl=_MERGED['geod'],
+                     geothres=0.3, euclthres=0.02, device=torch.device(DEV), smpl=s['smpl'], pose_prior=s['prior'], **extra)
+
+
+def _merged_fit(fitter, **override):
+    out = fitter(*_MERGED['args'], **dict(_MERGED['kwargs'], **override))
+    torch.cuda.synchronize()
+    return [x.detach().clone() for x in out[:6]] + [v.detach().clone() for v in out[6]]
+
+
+def _assert_same_bits(got, want):
+    assert len(got) == len(want) == 6 + len(want[6:]) and len(want) > 6
+    for k, (a, b) in enumerate(zip(got, want)):
+        assert torch.equal(a, b), 'output %d' % k
+
+
+def test_kept_and_unkept_sessions_are_the_same_code(monkeypatch):
+    """TUCH_SMPLIFY_SESSIONS=0 only decides whether the session outlives the call: the same launches, the same bits in
+    the six tensors and in every entry of optiverts."""
+    kept = _merged_case(monkeypatch)['kept']
+    monkeypatch.setenv('TUCH_SMPLIFY_SESSIONS', '0')
+    fresh = _merged_fitter()
+    assert not fresh.keep_sessions
+    got = _merged_fit(fresh)
+    assert fresh.graph_replayed == {'stage1': 3, 'stage2': 3} and len(fresh._sessions) == 0
+    assert len(got) == 6 + 6
+    _assert_same_bits(got, kept)
+
+
+def test_recording_history_changes_nothing_else(monkeypatch):
+    """record_history adds clones around each iteration of the same loops: identical outputs, one record per iteration of
+    each stage, parameters recorded BEFORE the update, a fresh history per call."""
+    case = _merged_case(monkeypatch)
+    init_pose = case['args'][0]
+    fitter = _merged_fitter(record_history=True)
+    for call in range(2):                                # the second call (replays only) starts its history afresh
+        got = _merged_fit(fitter)
+        if call == 0:
+            _assert_same_bits(got, case['kept'])
+        history = fitter.history
+        assert len(history['stage1']) == len(history['stage2']) == 6
+        # stage 2 with contact optimises [body_pose, global_orient]; stage 1 does not move the body pose
+        assert torch.equal(history['stage2'][0]['params'][0], init_pose[:, 3:])
+        assert history['stage2'][0]['params'][1].shape == (3, 3)
+        assert not torch.equal(history['stage2'][-1]['params'][0], got[2][:, 3:])      # the last update came after the last record
+        assert all(torch.isfinite(h['loss']).all() and h['loss'].numel() == 1 for st in history.values() for h in st)
+    assert fitter.graph_replayed == {'stage1': 6, 'stage2': 6}
+
+
+class _RefusedCapture:
+    """Stands in for torch.cuda.graph: refuses before any capture begins (nothing on the GPU is made to fail)."""
+
+    def __init__(self, *args, **kwargs):
+        pass
+
+    def __enter__(self):
+        raise RuntimeError('capture refused by the test')
+
+    def __exit__(self, *exc):
+        return False
+
+
+def test_a_failed_capture_finishes_the_fit_eagerly(monkeypatch, caplog):
+    """The one fallback: the capture of the stage-1 loop raises -> one warning, the session is not kept, the remaining
+    iterations of stage 1 and all of stage 2 run eagerly through the same runner; the result is the eager fit's."""
+    import logging
+    _merged_case(monkeypatch)
+    eager = _merged_fit(_merged_fitter(use_graph=False))
+    fitter = _merged_fitter()
+    monkeypatch.setattr(torch.cuda, 'graph', _RefusedCapture)
+    with caplog.at_level(logging.WARNING, logger='tuch_amd.smplify.smplifydc'):
+        got = _merged_fit(fitter)
+    warnings = [r for r in caplog.records if r.name == 'tuch_amd.smplify.smplifydc' and r.levelno >= logging.WARNING]
+    assert len(warnings) == 1 and 'stage1' in warnings[0].getMessage()
+    assert fitter._sessions == {} and fitter.graph_replayed == {}
+    assert len(got) == len(eager) == 6 + 6
+    for a, b, name in zip(got[:6], eager[:6], ('verts', 'joints', 'pose', 'betas', 'cam', 'reproj')):
+        assert_close(a.cpu().numpy(), b.cpu().numpy(), 2e-3, 2e-4, name)
+    assert_close(got[-1].cpu().numpy(), eager[-1].cpu().numpy(), 2e-3, 2e-4, 'last optiverts')
+
+
+def test_a_failed_capture_raises_in_strict_mode(monkeypatch):
+    _merged_case(monkeypatch)
+    monkeypatch.setenv('TUCH_GRAPH_STRICT', '1')
+    fitter = _merged_fitter()
+    assert fitter.graph_strict
+    monkeypatch.setattr(torch.cuda, 'graph', _RefusedCapture)
+    with pytest.raises(RuntimeError, match='capture refused by the test'):
+        _merged_fit(fitter)
+    assert fitter._sessions == {}
+
+
+def test_contact_without_ignore_idxs_is_refused_early(monkeypatch):
+    _merged_case(monkeypatch)
+    fitter = _merged_fitter()
+    with pytest.raises(ValueError, match='ignore_idxs'):
+        _merged_fit(fitter, ignore_idxs=None)
+    assert fitter._sessions == {} and fitter.graph_replayed == {}
+
+
+def test_unkept_session_under_an_enclosing_capture(monkeypatch):
+    """Without kept sessions the fit still unrolls into an enclosing capture (it used to try a capture inside the
+    capture): the replayed graph gives the bits of the same fitter's own eager call."""
+    from tuch_amd import ops
+    case = _merged_case(monkeypatch)
+    monkeypatch.setenv('TUCH_SMPLIFY_SESSIONS', '0')
+    monkeypatch.setenv('TUCH_GRAPH_STRICT', '1')
+    fitter = _merged_fitter(num_iters=5)
+    assert not fitter.keep_sessions
+    with ops.off_default_stream(DEV):
+        warm = _merged_fit(fitter)
+        assert fitter.graph_replayed == {'stage1': 2, 'stage2': 2} and len(fitter._sessions) == 0
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=side, capture_error_mode='thread_local'):
+            res = fitter(*case['args'], **case['kwargs'])
+        torch.cuda.current_stream().wait_stream(side)
+        assert fitter.graph_replayed == {'stage1': 0, 'stage2': 0} and len(fitter._sessions) == 0
+        graph.replay()
+        torch.cuda.synchronize()
+    _assert_same_bits(list(res[:6]) + list(res[6]), warm)

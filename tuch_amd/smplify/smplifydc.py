@@ -7,17 +7,25 @@ Same constructor and ``__call__`` signature / 7-tuple return as the reference
     they do not ship; with the licensed files present the reference's paths are used;
   * the device follows the inputs (the reference hard-codes 'cuda', SURVEY.md F7);
   * the contact term of every iteration is one batched pass over the HIP kernels.
+
+One driver (``__call__``): get a session for the call's constants (static tensors, the three iteration closures, the two
+loops), copy the inputs into it, run stage 1, run stage 2, evaluate, return clones.  One loop runner (``_Stage.run``) with
+three modes: eager launches (``use_graph=False``, not a HIP device, ``num_iters <= 4``), unrolled into an enclosing capture,
+or three eager iterations + capture + replay (replay only on later calls of a kept session).  ``record_history`` and
+``TUCH_SMPLIFY_SESSIONS`` do not select other code: the first adds clones around each iteration, the second decides whether
+the session outlives the call.  One fallback: a capture that fails (and ``TUCH_GRAPH_STRICT`` unset) is logged, and the rest
+of the fit runs eagerly through the same runner.
 """
 from __future__ import annotations
 
+import contextlib
 import logging
 import os
 
 import numpy as np
 import torch
 
-from .losses import (body_fitting_loss, camera_fitting_loss, contact_fitting_loss, contact_model_for,
-                     stage2_objective)
+from .losses import body_fitting_loss, camera_fitting_loss, contact_model_for, stage2_objective
 from .prior import MaxMixturePrior
 from .. import ops
 from ..optim import make_adam
@@ -79,7 +87,7 @@ class SMPLifyDC():
         # *before* every update are kept per stage in self.history = {'stage1': [...], 'stage2': [...]}
         self.record_history = record_history
         # read once: TUCH_GRAPH_STRICT=1 turns a failed capture into an error (the tests set it), TUCH_SMPLIFY_SESSIONS=0
-        # makes every call capture its loops afresh
+        # makes every call build its session and capture its loops afresh
         self.graph_strict = os.environ.get('TUCH_GRAPH_STRICT', '0') == '1'
         self.keep_sessions = os.environ.get('TUCH_SMPLIFY_SESSIONS', '1') != '0'
         self.fused_adam = os.environ.get('TUCH_FUSED_ADAM', '1') != '0'      # 0: Adam as a launch of its own (A/B, tests)
@@ -89,130 +97,91 @@ class SMPLifyDC():
         # with SMPLify-DC in the loop runs 10 + 10 iterations per call, far too few to pay for two captures each time
         self._sessions = {}
 
-    def _optimise(self, params, iteration, num_iters, adam_kwargs, collect=None, stage=''):
-        """Run ``num_iters`` Adam iterations of ``iteration()`` (which returns (loss, vertices))."""
-        graph_ok = self.use_graph and params[0].is_cuda and num_iters > 4
-        # torch.optim.Adam's update as one launch where it applies (tuch_amd/optim.py), else torch's own
-        optimizer = make_adam(params, self.step_size, capturable=graph_ok, **adam_kwargs)
-        static = {}
-        history = self.history[stage] if self.record_history else None
-
-        def one():
-            if history is not None:
-                static['params'] = [p.detach().clone() for p in params]
-            loss, verts = iteration()
-            optimizer.zero_grad(set_to_none=graph_ok)
-            ops.backward_scalar(loss)
-            optimizer.step()
-            static['verts'] = verts
-            static['loss'] = loss.detach()
-            return verts
-
-        def keep():
-            if history is not None:
-                history.append({'loss': static['loss'].clone(), 'params': [p.clone() for p in static['params']]})
-
-        done = 0
-        if graph_ok:
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(3):
-                    verts = one()
-                    keep()
-                    if collect is not None:
-                        collect.append(verts.detach().clone())
-            torch.cuda.current_stream().wait_stream(side)
-            done = 3
-            try:
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph, capture_error_mode='thread_local'):
-                    one()
-            except Exception as exc:
-                # a loop that cannot be captured still runs (eagerly), but never silently: TUCH_GRAPH_STRICT=1
-                # (set by the tests) turns this into an error
-                if self.graph_strict:
-                    raise
-                log.warning('SMPLifyDC: hipGraph capture of the %s loop failed (%r); finishing with eager launches',
-                            stage, exc)
-                torch.cuda.synchronize()
-                graph = None
-            if graph is not None:
-                for _ in range(num_iters - done):
-                    graph.replay()
-                    keep()
-                    if collect is not None:
-                        collect.append(static['verts'].detach().clone())
-                self.graph_replayed[stage] = num_iters - done
-                return
-        for _ in range(num_iters - done):
-            verts = one()
-            keep()
-            if collect is not None:
-                collect.append(verts)
-
-    # ------------------------------------------------------------------ loops kept between calls
     class _Stage:
-        """One Adam loop on static tensors: three eager iterations + capture the first time, replays afterwards."""
+        """One Adam loop on a session's static tensors, and the only loop runner: eager launches, unrolled into an enclosing
+        capture, or three eager iterations + capture the first time and replays afterwards."""
 
         def __init__(self, owner, name, params, iteration, adam_kwargs, fuse_backward=False):
             self.owner, self.name, self.params, self.iteration = owner, name, params, iteration
             # fuse_backward (the contact stage 2: parameters = the body model's two pose tensors, objective = one root node):
             # the body model's last backward kernel applies Adam's update itself, step() is then a no-op (optim.py)
             self.optimizer = make_adam(params, owner.step_size, capturable=True, fuse_backward=fuse_backward, **adam_kwargs)
-            self.graph, self.verts, self.loss = None, None, None
+            self.graph, self.verts, self.loss, self.before = None, None, None, None
 
         def _one(self):
+            record = self.owner.record_history
+            if record:
+                self.before = [p.detach().clone() for p in self.params]
             loss, verts = self.iteration()
             self.optimizer.zero_grad(set_to_none=True)
             ops.backward_scalar(loss)
             self.optimizer.step()
-            self.verts, self.loss = verts, loss.detach()
+            self.verts, self.loss = verts, loss.detach().clone() if record else loss.detach()
 
-        def run(self, num_iters, collect):
+        def run(self, num_iters, collect, capture):
+            """Returns whether the loop ran captured (replayed or unrolled); False: eager launches, as asked for or because
+            the capture failed -- the caller then runs what is left of the fit eagerly and does not keep the session."""
+            owner = self.owner
             for state in self.optimizer.state.values():            # a fresh optimiser per call (smplifydc.py:117,150)
                 for v in state.values():
                     if torch.is_tensor(v):
                         v.zero_()
+            history = owner.history[self.name] if owner.record_history else None
+
+            def iterate(count, step):
+                for _ in range(count):
+                    step()
+                    if collect is not None:
+                        collect.append(self.verts.detach().clone())
+                    if history is not None:
+                        history.append({'loss': self.loss.clone(), 'params': [p.clone() for p in self.before]})
+            if not capture:
+                iterate(num_iters, self._one)
+                return False
             if torch.cuda.is_current_stream_capturing():
                 # an ENCLOSING capture is recording (TUCH.forward_train_step --run_smplify captured as one hipGraph: BASELINE
                 # config 5): a child graph cannot be replayed into it -- the iterations are unrolled into the enclosing graph
-                for _ in range(num_iters):
-                    self._one()
-                    if collect is not None:
-                        collect.append(self.verts.detach().clone())
-                self.owner.graph_replayed[self.name] = 0
-                return
+                iterate(num_iters, self._one)
+                owner.graph_replayed[self.name] = 0
+                return True
             done = 0
             if self.graph is None:
                 side = torch.cuda.Stream()
                 side.wait_stream(torch.cuda.current_stream())
                 with torch.cuda.stream(side):
-                    for _ in range(min(3, num_iters)):
-                        self._one()
-                        if collect is not None:
-                            collect.append(self.verts.detach().clone())
+                    iterate(3, self._one)
                 torch.cuda.current_stream().wait_stream(side)
-                done = min(3, num_iters)
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph, capture_error_mode='thread_local'):
-                    self._one()
+                done = 3
+                try:
+                    graph = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(graph, capture_error_mode='thread_local'):
+                        self._one()
+                except Exception as exc:
+                    # a loop that cannot be captured still runs (eagerly), but never silently: TUCH_GRAPH_STRICT=1
+                    # (set by the tests) turns this into an error
+                    if owner.graph_strict:
+                        raise
+                    log.warning('SMPLifyDC: hipGraph capture of the %s loop failed (%r); finishing with eager launches',
+                                self.name, exc)
+                    torch.cuda.synchronize()
+                    self.optimizer.zero_grad()       # a half-recorded fused update must not swallow the next step()
+                    iterate(num_iters - done, self._one)
+                    return False
                 self.graph = graph
-            for _ in range(num_iters - done):
-                self.graph.replay()
-                if collect is not None:
-                    collect.append(self.verts.detach().clone())
-            self.owner.graph_replayed[self.name] = num_iters - done
+            iterate(num_iters - done, self.graph.replay)
+            owner.graph_replayed[self.name] = num_iters - done
+            return True
 
     def _session(self, batch, use_contact, contactlist, segments, contact_loss_weight, with_pairs, like):
+        """(key, session): the static tensors, the three iteration closures and the two loops of a fit with these constants."""
         # everything a captured loop bakes in: the tables (the session keeps them alive, so their ids cannot be reused by
         # other objects) and the fitter's own settings -- changing one of those after a call starts a new session
         key = (batch, bool(use_contact), id(contactlist), id(segments), float(contact_loss_weight), bool(with_pairs),
                float(self.step_size), float(self.euclthres), float(self.focal_length), tuple(self.ign_joints),
-               id(self.pose_prior), int(self.num_iters))
+               id(self.pose_prior), int(self.num_iters), bool(self.record_history), bool(self.fused_adam))
         sess = self._sessions.get(key)
         if sess is not None:
-            return sess
+            return key, sess
         dev, f32 = like.device, torch.float32
         z = lambda *shape, dtype=f32: torch.zeros(*shape, dtype=dtype, device=dev)
         t = dict(body_pose=z(batch, 69), global_orient=z(batch, 3), betas=z(batch, 10), cam=z(batch, 3), init_cam=z(batch, 3),
@@ -245,59 +214,22 @@ class SMPLifyDC():
 
         def flags(bp, go, be, ct):
             body_pose.requires_grad, global_orient.requires_grad, betas.requires_grad, cam.requires_grad = bp, go, be, ct
-        sess = dict(t=t, flags=flags, use_contact=use_contact, keys_alive=(contactlist, segments, self.pose_prior))
-        # stage 1 optimises [betas, cam] with contact, [global_orient, cam] without (smplifydc.py:104-117)
-        flags(False, not use_contact, bool(use_contact), True)
-        sess['stage1'] = self._Stage(self, 'stage1', [betas, cam] if use_contact else [global_orient, cam], camera_iteration,
-                                     dict(betas=(0.9, 0.999)))
+        # stage 1 optimises [betas, cam] with contact, [global_orient, cam] without (smplifydc.py:104-117); stage 2 is built
+        # by the first call, once its flags are set
+        stage1_flags = (False, not use_contact, bool(use_contact), True)
+        flags(*stage1_flags)
+        sess = dict(t=t, flags=flags, stage1_flags=stage1_flags, stage2=None, keys_alive=(contactlist, segments, self.pose_prior),
+                    stage1=self._Stage(self, 'stage1', [betas, cam] if use_contact else [global_orient, cam], camera_iteration,
+                                       dict(betas=(0.9, 0.999))))
         if use_contact:
-            sess['stage2'] = (lambda: flags(True, True, False, False),
-                              lambda: self._Stage(self, 'stage2', [body_pose, global_orient], contact_iteration, {},
-                                                  fuse_backward=self.fused_adam))
+            sess['stage2_flags'] = (True, True, False, False)
+            sess['make_stage2'] = lambda: self._Stage(self, 'stage2', [body_pose, global_orient], contact_iteration, {},
+                                                      fuse_backward=self.fused_adam)
         else:
-            sess['stage2'] = (lambda: flags(True, True, True, False),
-                              lambda: self._Stage(self, 'stage2', [body_pose, betas, global_orient], body_iteration,
-                                                  dict(betas=(0.9, 0.999))))
-        while len(self._sessions) >= 4:
-            self._sessions.pop(next(iter(self._sessions)))
-        self._sessions[key] = sess
-        return sess
-
-    def _call_cached(self, init_pose, init_betas, init_cam_t, camera_center, keypoints_2d, use_contact, contactlist,
-                     gt_contact, ignore_idxs, has_discrete_contact, has_gt_keypoints, contact_loss_weight, segments):
-        batch = init_pose.shape[0]
-        with_pairs = gt_contact is not None and gt_contact[0] is not None
-        sess = self._session(batch, use_contact, contactlist, segments, contact_loss_weight, with_pairs, init_pose)
-        t = sess['t']
-        with torch.no_grad():
-            put = lambda dst, src: dst.copy_(src)
-            put(t['body_pose'], init_pose[:, 3:]); put(t['global_orient'], init_pose[:, :3]); put(t['betas'], init_betas)
-            put(t['cam'], init_cam_t); put(t['init_cam'], init_cam_t); put(t['centre'], camera_center)
-            put(t['j2d'], keypoints_2d[:, :, :2]); put(t['conf1'], keypoints_2d[:, :, -1])
-            put(t['conf2'], keypoints_2d[:, :, -1])
-            t['conf2'].index_fill_(1, self._ignored(t['conf2'].device), 0.0)                                         # smplifydc.py:153,198
-            if use_contact:
-                put(t['valid'], ~ignore_idxs)
-                if t.get('select') is not None:
-                    put(t['select'], (gt_contact[0] == 1) & has_discrete_contact.bool()[:, None] & (~ignore_idxs)[:, None])
-        sess['flags'](False, not use_contact, bool(use_contact), True)
-        sess['stage1'].run(self.num_iters, None)
-        set_flags, make_stage = sess['stage2']
-        set_flags()
-        if not isinstance(sess.get('stage2_obj'), self._Stage):
-            sess['stage2_obj'] = make_stage()
-        optiverts = []
-        sess['stage2_obj'].run(self.num_iters, optiverts)
-        with torch.no_grad():
-            out = self.smpl(global_orient=t['global_orient'], body_pose=t['body_pose'], betas=t['betas'], return_full_pose=True)
-            conf = t['conf2'].clone()
-            if has_gt_keypoints is not None:                                             # smplifydc.py:219-220, no host sync
-                conf[:, :25] = torch.where(has_gt_keypoints.bool()[:, None], torch.zeros_like(conf[:, :25]), conf[:, :25])
-            reprojection_loss = body_fitting_loss(t['body_pose'], t['betas'], out.joints, t['cam'], t['centre'], t['j2d'], conf,
-                                                  self.pose_prior, focal_length=self.focal_length, output='reprojection')
-        pose = torch.cat([t['global_orient'], t['body_pose']], dim=-1).detach().clone()
-        return (out.vertices.detach(), out.joints.detach(), pose, t['betas'].detach().clone(), t['cam'].detach().clone(),
-                reprojection_loss, optiverts if optiverts else None)
+            sess['stage2_flags'] = (True, True, True, False)
+            sess['make_stage2'] = lambda: self._Stage(self, 'stage2', [body_pose, betas, global_orient], body_iteration,
+                                                      dict(betas=(0.9, 0.999)))
+        return key, sess
 
     def __call__(self, init_pose, init_betas, init_cam_t,
                  camera_center, keypoints_2d, use_contact=False,
@@ -307,111 +239,57 @@ class SMPLifyDC():
                  contact_loss_return='sum', segments=None):
         """Fit a batch of bodies.  Returns (vertices, joints, pose, betas, camera_translation,
         reprojection_loss, optiverts) exactly like the reference (smplifydc.py:231-236)."""
-        if not (self.use_graph and init_pose.is_cuda):
-            return self._fit(init_pose, init_betas, init_cam_t, camera_center, keypoints_2d, use_contact, contactlist,
-                             gt_contact, ignore_idxs, has_discrete_contact, has_gt_keypoints, contact_loss_weight,
-                             contact_loss_return, segments)
-        from ..ops import off_default_stream
-        with off_default_stream(init_pose.device):       # graph replays never run on the NULL stream (ops.py)
-            return self._fit(init_pose, init_betas, init_cam_t, camera_center, keypoints_2d, use_contact, contactlist,
-                             gt_contact, ignore_idxs, has_discrete_contact, has_gt_keypoints, contact_loss_weight,
-                             contact_loss_return, segments)
-
-    def _fit(self, init_pose, init_betas, init_cam_t, camera_center, keypoints_2d, use_contact, contactlist, gt_contact,
-             ignore_idxs, has_discrete_contact, has_gt_keypoints, contact_loss_weight, contact_loss_return, segments):
-        if (self.use_graph and init_pose.is_cuda and self.num_iters > 4 and not self.record_history
-                and self.keep_sessions
-                and (not use_contact or (ignore_idxs is not None and isinstance(contactlist, (dict, list))))):
-            try:
-                return self._call_cached(init_pose, init_betas, init_cam_t, camera_center, keypoints_2d, use_contact,
-                                         contactlist, gt_contact, ignore_idxs, has_discrete_contact, has_gt_keypoints,
-                                         contact_loss_weight, segments)
-            except Exception as exc:
-                if self.graph_strict:
-                    raise
-                log.warning('SMPLifyDC: the cached hipGraph loops failed (%r); running this call without them', exc)
-                self._sessions.clear()
-                torch.cuda.synchronize()
+        if use_contact and ignore_idxs is None:
+            raise ValueError('SMPLifyDC: use_contact=True needs ignore_idxs, a [B] bool tensor (all False: every body gets '
+                             'contact terms)')
+        on_gpu = self.use_graph and init_pose.is_cuda
+        capture = on_gpu and self.num_iters > 4
         if self.record_history:
             self.history = {'stage1': [], 'stage2': []}
-        camera_translation = init_cam_t.clone()
-        joints_2d = keypoints_2d[:, :, :2].contiguous()
-        joints_conf = keypoints_2d[:, :, -1].clone()
-        body_pose = init_pose[:, 3:].detach().clone()
-        global_orient = init_pose[:, :3].detach().clone()
-        betas = init_betas.detach().clone()
-
-        # ---- stage 1: camera translation (+ shape with contact, + orientation without)
-        body_pose.requires_grad = False
-        camera_translation.requires_grad = True
-        global_orient.requires_grad = not use_contact
-        betas.requires_grad = bool(use_contact)
-        stage1 = [betas, camera_translation] if use_contact else [global_orient, camera_translation]
-        shape_prior_weight = 1.0 if use_contact else 0.0
-
-        def camera_iteration():
-            out = self.smpl(global_orient=global_orient, body_pose=body_pose, betas=betas)
-            return camera_fitting_loss(out, camera_translation, init_cam_t, camera_center, joints_2d,
-                                       joints_conf, focal_length=self.focal_length,
-                                       shape_prior_weight=shape_prior_weight), out.vertices
-
-        self._optimise(stage1, camera_iteration, self.num_iters, dict(betas=(0.9, 0.999)), stage='stage1')
-
-        # ---- stage 2: pose + global orientation
-        optiverts = []
-        joints_conf.index_fill_(1, self._ignored(joints_conf.device), 0.0)                        # smplifydc.py:153,198
-        camera_translation.requires_grad = False
-        # snapshots of the stage-1 result (smplifydc.py:141-142), taken before gradients are switched on:
-        # a clone of a leaf that requires grad would keep its AccumulateGrad node (created on the
-        # default stream) alive and break the graph capture of the loop below
-        pose_stage1 = body_pose.detach().clone()
-        orient_stage1 = global_orient.detach().clone()
-        body_pose.requires_grad = True
-        global_orient.requires_grad = True
-        if use_contact:
-            betas.requires_grad = False
-
-            def contact_iteration():
-                out = self.smpl(global_orient=global_orient, body_pose=body_pose, betas=betas)
-                loss = contact_fitting_loss(body_pose, global_orient, pose_stage1, orient_stage1,
-                                            betas, out.joints, self.geomask, self.euclthres,
-                                            camera_translation, camera_center, joints_2d, joints_conf,
-                                            self.pose_prior, cdict=contactlist, gt_contact=gt_contact,
-                                            ignore_idxs=ignore_idxs,
-                                            has_discrete_contact=has_discrete_contact,
-                                            verts=out.vertices, face_tensor=self.face_tensor,
-                                            focal_length=self.focal_length,
-                                            contact_loss_weight=contact_loss_weight,
-                                            output=contact_loss_return, segments=segments)
-                return loss, out.vertices
-
-            self._optimise([body_pose, global_orient], contact_iteration, self.num_iters, {}, optiverts, stage='stage2')
-        else:
-            betas.requires_grad = True
-
-            def body_iteration():
-                out = self.smpl(global_orient=global_orient, body_pose=body_pose, betas=betas)
-                return body_fitting_loss(body_pose, betas, out.joints, camera_translation, camera_center,
-                                         joints_2d, joints_conf, self.pose_prior,
-                                         focal_length=self.focal_length), out.vertices
-
-            self._optimise([body_pose, betas, global_orient], body_iteration, self.num_iters,
-                           dict(betas=(0.9, 0.999)), optiverts, stage='stage2')
-        if len(optiverts) == 0:
-            optiverts = None
-
-        # ---- final evaluation
-        with torch.no_grad():
-            out = self.smpl(global_orient=global_orient, body_pose=body_pose, betas=betas,
-                            return_full_pose=True)
-            if has_gt_keypoints is not None:
-                joints_conf[has_gt_keypoints, :25] = 0
-            reprojection_loss = body_fitting_loss(body_pose, betas, out.joints, camera_translation,
-                                                  camera_center, joints_2d, joints_conf, self.pose_prior,
-                                                  focal_length=self.focal_length, output='reprojection')
-        pose = torch.cat([global_orient, body_pose], dim=-1).detach()
-        return (out.vertices.detach(), out.joints.detach(), pose, betas.detach(), camera_translation,
-                reprojection_loss, optiverts)
+        # graph replays never run on the NULL stream (ops.py)
+        with ops.off_default_stream(init_pose.device) if on_gpu else contextlib.nullcontext():
+            with_pairs = gt_contact is not None and gt_contact[0] is not None
+            key, sess = self._session(init_pose.shape[0], use_contact, contactlist, segments, contact_loss_weight, with_pairs,
+                                      init_pose)
+            t = sess['t']
+            with torch.no_grad():
+                put = lambda dst, src: dst.copy_(src)
+                put(t['body_pose'], init_pose[:, 3:]); put(t['global_orient'], init_pose[:, :3]); put(t['betas'], init_betas)
+                put(t['cam'], init_cam_t); put(t['init_cam'], init_cam_t); put(t['centre'], camera_center)
+                put(t['j2d'], keypoints_2d[:, :, :2]); put(t['conf1'], keypoints_2d[:, :, -1])
+                put(t['conf2'], keypoints_2d[:, :, -1])
+                t['conf2'].index_fill_(1, self._ignored(t['conf2'].device), 0.0)                                     # smplifydc.py:153,198
+                if use_contact:
+                    put(t['valid'], ~ignore_idxs)
+                    if t.get('select') is not None:
+                        put(t['select'], (gt_contact[0] == 1) & has_discrete_contact.bool()[:, None] & (~ignore_idxs)[:, None])
+            # ---- stage 1: camera translation (+ shape with contact, + orientation without)
+            sess['flags'](*sess['stage1_flags'])
+            capture = sess['stage1'].run(self.num_iters, None, capture)
+            # ---- stage 2: pose + global orientation (+ shape without contact)
+            sess['flags'](*sess['stage2_flags'])
+            if sess['stage2'] is None:
+                sess['stage2'] = sess['make_stage2']()
+            optiverts = []
+            capture = sess['stage2'].run(self.num_iters, optiverts, capture)
+            # captured loops are kept for the next call; a session that ran eagerly (or lost a capture) is dropped
+            if not (capture and self.keep_sessions):
+                self._sessions.pop(key, None)
+            elif key not in self._sessions:
+                while len(self._sessions) >= 4:
+                    self._sessions.pop(next(iter(self._sessions)))
+                self._sessions[key] = sess
+            # ---- final evaluation
+            with torch.no_grad():
+                out = self.smpl(global_orient=t['global_orient'], body_pose=t['body_pose'], betas=t['betas'], return_full_pose=True)
+                conf = t['conf2'].clone()
+                if has_gt_keypoints is not None:                                         # smplifydc.py:219-220, no host sync
+                    conf[:, :25] = torch.where(has_gt_keypoints.bool()[:, None], torch.zeros_like(conf[:, :25]), conf[:, :25])
+                reprojection_loss = body_fitting_loss(t['body_pose'], t['betas'], out.joints, t['cam'], t['centre'], t['j2d'], conf,
+                                                      self.pose_prior, focal_length=self.focal_length, output='reprojection')
+            pose = torch.cat([t['global_orient'], t['body_pose']], dim=-1).detach().clone()
+            return (out.vertices.detach(), out.joints.detach(), pose, t['betas'].detach().clone(), t['cam'].detach().clone(),
+                    reprojection_loss, optiverts if optiverts else None)
 
     def _ignored(self, device):
         """ign_joints as an index tensor on `device`."""
