@@ -385,6 +385,26 @@ int tuch_region_pair_min(const tuch_contact_model* model, const float* verts, in
 int tuch_region_pair_min_bwd(const tuch_contact_model* model, const float* verts, int B, const int32_t* ij,
                              const float* grad_out, float* grad_verts, void* stream);
 
+/* Self-contact detection (csrc/self_contact.hip): TUCH.get_verts_in_contact, train_module.py:93-110, and the contact
+ * signature whose per-body minimum eval.py:135-136 reads from a file.  A pair (i, j) QUALIFIES when its mask bit is set
+ * and |v_i - v_j|^2 < euclthres^2 (direct differences, the same bits as tuch_v2v_min_masked / tuch_region_pair_min;
+ * euclthres <= 0: nothing qualifies; no special case for i == j: the mask decides).  geomask_bits: tuch_pack_geomask's
+ * layout, from it or from tuch_contact_model_mask_bits; the bit of (i, j) is bit j % 64 of word [j / 64][i], i.e.
+ * geomask[i][j] of the packed byte matrix -- the reference's `cmask[i][j]` and the orientation tuch_region_pair_min uses
+ * for (first region, second region); tuch_v2v_min_masked's minimum for vertex i runs over geomask[j][i]: the same thing
+ * for a symmetric mask only.
+ * Per vertex i: in_contact = some j qualifies; min_d2 = the minimum over the qualifying j (+inf when none); partner =
+ * the smallest j attaining it (-1 when none).  cnc_d2 [B] = minimum over all qualifying pairs of the body (+inf: no
+ * contact).  With a region table -- vreg_off [V+1] / vreg: the CSR lists vertex -> region ids in [0, R), R <= 128;
+ * regions may overlap or be empty, a vertex may belong to none -- sig_d2 [B,R,R]: sig_d2[b][r1][r2] = minimum over the
+ * qualifying pairs with r1 in regions(i) and r2 in regions(j), +inf when none.  vreg_off = NULL: no signature (vreg, R,
+ * sig_d2 ignored).  Two launches on `stream` (preset of sig_d2 / cnc_d2, then the search), no workspace, no
+ * synchronisation; all minima are order-free: bit-identical from run to run and in any batch.  B = 0: no-op. */
+int tuch_self_contact(const float* verts /* [B,V,3] */, const uint64_t* geomask_bits, int B, int V, float euclthres,
+                      const int32_t* vreg_off /* [V+1] or NULL */, const int32_t* vreg /* region ids */, int R,
+                      uint8_t* in_contact /* [B,V] */, int32_t* partner /* [B,V] */, float* min_d2 /* [B,V] */,
+                      float* sig_d2 /* [B,R,R] or NULL */, float* cnc_d2 /* [B] */, void* stream);
+
 /* ---- SMPL forward / backward: tuch/models/smpl.py:34-56 over smplx 0.1.13 lbs() -------------
  * Model arrays are HOST pointers in the layouts smplx registers them: v_template [V,3],
  * shapedirs [V,3,10], posedirs [207,3V], J_regressor [24,V], lbs_weights [V,24], parents [24],

@@ -154,6 +154,7 @@ _SIGNATURES = {
                                              c_size_t, c_void_p, c_void_p]),
     'tuch_fixed_to_float': (c_int, [c_void_p, c_size_t, c_void_p, c_void_p]),
     'tuch_region_pair_min_bwd': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'tuch_self_contact': (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_int] + [c_void_p] * 6),
     'tuch_procrustes': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'tuch_pose_metrics': (c_int, [c_void_p] * 5 + [c_int] * 5 + [c_void_p] * 5),
 }

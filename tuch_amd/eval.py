@@ -11,6 +11,9 @@ with a chain of torch ops over the concatenated validation set (trainer.py:229-2
         ev.add(pred_vertices, gt_vertices=gt_vertices)        # no host synchronisation
     ev.summary(cnc=cnc_arr)                                   # what print_final_result prints, millimetres
 
+    ev = Evaluator(..., contact=SelfContact(geodists))        # contact_detect.py: cnc of the gt vertices recorded by add()
+    ev.summary()                                              # ... and the contact / no-contact / unclear split from it
+
 One launch of tuch_pose_metrics (csrc/pose_eval.hip) per call: the H36M joints of pred (and gt) are regressed with
 every entry of the regressor, the pelvis (row pelvis_index) is subtracted before the joint map, and the aligned error
 comes from the same Procrustes device function as tuch_amd.utils.pose_utils.  With gt_joints instead of gt_vertices
@@ -157,9 +160,12 @@ class Evaluator:
     """Per-body errors of a whole evaluation, accumulated on the device.
 
     The regressor and joint map are prepared on the device once; add() writes each batch's results at a running
-    offset (no host synchronisation); results() copies them out; summary() / validation_metrics() reduce them."""
+    offset (no host synchronisation); results() copies them out; summary() / validation_metrics() reduce them.
 
-    def __init__(self, J_regressor, joint_map, capacity, pelvis_index=0, device=None, return_joints=False):
+    contact: a ``contact_detect.SelfContact``.  add() then also records every body's smallest self-contact distance
+    ('cnc': inf = no contact) -- the number eval.py:135-136 reads from a file -- and summary() splits the errors by it."""
+
+    def __init__(self, J_regressor, joint_map, capacity, pelvis_index=0, device=None, return_joints=False, contact=None):
         if device is None:
             if not torch.cuda.is_available():
                 raise RuntimeError('tuch_amd.eval.Evaluator needs a HIP device (there is no host fallback)')
@@ -178,6 +184,8 @@ class Evaluator:
         self._v2v = torch.full((self.capacity,), float('nan'), **kw)
         self._joints = torch.full((self.capacity, R, 3), float('nan'), **kw) if return_joints else None
         self._has_v2v = False
+        self.contact = contact
+        self._cnc = torch.full((self.capacity,), float('nan'), **kw) if contact is not None else None
         self.count = 0
 
     def reset(self):
@@ -186,11 +194,17 @@ class Evaluator:
         self._v2v.fill_(float('nan'))
         if self._joints is not None:
             self._joints.fill_(float('nan'))
+        if self._cnc is not None:
+            self._cnc.fill_(float('nan'))
         self._has_v2v = False
         self.count = 0
 
-    def add(self, pred_vertices, gt_vertices=None, gt_joints=None):
-        """One batch (pose_errors's arguments); returns the slice [start, stop) its bodies were written to."""
+    def add(self, pred_vertices, gt_vertices=None, gt_joints=None, contact_vertices=None):
+        """One batch (pose_errors's arguments); returns the slice [start, stop) its bodies were written to.
+        With a contact detector: the self-contact distance of contact_vertices [B, V', 3] (default: gt_vertices) is
+        recorded beside the errors; a batch with neither leaves NaN."""
+        if contact_vertices is not None and self.contact is None:
+            raise ValueError('contact_vertices given, but the Evaluator was created without contact=')
         B = _check_batch(pred_vertices, gt_vertices, gt_joints, self.J_regressor.shape[1], self.joint_map.shape[0])
         if pred_vertices.device != self.device:
             raise ValueError('batch on %s, evaluator on %s' % (pred_vertices.device, self.device))
@@ -202,24 +216,36 @@ class Evaluator:
             _launch(pred_vertices, gt_vertices, gt_joints, self.J_regressor, self.joint_map, self.pelvis_index,
                     self._mpjpe[s], self._pa[s], self._v2v[s] if gt_vertices is not None else None,
                     self._joints[s] if self._joints is not None else None)
+            if self.contact is not None:
+                cv = contact_vertices if contact_vertices is not None else gt_vertices
+                if cv is not None:
+                    if cv.shape[0] != B:
+                        raise ValueError('contact_vertices has %d bodies, the batch %d' % (cv.shape[0], B))
+                    self._cnc[s] = self.contact.cnc(cv)
         self._has_v2v |= gt_vertices is not None
         self.count = start + B
         return start, self.count
 
     def results(self):
         """numpy float32 per-body arrays of the bodies added so far: 'mpjpe', 'pa_mpjpe' (metres), 'v2v' (when any
-        batch had gt_vertices; NaN for the bodies of the others) and 'joints' [n, R, 3] (with return_joints)."""
+        batch had gt_vertices; NaN for the bodies of the others), 'joints' [n, R, 3] (with return_joints) and 'cnc'
+        (with a contact detector: metres, inf = no contact, NaN for bodies added without vertices to look at)."""
         n = self.count
         out = {'mpjpe': self._mpjpe[:n].cpu().numpy(), 'pa_mpjpe': self._pa[:n].cpu().numpy()}
         if self._has_v2v:
             out['v2v'] = self._v2v[:n].cpu().numpy()
         if self._joints is not None:
             out['joints'] = self._joints[:n].cpu().numpy()
+        if self._cnc is not None:
+            out['cnc'] = self._cnc[:n].cpu().numpy()
         return out
 
     def summary(self, cnc=None, euclthres_lower=0.01):
-        """pose_summary of the bodies added so far (keys there)."""
+        """pose_summary of the bodies added so far (keys there); cnc defaults to the recorded values when the evaluator
+        has a contact detector."""
         r = self.results()
+        if cnc is None:
+            cnc = r.get('cnc')
         return pose_summary(r['mpjpe'], r['pa_mpjpe'], cnc, euclthres_lower)
 
     def validation_metrics(self):

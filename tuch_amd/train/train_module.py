@@ -5,6 +5,8 @@ Same constructor and ``forward_train_step(input_batch) -> (loss, losses, output)
 (train_module.py:31-66, 105-335).  What runs where:
   * ``contact_from_verts`` (:69-91, "Speed up this function will speed up training loop!") -- one HIP kernel over all
     region pairs instead of a Python loop of three bmm's per pair;
+  * ``get_verts_in_contact`` (:93-110, a [V,V] distance matrix per body in a Python loop) -- one HIP kernel pass over
+    the batch (contact_detect.SelfContact);
   * ``estimate_translation`` (:171-180, per-sample numpy solves on the host in the reference) and
     ``rotation_matrix_to_angle_axis`` (:208-212) -- HIP kernels, no host round trip;
   * the dictionary of best fits (:142-146, :265) -- on the device (train/fits_dict.py);
@@ -50,6 +52,7 @@ class TUCH():
             faces = bodymodel.faces
         regions, pairs = ops.region_tables(contactlists)
         self._model = ops.ContactModel(faces, None, None, regions, pairs, device=device)
+        self._self_contact = {}          # (geothres, euclthres) -> SelfContact, built by get_verts_in_contact
 
     # ------------------------------------------------------------------ train_module.py:69-91
     def contact_from_verts(self, verts, mode='regions'):
@@ -57,6 +60,19 @@ class TUCH():
         if mode != 'regions':
             raise ValueError("only mode='regions' exists in the reference")
         return self._model.region_pair_min(verts)[0]
+
+    # ------------------------------------------------------------------ train_module.py:93-110
+    def get_verts_in_contact(self, verts, geothres=0.3, euclthres=0.02):
+        """[B,V,3] -> {bidx: [idxs1, idxs2]}: the vertices with another vertex closer than ``euclthres`` and at least
+        ``geothres`` away along the surface, and the nearest such vertex of each (the reference reads the two thresholds
+        from configs/config.py:90-91).  One kernel pass for the batch (contact_detect.SelfContact)."""
+        if self.geodistssmpl is None:
+            raise ValueError('get_verts_in_contact needs the geodesic distances: TUCH(..., geodistssmpl=...) was not given')
+        key = (float(geothres), float(euclthres))
+        if key not in self._self_contact:
+            from ..contact_detect import SelfContact
+            self._self_contact[key] = SelfContact(self.geodistssmpl, geothres=key[0], euclthres=key[1])
+        return self._self_contact[key].verts_in_contact(verts)
 
     # ------------------------------------------------------------------ train_module.py:105-335
     def forward_train_step(self, input_batch):
