@@ -405,6 +405,50 @@ int tuch_self_contact(const float* verts /* [B,V,3] */, const uint64_t* geomask_
                       uint8_t* in_contact /* [B,V] */, int32_t* partner /* [B,V] */, float* min_d2 /* [B,V] */,
                       float* sig_d2 /* [B,R,R] or NULL */, float* cnc_d2 /* [B] */, void* stream);
 
+/* ---- mesh renderer (csrc/render.hip): what tuch/utils/renderer.py asks of pyrender, on the compute units --------
+ * tuch_render_mesh: B bodies x n_views (1..32) views -> face [B,n_views,H,W] (triangle id, -1 = empty), depth (the same
+ * shape; camera-space z in metres at the pixel centre, 0 = empty: the reference's `rend_depth > 0`) and image
+ * [B,n_views,H,W,3] in [0,1].
+ * Camera: utils/geometry.perspective_projection.  p = view_rot[w] v + cam_t[b] lands at (focal p.x / p.z + cx,
+ * focal p.y / p.z + cy); the pixel in row r, column c has its centre at (c + 0.5, r + 0.5).
+ * Coverage is exact and watertight: the projections are snapped to 1/256 px, the edge functions are 64-bit integers, a
+ * centre on an edge belongs to the triangle when the centre moved by (+eps, +eps^2) is strictly inside (top-left rule):
+ * exactly one of the triangles that share an edge or a vertex, whatever the face order or winding.  No back-face
+ * culling.  A triangle is dropped whole when a corner has p.z <= 1e-3 m, a coordinate that is not finite (or a
+ * projection beyond +-2^21 px), an index outside [0,V), or when its snapped area is zero; triangles partly outside the
+ * image are clipped to it by their bounding box.
+ * Visibility: one 64-bit key per pixel (float bits of z, face id) merged with an atomic minimum -- the nearest surface,
+ * at equal depth the smaller face id; z is interpolated perspective-correctly (1 / z linear in screen space) with the
+ * barycentrics of the UNSNAPPED float32 projections, clamped to the triangle -- only coverage is decided on the snapped
+ * grid.  Order-free: outputs are bit-identical from run to run and for a body alone or inside any batch.
+ * Shading: area-weighted vertex normals (gathered through vf_off [V+1] / vf_ids, the vertex -> faces CSR lists, in list
+ * order) and the vertex colours, interpolated perspective-correctly; rgb = albedo / 255 * min(1, 0.3 + 0.7 max(0, -n_z))
+ * with n in the camera frame: the reference's ambient term and its lights along the viewing direction.  pyrender's
+ * physically based look is NOT emulated.  colors [B,V,3] u8 or NULL (230,230,230: renderer.py:185); empty pixels take
+ * background [B,H,W,3] in the views whose bit is set in background_views (bit w = view w) and 1.0 elsewhere or when
+ * background is NULL.
+ * One memset and three launches on `stream`, no synchronisation, capturable.  B = 0: no-op. */
+size_t tuch_render_workspace_bytes(int B, int n_views, int V, int F, int H, int W);
+int tuch_render_mesh(const float* verts /* [B,V,3] */, const int32_t* faces /* [F,3] */, const int32_t* vf_off /* [V+1] */,
+                     const int32_t* vf_ids, int B, int V, int F, const float* cam_t /* [B,3] */,
+                     const float* view_rot /* [n_views,3,3] */, int n_views, float focal, float cx, float cy, int H, int W,
+                     const uint8_t* colors /* [B,V,3] or NULL */, const float* background /* [B,H,W,3] or NULL */,
+                     unsigned int background_views, int32_t* face, float* depth, float* image, void* workspace,
+                     size_t workspace_bytes, void* stream);
+/* The reference's contact colouring (renderer.py:199-224) for a batch: colors [B,V,3] u8.  meshcols of a body =
+ * (v - min_axis) * 255 / max_axis(v - min_axis) in float32, in this order, truncated.  Untouched vertices keep 230.
+ * Pair form (pair_off [B+1] != NULL; c1, c2 [n_pairs]: body b owns the pairs pair_off[b] .. pair_off[b+1]): both
+ * vertices of pair k get (meshcols[c1[k]] + meshcols[c2[k]]) >> 1; pairs in list order, the last write wins.
+ * Region form (contact [B,P] 0/1 != NULL; pairs [P,2] region ids; region_first [R]: the first LISTED vertex of each
+ * region, -1 for an empty one; vreg_off / vreg: tuch_self_contact's vertex -> regions table): every vertex of both
+ * regions of every active pair gets meshcols[region_first[first region]]; pairs in increasing order, the last wins; a
+ * pair whose first region is empty is skipped.  Entries outside their range are ignored.  Three launches, order-free. */
+size_t tuch_contact_vertex_colors_workspace_bytes(int B, int V, int R);
+int tuch_contact_vertex_colors(const float* verts /* [B,V,3] */, int B, int V, const int32_t* pair_off, const int32_t* c1,
+                               const int32_t* c2, int n_pairs, const uint8_t* contact, const int32_t* pairs, int P,
+                               const int32_t* region_first, const int32_t* vreg_off, const int32_t* vreg, int R,
+                               uint8_t* colors, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- SMPL forward / backward: tuch/models/smpl.py:34-56 over smplx 0.1.13 lbs() -------------
  * Model arrays are HOST pointers in the layouts smplx registers them: v_template [V,3],
  * shapedirs [V,3,10], posedirs [207,3V], J_regressor [24,V], lbs_weights [V,24], parents [24],

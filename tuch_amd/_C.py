@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_float, c_int, c_size_t, c_void_p
+from ctypes import POINTER, c_char_p, c_float, c_int, c_size_t, c_uint, c_void_p
 
 import torch  # noqa: F401  (must be imported first so the HIP runtime it ships is the one in the process)
 
@@ -157,6 +157,12 @@ _SIGNATURES = {
     'tuch_self_contact': (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_int] + [c_void_p] * 6),
     'tuch_procrustes': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'tuch_pose_metrics': (c_int, [c_void_p] * 5 + [c_int] * 5 + [c_void_p] * 5),
+    'tuch_render_workspace_bytes': (c_size_t, [c_int] * 6),
+    'tuch_render_mesh': (c_int, [c_void_p] * 4 + [c_int] * 3 + [c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_int, c_int,
+                                 c_void_p, c_void_p, c_uint, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'tuch_contact_vertex_colors_workspace_bytes': (c_size_t, [c_int] * 3),
+    'tuch_contact_vertex_colors': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
+                                           c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 

@@ -35,6 +35,10 @@ _MAP = {
     'tuch.eft.loss': 'tuch_amd.eft.loss',
 }
 
+# mapped only on request (install_renderer): after a plain install() the name keeps coming from the checkout
+_OPTIONAL = {'tuch.utils.renderer': 'tuch_amd.utils.renderer'}
+_enabled = {}
+
 _PACKAGES = ('tuch', 'tuch.utils', 'tuch.smplify', 'tuch.models', 'tuch.train', 'tuch.eft')
 
 
@@ -91,7 +95,7 @@ class _MappedFinder(importlib.abc.MetaPathFinder):
     somebody emptied sys.modules of `tuch.*`; every other name falls through to the ordinary finders."""
 
     def find_spec(self, fullname, path=None, target=None):
-        ours = _MAP.get(fullname)
+        ours = _MAP.get(fullname) or _enabled.get(fullname)
         if ours is None:
             return None
         return importlib.machinery.ModuleSpec(fullname, _MappedLoader(ours))
@@ -138,8 +142,30 @@ def install(overwrite: bool = True):
     return installed
 
 
+def install_renderer():
+    """Opt in: `tuch.utils.renderer` -> tuch_amd.utils.renderer (the device rasteriser; no pyrender / OpenGL).  install()
+    alone leaves that name to the reference checkout, whose file needs pyrender, trimesh and torchvision; call this
+    after it (or instead of it: the packages are registered here too).  uninstall() undoes it."""
+    if _finder not in sys.meta_path:
+        sys.meta_path.insert(0, _finder)
+    for pkg in ('tuch', 'tuch.utils'):
+        if pkg not in sys.modules:
+            _package(pkg)
+    installed = []
+    for ref_name, our_name in _OPTIONAL.items():
+        mod = importlib.import_module(our_name)
+        _enabled[ref_name] = our_name
+        sys.modules[ref_name] = mod
+        parent, _, leaf = ref_name.rpartition('.')
+        setattr(sys.modules[parent], leaf, mod)
+        installed.append(ref_name)
+    importlib.invalidate_caches()
+    return installed
+
+
 def uninstall():
-    """Undo install(): the finder, the registered packages and the mapped names (tests)."""
+    """Undo install() and install_renderer(): the finder, the registered packages and the mapped names (tests)."""
+    _enabled.clear()
     if _finder in sys.meta_path:
         sys.meta_path.remove(_finder)
     for k in [k for k in sys.modules if k == 'tuch' or k.startswith('tuch.')]:
