@@ -246,7 +246,7 @@ int tuch_contact_model_create(tuch_contact_model** out, int V, int F, const int3
                               int num_pairs, const int32_t* pairs);
 void tuch_contact_model_destroy(tuch_contact_model* model);
 /* Switches of the hot calls (A/B measurements, tests): winding_ray (0 never / 1 when only flags are wanted / 2 also for
- * w), winding_tree, winding_strips, tree_waves, ray_pair_cap, ray_waves, ray_fans, v2v_tree, v2v_flat, v2v_pairs, v2v_waves, v2v_lds,
+ * w), winding_tree, winding_strips, tree_waves, ray_pair_cap, ray_waves, v2v_tree, v2v_flat, v2v_pairs, v2v_waves, v2v_lds,
  * seg_splits, seg_fused, seg_assist (fixed at create), hd_search, hd_search_waves, hd_overlap, canary.  (Deterministic mode is process-wide: tuch_set_deterministic.)  The environment variables TUCH_<NAME> are read ONCE, by
  * tuch_contact_model_create; afterwards only set_option changes a model's switches -- no hot call looks at the
  * environment, so a captured hipGraph cannot depend on it.  (The workspace sizes depend on ray_pair_cap and canary:
@@ -317,25 +317,6 @@ int tuch_v2v_min_model_shared(const tuch_contact_model* model, const float* vert
 int tuch_v2v_min_model_shared_zero(const tuch_contact_model* model, const float* verts, int B, float* min_d2, int32_t* argmin,
                                    void* hint_inout, void* workspace, size_t workspace_bytes, int leave_room, void* zero,
                                    size_t zero_bytes, void* stream);
-
-/* The search for a caller that only needs partners within `cap` of vertices OUTSIDE the body -- the SMPLify-DC contact term:
- * an exterior vertex contributes only if its nearest admissible vertex is closer than euclthres (tuch/smplify/losses.py:99-104),
- * an interior one at any distance (:100-101).  prev_exterior [B,V]: the flags of the previous iteration (tuch_v2v_min_model_fix
- * keeps them current; zeros at first: nothing capped).  A vertex with prev_exterior != 0 and an admissible hint starts its
- * search at cap^2: found closer -> exact; else min_d2 = cap^2 and argmin = its hint (a real admissible vertex, farther than
- * cap).  tuch_v2v_min_model_fix -- called with the SAME workspace once the inside test's flags `exterior` of THIS iteration
- * exist -- searches the columns again
- * that were cut off at the cap and are inside now (exhaustively: the exact result), and stores the flags as the next
- * prediction.  Together: exact (min_d2, argmin) for every vertex that is inside or has a partner within cap; cap must be
- * >= the loss's threshold (callers add 0.1 %: the loss recomputes the distance with its own rounding).
- * tuch_v2v_min_model_can_cap: does this model's search support it (leaf scan + hints; option v2v_cap)? */
-int tuch_v2v_min_model_can_cap(const tuch_contact_model* model);
-int tuch_v2v_min_model_capped(const tuch_contact_model* model, const float* verts, int B, float* min_d2, int32_t* argmin,
-                              void* hint_inout, void* workspace, size_t workspace_bytes, int leave_room, void* zero,
-                              size_t zero_bytes, const uint8_t* prev_exterior, float cap, void* stream);
-int tuch_v2v_min_model_fix(const tuch_contact_model* model, int B, const uint8_t* exterior, uint8_t* prev_exterior, float cap,
-                           float* min_d2, int32_t* argmin, void* hint_inout, void* workspace, size_t workspace_bytes,
-                           void* stream);
 
 /* Cluster tree over the faces of a closed mesh (host only, no device needed): the structure behind the
  * hierarchical evaluation of winding_numbers (tuch/utils/contact.py:112-147) inside tuch_exterior_flags.

@@ -218,29 +218,6 @@ def test_exterior_flags_and_segments(tag):
         assert (ext[b] != ext_ref).sum() == 0
 
 
-@pytest.mark.parametrize('tag', TAGS)
-def test_exterior_flags_same_bits_in_every_form_of_the_ray_test(tag):
-    """Option ray_cross (csrc/ray_winding.hip): near lists, regrouping and crossings in one launch (1, ray_cross_kernel) or the
-    three launches of rounds 2 - 5 (0).  Option ray_fans: the vertices' closing fans computed by the finalize kernel (0), by
-    extra workgroups of the chain's first launch (1, only when the leaves' strip runs tile the stream) or of the near-list
-    launch (2, three-launch form only).  Flags, segment flags and winding sums are the same bits in every combination."""
-    g, gm = golden(tag), golden_mask(tag)
-    model = make_model(g, gm, True, False)
-    verts = torch.tensor(g['verts'], device=dev())
-    got = {}
-    for cross in (0, 1):
-        for fans in (0, 1, 2):
-            model.set_option('ray_cross', cross)
-            model.set_option('ray_fans', fans)
-            ext, w, _, seg_e = model.exterior_flags(verts, apply_segments=True, return_details=True)
-            plain = model.exterior_flags(verts, apply_segments=False)
-            filtered = model.exterior_flags(verts, apply_segments=True)
-            got[cross, fans] = (ext.clone(), w.clone(), seg_e.clone(), plain.clone(), filtered.clone())
-    for key, vals in got.items():
-        for a, b, what in zip(vals, got[0, 0], ('exterior', 'w', 'segment flags', 'exterior without segments', 'flags only')):
-            assert torch.equal(a, b), (tag, key, what)
-
-
 @pytest.mark.parametrize('tag', SMALL)
 @pytest.mark.parametrize('mode', [0, 1])
 def test_contact_terms_forward_backward(tag, mode):

@@ -107,11 +107,6 @@ _SIGNATURES = {
     'tuch_v2v_min_model_shared_zero': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int,
                                                c_void_p, c_size_t, c_void_p]),
     'tuch_exterior_workspace_bytes': (c_size_t, [c_void_p, c_int]),
-    'tuch_v2v_min_model_can_cap': (c_int, [c_void_p]),
-    'tuch_v2v_min_model_capped': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int,
-                                          c_void_p, c_size_t, c_void_p, c_float, c_void_p]),
-    'tuch_v2v_min_model_fix': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
-                                       c_size_t, c_void_p]),
     'tuch_exterior_flags': (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_size_t, c_void_p]),
     'tuch_winding_points_workspace_bytes': (c_size_t, [c_void_p, c_int, c_int]),

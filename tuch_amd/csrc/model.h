@@ -40,12 +40,8 @@ struct tuch_options {
     int tree_waves = 32768;     // frontier choice of the solid-angle walk (128-query blocks)
     int ray_pair_cap = 16;      // (ray, leaf) pairs per query the pair list has room for
     int ray_waves = 32768;      // wavefronts of the crossing kernel
-    int ray_fans = 0;           // the vertices' closing fans (they need the vertices only): 0 inside ray_finalize_verts_kernel, 1 by extra workgroups of the inside test's FIRST launch (ray_leaf_bounds_kernel), 2 of ray_near_kernel's launch.  Round 5, batch 64: 0.427 / 0.444 / 0.424 ms per step -- the finalize kernel drops from 28 to 6 - 13 us, but the launch that carries the fans grows by more (1: the search then starts ahead of ray_near, which crawls beside it: 117 us)
-    int ray_cross = 0;          // the vertices' inside test: 0 the three launches of rounds 2 - 5 (ray_near -> ray_tiles_fill -> ray_leaf; also what arbitrary points take), 1 near lists, regrouping and crossings in ONE launch (ray_cross_kernel, round 6: one wavefront per (leaf, body), rays gathered in an LDS ring -- no lists, no pair table; 150 us alone against 51 + 24 + 100 and 6.1e7 against 6.5e7 vector instructions at batch 64, but the replayed step is 0.412 against 0.410 ms there -- the step's middle is bound by the SUM of the vector work of this test and of the search beside it, not by the chain -- and 0.214 against 0.176 ms at batch 8, where 3440 long one-wave chains are fewer than the chip's wave slots)
-    int ray_cross_split = 0;    // ray_cross_kernel: wavefronts that share a leaf's query blocks (0: 4 up to batch 8, 2 up to 32, else 1)
     int v2v_tree = 1;           // 0: flat nearest-vertex search
     int v2v_waves = 0;          // frontier choice of the search (wavefronts aimed at; 0: the form's own default)
-    int v2v_cap = 0;            // SMPLify-DC stage 2: 1 the search of vertices the previous iteration found outside the body starts at the loss's cap (euclthres) and the few that turn out inside are searched again behind the inside test (tuch_v2v_min_model_capped / _fix, round 6).  Exact (bit-identical fits, tests/test_gpu_properties.py); the search itself drops from 171 to 81 us inside the step at batch 64, the step does not move (0.405 against 0.415 ms, within the blocks' spread; batch 8: 0.183 against 0.177): the inside test's chain is the critical path either way, and the second pass is one more dependent launch on it.  Off.
     int v2v_flat = 2;           // search: 2 lanes over a subtree's leaves first (v2v_scan_kernel), 0 the stackless walk (v2v_tree_kernel)
     int v2v_pairs = 24;         // scan: a leaf in reach of FEWER columns of the wavefront than this is not walked row by row for all 64 lanes; its (leaf, column) pairs are queued and evaluated one per lane (round 5); 0: every leaf row by row (round 4)
     int v2v_lds = -1;           // search beside the inside test: -1 capped at 7 wavefronts per SIMD by register count (-4 / -5 / -6: at that many; round 4, lighter scan: 7 0.487, 6 0.494, 5 0.512, 4 0.530 ms per step), > 0 by an LDS allocation of that many bytes per workgroup (6400: round 2), 0 uncapped
