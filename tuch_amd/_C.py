@@ -5,6 +5,7 @@ torch only supplies device memory and the current stream.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 from ctypes import POINTER, c_char_p, c_float, c_int, c_size_t, c_uint, c_void_p
@@ -188,6 +189,15 @@ class TuchError(RuntimeError):
 def check(rc: int) -> None:
     if rc != 0:
         raise TuchError('libtuch_amd error %d: %s' % (rc, lib().tuch_last_error().decode()))
+
+
+def create_context(device):
+    """What a *_create call runs under: its device, or nothing when TUCH_HOST_TABLES=1 keeps the tables in host memory."""
+    if os.environ.get('TUCH_HOST_TABLES', '0') not in ('', '0'):
+        return contextlib.nullcontext()
+    if torch.device(device).type != 'cuda':
+        raise TuchError('tuch_amd kernels need a HIP device, the model was created for %s' % device)
+    return torch.cuda.device(device)
 
 
 def ptr(t) -> c_void_p:

@@ -72,3 +72,8 @@ void tuch_table_free(void* p)
     if (!p) return;
     if (g_host_tables) free(p); else (void)hipFree(p);
 }
+void tuch_tables::release()
+{
+    for (void* p : held) tuch_table_free(p);
+    held.clear();
+}

@@ -399,17 +399,17 @@ bool tuch_cluster_tree_build_impl(int V, int F, const int32_t* faces, int leaf_f
     // ---- exact streams of the leaves (in preorder), then the cap streams of all nodes
     t.num_nodes = N;
     t.face_leaf.assign(F, 0);
-    t.nodes.assign((size_t)N * 8, 0);
+    t.nodes.assign((size_t)N * kNodeWords, 0);
     std::vector<int32_t> sub;
     std::vector<int> leaf_seq(N, -1);
     int nleaves_seen = 0;
     for (int i = 0; i < N; ++i) {
         const Group& g = groups[order[i]];
-        int32_t* nd = &t.nodes[(size_t)i * 8];
-        nd[4] = skip[order[i]];
-        nd[5] = g.c0 >= 0 ? pre[g.c0] : -1;
-        nd[6] = g.c1 >= 0 ? pre[g.c1] : -1;
-        nd[7] = (int)g.faces.size();
+        int32_t* nd = &t.nodes[(size_t)i * kNodeWords];
+        nd[kNodeSkip] = skip[order[i]];
+        nd[kNodeChild0] = g.c0 >= 0 ? pre[g.c0] : -1;
+        nd[kNodeChild1] = g.c1 >= 0 ? pre[g.c1] : -1;
+        nd[kNodeFaces] = (int)g.faces.size();
         if (g.c0 >= 0) continue;
         leaf_seq[i] = nleaves_seen++;
         for (int f : g.faces) t.face_leaf[f] = leaf_seq[i];
@@ -418,8 +418,8 @@ bool tuch_cluster_tree_build_impl(int V, int F, const int32_t* faces, int leaf_f
         const size_t begin = t.vidx.size();
         tuch_build_strips(sub.data(), (int)g.faces.size(), t.vidx, t.sign, nullptr);
         pad3(t.vidx, t.sign, begin);
-        nd[2] = (int)begin;
-        nd[3] = (int)(t.vidx.size() - begin);
+        nd[kNodeExactOff] = (int)begin;
+        nd[kNodeExactLen] = (int)(t.vidx.size() - begin);
     }
     t.exact_len = (int)t.vidx.size();
     std::vector<char> inset(F, 0);
@@ -438,8 +438,8 @@ bool tuch_cluster_tree_build_impl(int V, int F, const int32_t* faces, int leaf_f
             }
         }
         if (t.vidx.size() > begin) pad3(t.vidx, t.sign, begin);
-        t.nodes[(size_t)i * 8 + 0] = (int)begin;
-        t.nodes[(size_t)i * 8 + 1] = (int)(t.vidx.size() - begin);
+        t.nodes[(size_t)i * kNodeWords + kNodeCapOff] = (int)begin;
+        t.nodes[(size_t)i * kNodeWords + kNodeCapLen] = (int)(t.vidx.size() - begin);
     }
     t.stream_len = (int)t.vidx.size();
 
@@ -477,7 +477,7 @@ bool tuch_cluster_tree_build_impl(int V, int F, const int32_t* faces, int leaf_f
         if (t.rows[(size_t)nd * 2 + 1]++ == 0) t.rows[(size_t)nd * 2] = pos;
     }
     for (int i = N - 1; i >= 0; --i) {               // inner nodes: the span of their leaves
-        const int c0 = t.nodes[(size_t)i * 8 + 5], c1 = t.nodes[(size_t)i * 8 + 6];
+        const int c0 = t.child0(i), c1 = t.child1(i);
         if (c0 < 0) continue;
         int lo = 1 << 30, hi = 0;
         for (int c : {c0, c1})
@@ -495,26 +495,25 @@ bool tuch_cluster_tree_build_impl(int V, int F, const int32_t* faces, int leaf_f
         while ((int)fr.size() < target) {
             int best = -1;
             for (size_t i = 0; i < fr.size(); ++i)
-                if (t.nodes[(size_t)fr[i] * 8 + 5] >= 0 &&
-                    (best < 0 || t.nodes[(size_t)fr[i] * 8 + 7] > t.nodes[(size_t)fr[best] * 8 + 7])) best = (int)i;
+                if (!t.is_leaf(fr[i]) && (best < 0 || t.num_faces(fr[i]) > t.num_faces(fr[best]))) best = (int)i;
             if (best < 0) break;
             const int n = fr[best];
-            fr[best] = t.nodes[(size_t)n * 8 + 5];
-            fr.push_back(t.nodes[(size_t)n * 8 + 6]);
+            fr[best] = t.child0(n);
+            fr.push_back(t.child1(n));
         }
         std::sort(fr.begin(), fr.end());
         // launch order of the (subtree, query block) pairs: pairs whose queries live inside the subtree
         // walk it down to the leaves (long-running) and go first, far pairs (one cap) fill the tail
         std::vector<std::pair<long, int32_t>> cost;
         for (size_t si = 0; si < fr.size(); ++si) {
-            const int lo = fr[si], hi = t.nodes[(size_t)fr[si] * 8 + 4];
+            const int lo = fr[si], hi = t.skip(fr[si]);
             for (int qb = 0; qb < t.num_qblocks; ++qb) {
                 long home = 0;
                 for (int k = 0; k < 128; ++k) {
                     const int ln = seq_node[vkey[t.qperm[(size_t)qb * 128 + k]]];
                     home += (ln >= lo && ln < hi);
                 }
-                cost.emplace_back(-(home * 100000L + t.nodes[(size_t)fr[si] * 8 + 7]), (int32_t)((si << 16) | qb));
+                cost.emplace_back(-(home * 100000L + t.num_faces(fr[si])), (int32_t)((si << 16) | qb));
             }
         }
         std::stable_sort(cost.begin(), cost.end(), [](const std::pair<long, int32_t>& a, const std::pair<long, int32_t>& b) {
@@ -525,7 +524,7 @@ bool tuch_cluster_tree_build_impl(int V, int F, const int32_t* faces, int leaf_f
         for (size_t si = 0; si < fr.size(); ++si) {
             int count = 0;
             for (int a = 0; a < fr[si] && count < 8; ++a)
-                if (t.nodes[(size_t)a * 8 + 4] > fr[si]) { t.ancestors.push_back(a); ++count; }
+                if (t.skip(a) > fr[si]) { t.ancestors.push_back(a); ++count; }
             for (; count < 8; ++count) t.ancestors.push_back(-1);
         }
         t.frontier_nodes.insert(t.frontier_nodes.end(), fr.begin(), fr.end());

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <vector>
 
 #define TUCH_OK 0
 #define TUCH_ERR_ARG -1
@@ -62,6 +63,25 @@ int tuch_host_tables();
 int tuch_table_upload(void** dst, const void* src, size_t bytes);
 int tuch_table_download(void* dst_host, const void* src, size_t bytes);
 void tuch_table_free(void* p);
+// Owner of one model's tables.  put() uploads `count` elements into *field and remembers the pointer; once a put has
+// failed the later ones do nothing (their fields stay nullptr), so a builder is a plain sequence of puts and the model's
+// create returns tables.rc.  A table of zero bytes is nullptr and TUCH_OK: several features are switched on by a table
+// being there.  release() (and deleting the model) frees everything put so far.
+struct tuch_tables {
+    int rc = TUCH_OK;
+    std::vector<void*> held;
+    tuch_tables() = default;
+    tuch_tables(const tuch_tables&) = delete;       // one owner per pointer
+    ~tuch_tables() { release(); }
+    template <typename T>
+    void put(T** field, const T* src, size_t count)
+    {
+        if (rc != TUCH_OK) return;
+        rc = tuch_table_upload((void**)field, src, count * sizeof(T));
+        if (*field) held.push_back(*field);
+    }
+    void release();
+};
 
 // Deterministic mode (the default; TUCH_DETERMINISTIC=0, read once when the library is loaded, or tuch_set_deterministic(0),
 // selects float atomics): the gradient

@@ -21,13 +21,12 @@
 #include "workspace.h"
 #include <algorithm>
 #include <mutex>
-#include <type_traits>
 #include <numeric>
-#include <stdlib.h>
 #include <string.h>
 #include <vector>
 
 struct tuch_hd_model {
+    tuch_tables tables;  // owns the device tables below
     const tuch_contact_model* cm;
     int N, V, F;
     int K;               // non-zeros per regressor row (3: barycentric samples; up to 8 for a general sparse regressor)
@@ -42,24 +41,18 @@ struct tuch_hd_model {
     int32_t* v_ent;
     int32_t* offsets;    // [kMaxBatch+1] = b * N (device): where body b's slots start
     int tree_order;      // mask ids are tree positions (the model's mask in tree order is used)
-    std::vector<int32_t>* order_host;   // sorted -> original index
+    std::vector<int32_t> order_host;    // sorted -> original index
     // the search of the selected points and their inside test only share their input: the inside test runs on a stream of
     // the model's own beside the search (option hd_overlap; fork / join through events, capturable)
     hipStream_t side;
     hipEvent_t ev_fork, ev_join;
-    std::mutex* enqueue;                // one forward call at a time enqueues on `side`
+    mutable std::mutex enqueue;         // one forward call at a time enqueues on `side`
 };
 
 namespace {
 
 constexpr int kMaxBatch = 4096;
 constexpr int kSel = 1024;
-
-template <typename T>
-int upload(T** dst, const T* src, size_t count)
-{
-    return tuch_table_upload((void**)dst, src, count * sizeof(T));
-}
 
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
@@ -438,27 +431,15 @@ Work work_layout(const tuch_hd_model* hm, int B)
 extern "C" void tuch_hd_model_destroy(tuch_hd_model* hm)
 {
     if (!hm) return;
-    void* dev[] = {hm->idx, hm->w, hm->face, hm->tv, hm->mask_id, hm->orig, hm->by_orig, hm->v_off, hm->v_ent, hm->offsets};
-    for (void* p : dev) tuch_table_free(p);
     if (hm->side) (void)hipStreamDestroy(hm->side);
     if (hm->ev_fork) (void)hipEventDestroy(hm->ev_fork);
     if (hm->ev_join) (void)hipEventDestroy(hm->ev_join);
-    delete hm->enqueue;
-    delete hm->order_host;
-    free(hm);
+    delete hm;
 }
 
 // hd_idx / hd_w [N,3]: the three non-zeros of every row of the HD vertex regressor; hd_face [N]: the face each point
 // was sampled from.  The contact model must outlive the HD model.
-extern "C" int tuch_hd_model_create_k(tuch_hd_model** out, const tuch_contact_model* cm, int N, int K, const int32_t* hd_idx,
-                                      const float* hd_w, const int32_t* hd_face);
-extern "C" int tuch_hd_model_create(tuch_hd_model** out, const tuch_contact_model* cm, int N, const int32_t* hd_idx,
-                                    const float* hd_w, const int32_t* hd_face)
-{
-    return tuch_hd_model_create_k(out, cm, N, 3, hd_idx, hd_w, hd_face);
-}
-
-// The same for a regressor with up to K <= 8 non-zeros per row (hd_idx / hd_w [N,K]; rows with fewer: weight 0, any valid id).
+// K <= 8 non-zeros per row (hd_idx / hd_w [N,K]; rows with fewer: weight 0, any valid id).
 extern "C" int tuch_hd_model_create_k(tuch_hd_model** out, const tuch_contact_model* cm, int N, int K, const int32_t* hd_idx,
                                       const float* hd_w, const int32_t* hd_face)
 {
@@ -483,7 +464,7 @@ extern "C" int tuch_hd_model_create_k(tuch_hd_model** out, const tuch_contact_mo
     std::iota(order.begin(), order.end(), 0);
     // Within a patch: by the mask vertex (first vertex of the face, loss.py:88), then by face -- consecutive points that
     // inherit the same mask row form the runs hd_search.hip fetches one mask word for.
-    const bool tree = cm->tree_nodes > 0 && cm->tree_face_leaf_host;
+    const bool tree = cm->tree_nodes > 0;
     if (tree)
         std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
             const int fa = hd_face[a], fb = hd_face[b];
@@ -494,7 +475,7 @@ extern "C" int tuch_hd_model_create_k(tuch_hd_model** out, const tuch_contact_mo
             return fa < fb;
         });
     std::vector<int32_t> pos(V);
-    const bool tree_mask = tree && cm->tree_mask_bits && cm->tree_qperm_host;
+    const bool tree_mask = tree && cm->tree_mask_bits;
     if (tree_mask)
         for (int i = 0; i < V; ++i) pos[cm->tree_qperm_host[i]] = i;
     std::vector<int32_t> idx((size_t)N * K), face(N), tv(N), mask_id(N);
@@ -521,10 +502,9 @@ extern "C" int tuch_hd_model_create_k(tuch_hd_model** out, const tuch_contact_mo
     }
     std::vector<int32_t> offsets(kMaxBatch + 1);
     for (int b = 0; b <= kMaxBatch; ++b) offsets[b] = (int32_t)((long)b * N < 0x7fffffffL ? (long)b * N : 0x7fffffffL);
-    tuch_hd_model* hm = (tuch_hd_model*)calloc(1, sizeof(tuch_hd_model));
+    tuch_hd_model* hm = new tuch_hd_model();
     hm->cm = cm; hm->N = N; hm->V = V; hm->F = F; hm->K = K; hm->tree_order = tree_mask ? 1 : 0;
-    hm->order_host = new std::vector<int32_t>(order);
-    hm->enqueue = new std::mutex();
+    hm->order_host = order;
     if (!tuch_host_tables() &&
         (hipStreamCreateWithFlags(&hm->side, hipStreamNonBlocking) != hipSuccess ||
          hipEventCreateWithFlags(&hm->ev_fork, hipEventDisableTiming) != hipSuccess ||
@@ -534,34 +514,36 @@ extern "C" int tuch_hd_model_create_k(tuch_hd_model** out, const tuch_contact_mo
         *out = nullptr;
         return TUCH_ERR_HIP;
     }
-    int rc = upload(&hm->idx, idx.data(), idx.size());
-    if (rc == TUCH_OK) rc = upload(&hm->w, w.data(), w.size());
-    if (rc == TUCH_OK) rc = upload(&hm->face, face.data(), face.size());
-    if (rc == TUCH_OK) rc = upload(&hm->tv, tv.data(), tv.size());
-    if (rc == TUCH_OK) rc = upload(&hm->mask_id, mask_id.data(), mask_id.size());
-    if (rc == TUCH_OK) rc = upload(&hm->orig, order.data(), order.size());
-    if (rc == TUCH_OK) {
-        std::vector<int32_t> inverse(N);
-        for (int k = 0; k < N; ++k) inverse[order[k]] = k;
-        rc = upload(&hm->by_orig, inverse.data(), inverse.size());
-    }
-    if (rc == TUCH_OK) rc = upload(&hm->v_off, v_off.data(), v_off.size());
-    if (rc == TUCH_OK) rc = upload(&hm->v_ent, v_ent.data(), v_ent.size());
-    if (rc == TUCH_OK) rc = upload(&hm->offsets, offsets.data(), offsets.size());
-    if (rc != TUCH_OK) {
-        tuch_hd_model_destroy(hm);
-        *out = nullptr;
-        return rc;
-    }
-    *out = hm;
-    return TUCH_OK;
+    std::vector<int32_t> inverse(N);
+    for (int k = 0; k < N; ++k) inverse[order[k]] = k;
+    tuch_tables& tb = hm->tables;
+    tb.put(&hm->idx, idx.data(), idx.size());
+    tb.put(&hm->w, w.data(), w.size());
+    tb.put(&hm->face, face.data(), face.size());
+    tb.put(&hm->tv, tv.data(), tv.size());
+    tb.put(&hm->mask_id, mask_id.data(), mask_id.size());
+    tb.put(&hm->orig, order.data(), order.size());
+    tb.put(&hm->by_orig, inverse.data(), inverse.size());
+    tb.put(&hm->v_off, v_off.data(), v_off.size());
+    tb.put(&hm->v_ent, v_ent.data(), v_ent.size());
+    tb.put(&hm->offsets, offsets.data(), offsets.size());
+    const int rc = tb.rc;
+    *out = rc == TUCH_OK ? hm : nullptr;
+    if (rc != TUCH_OK) tuch_hd_model_destroy(hm);
+    return rc;
+}
+
+extern "C" int tuch_hd_model_create(tuch_hd_model** out, const tuch_contact_model* cm, int N, const int32_t* hd_idx,
+                                    const float* hd_w, const int32_t* hd_face)
+{
+    return tuch_hd_model_create_k(out, cm, N, 3, hd_idx, hd_w, hd_face);
 }
 
 extern "C" int tuch_hd_model_info(const tuch_hd_model* hm, int* N, int32_t* order_host)
 {
     TUCH_REQUIRE(hm, "tuch_hd_model_info: null model");
     if (N) *N = hm->N;
-    if (order_host) memcpy(order_host, hm->order_host->data(), sizeof(int32_t) * hm->N);
+    if (order_host) memcpy(order_host, hm->order_host.data(), sizeof(int32_t) * hm->N);
     return TUCH_OK;
 }
 
@@ -635,7 +617,7 @@ extern "C" int tuch_hd_contact_fwd(const tuch_hd_model* hm, const float* verts, 
     // to visit ~40 % of the rows, and building the seeds cost more than the sampling pass they replace)
     // the inside test of the points beside their search: fork here, join in front of the terms
     const bool overlap = hm->cm->opt.hd_overlap != 0;
-    std::unique_lock<std::mutex> lock(*hm->enqueue, std::defer_lock);
+    std::unique_lock<std::mutex> lock(hm->enqueue, std::defer_lock);
     hipStream_t ws_stream = s;
     if (overlap) {
         lock.lock();
@@ -714,7 +696,7 @@ extern "C" int tuch_hd_contact_selection(const tuch_hd_model* hm, const void* sa
         if (hipMemcpy(sel.data(), sv + sl.sel, sel.size() * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return TUCH_ERR_HIP;
         for (int b = 0; b < B; ++b)
             for (int k = 0; k < N; ++k)
-                selected_host[(size_t)b * N + k] = k < counts_host[b] ? (*hm->order_host)[sel[(size_t)b * N + k]] : -1;
+                selected_host[(size_t)b * N + k] = k < counts_host[b] ? hm->order_host[sel[(size_t)b * N + k]] : -1;
     }
     return TUCH_OK;
 }
@@ -738,7 +720,7 @@ extern "C" int tuch_hd_contact_details(const tuch_hd_model* hm, const void* save
         for (int k = 0; k < N; ++k) {
             const int32_t p = part[(size_t)b * N + k];
             partner_host[(size_t)b * N + k] =
-                k < counts[b] && p >= 0 && p < counts[b] ? (*hm->order_host)[sel[(size_t)b * N + p]] : -1;
+                k < counts[b] && p >= 0 && p < counts[b] ? hm->order_host[sel[(size_t)b * N + p]] : -1;
         }
     return TUCH_OK;
 }

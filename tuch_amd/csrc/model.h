@@ -7,6 +7,8 @@
 // Cluster tree over the faces (cluster_tree.hip): host form.  nodes[i] = {cap_off, cap_len, exact_off,
 // exact_len (0 for inner nodes), skip, child0, child1, num_faces}, preorder numbering; offsets index
 // the stream (vidx, sign): leaf strips first ([0, exact_len)), then the boundary caps of all nodes.
+enum { kNodeCapOff, kNodeCapLen, kNodeExactOff, kNodeExactLen, kNodeSkip, kNodeChild0, kNodeChild1, kNodeFaces, kNodeWords };
+struct tuch_rows { int first, count; };
 struct tuch_cluster_tree {
     int V = 0, F = 0, num_nodes = 0, exact_len = 0, stream_len = 0, num_qblocks = 0, num_heights = 0;
     std::vector<int32_t> nodes;
@@ -22,6 +24,17 @@ struct tuch_cluster_tree {
     // vertex belongs to exactly one leaf (the first leaf in preorder that touches it)
     std::vector<int32_t> rows;
     std::vector<int32_t> face_leaf;                   // [F]: sequence number (preorder) of the leaf that holds the face
+
+    int node(int i, int field) const { return nodes[(size_t)i * kNodeWords + field]; }
+    int skip(int i) const { return node(i, kNodeSkip); }              // the first node behind the subtree of i
+    int child0(int i) const { return node(i, kNodeChild0); }          // -1: i is a leaf
+    int child1(int i) const { return node(i, kNodeChild1); }
+    bool is_leaf(int i) const { return child0(i) < 0; }
+    int num_faces(int i) const { return node(i, kNodeFaces); }
+    int num_leaves() const { return height_off[1]; }
+    int leaf_node(int k) const { return height_nodes[k]; }            // the k-th leaf in preorder
+    tuch_rows rows_of(int i) const { return {rows[(size_t)i * 2], rows[(size_t)i * 2 + 1]}; }
+    tuch_rows leaf_rows(int k) const { return rows_of(leaf_node(k)); }
 };
 
 bool tuch_cluster_tree_build_impl(int V, int F, const int32_t* faces, int leaf_faces, tuch_cluster_tree& t);
@@ -101,7 +114,7 @@ extern "C" int tuch_winding_points(const tuch_contact_model* m, const float* ver
                                    uint8_t* exterior, void* workspace, size_t workspace_bytes, void* stream);
 
 struct tuch_contact_model {
-    int device;
+    tuch_tables tables;        // owns every device table below
     tuch_options opt;
     int V, F;
     int32_t* faces;            // [F,3]
@@ -147,15 +160,13 @@ struct tuch_contact_model {
     int mask_symmetric;        // geomask[i][j] == geomask[j][i] for all i, j
     int tree_num_frontiers;
     int tree_leaf_runs_tile;       // 1: the leaves' strip runs [ex_off, ex_off + ex_len) tile [0, tree_exact_len) without gaps
-    int* tree_frontier_off_host;   // [tree_num_frontiers+1]
-    int* tree_sub_leaf_host;       // host copy of tree_sub_leaf
-    int32_t* tree_face_leaf_host;  // [F] leaf (preorder sequence number) of every face, host copy (or nullptr)
-    int32_t* tree_qperm_host;      // [tree_qblocks*128] host copy of tree_qperm (or nullptr)
+    std::vector<int32_t> tree_frontier_off_host;   // [tree_num_frontiers+1]
+    std::vector<int32_t> tree_face_leaf_host;      // [F] leaf (preorder sequence number) of every face (or empty)
+    std::vector<int32_t> tree_qperm_host;          // [tree_qblocks*128] host copy of tree_qperm (or empty)
     // ordered one-ring of every vertex (closed manifold meshes only, else nullptr): ring_vidx[ring_off[v] + j] = r_j
     // with the faces around v being (v, r_j, r_{j+1}) in their own orientation, j cyclic (ray_winding.hip)
     int32_t* ring_off;         // [V+1]
     int32_t* ring_vidx;
-    int ring_max;              // largest valence
     // segments (tuch/utils/segmentation.py): CSR over segments
     int num_segments, num_caps, seg_q_total, seg_f_total;
     int32_t* seg_q_off;        // [S+1] into seg_q_vidx
@@ -188,8 +199,6 @@ struct tuch_contact_model {
     int num_seg_blocks;        // 64-query blocks over all segments
     int32_t* seg_blocks;       // [num_seg_blocks][2] = (segment, first query within the segment)
     int32_t* seg_of_q;         // [seg_q_total] segment of every entry of seg_q_vidx
-    int* seg_q_off_host;       // host copies for grid sizing
-    int* seg_f_off_host;
     int seg_q_max;
     // contact regions (ContactSigSMPL / classes): CSR over regions
     int num_regions, num_pairs, region_max;
@@ -200,5 +209,4 @@ struct tuch_contact_model {
     // bit k of a row = geomask[row vertex][k-th vertex of the second region]
     uint32_t* pair_mask;       // concatenated [n1][ceil(n2/32)] blocks, or nullptr
     int64_t* pair_mask_off;    // [P+1] word offsets
-    int* region_off_host;
 };

@@ -27,6 +27,7 @@
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct tuch_smpl_model {
+    tuch_tables tables;        // owns the device tables below
     int V, N3;                 // vertices, 3V
     int N3p;                   // row stride of blend / v_posed / g_vposed: 3V rounded up to 64 floats (rows start on 256 bytes)
     float* blend;              // [kFeatRows][N3p]: posedirs (207) | shapedirs^T (10) | v_template | zero rows; zero padding columns
@@ -43,7 +44,6 @@ struct tuch_smpl_model {
     int max_depth;
     int32_t* extra_ids;        // [21]
     int32_t* joint_map;        // [49]
-    int parents_host[24];
 };
 
 namespace {
@@ -1019,22 +1019,35 @@ BwdLayout bwd_layout(const tuch_smpl_model* m, int B)
     return l;
 }
 
-template <typename T>
-int upload(T** dst, const T* src, size_t count)
+// sparse skinning tables: the non-zero weights of every vertex in ascending joint order
+void put_sparse_skinning(tuch_smpl_model* m, const float* lbs_weights)
 {
-    return tuch_table_upload((void**)dst, src, count * sizeof(T));
+    const int V = m->V;
+    for (int v = 0; v < V; ++v) {
+        int n = 0;
+        for (int j = 0; j < kJoints; ++j) n += lbs_weights[(size_t)v * kJoints + j] != 0.0f;
+        m->skin_nnz = std::max(m->skin_nnz, n);
+    }
+    const bool off = getenv("TUCH_SKIN_DENSE") && atoi(getenv("TUCH_SKIN_DENSE")) != 0;     // A/B, tests (read per model)
+    if (m->skin_nnz > 4 || off) return;
+    std::vector<int32_t> sj((size_t)4 * V, 0);
+    std::vector<float> sw((size_t)4 * V, 0.f);
+    for (int v = 0; v < V; ++v) {
+        int n = 0;
+        for (int j = 0; j < kJoints; ++j)
+            if (lbs_weights[(size_t)v * kJoints + j] != 0.0f) {
+                sj[(size_t)n * V + v] = j;
+                sw[(size_t)n * V + v] = lbs_weights[(size_t)v * kJoints + j];
+                ++n;
+            }
+    }
+    m->tables.put(&m->skin_joint, sj.data(), sj.size());
+    m->tables.put(&m->skin_weight, sw.data(), sw.size());
 }
 
 }  // namespace
 
-extern "C" void tuch_smpl_model_destroy(tuch_smpl_model* m)
-{
-    if (!m) return;
-    void* dev[] = {m->blend, m->J_template, m->J_shapedirs, m->weights, m->weights_t, m->Jrx, m->parents, m->extra_ids, m->joint_map,
-                   m->skin_joint, m->skin_weight};
-    for (void* p : dev) tuch_table_free(p);
-    free(m);
-}
+extern "C" void tuch_smpl_model_destroy(tuch_smpl_model* m) { delete m; }
 
 // All arrays are HOST pointers in the layouts smplx registers them:
 // v_template [V,3], shapedirs [V,3,10], posedirs [207, 3V], J_regressor [24,V], lbs_weights [V,24],
@@ -1053,7 +1066,7 @@ extern "C" int tuch_smpl_model_create(tuch_smpl_model** out, int V, const float*
         TUCH_REQUIRE(extra_vertex_ids[e] >= 0 && extra_vertex_ids[e] < V, "tuch_smpl_model_create: bad picked vertex");
     for (int o = 0; o < kOutJoints; ++o)
         TUCH_REQUIRE(joint_map[o] >= 0 && joint_map[o] < kAllJoints, "tuch_smpl_model_create: bad joint_map entry");
-    tuch_smpl_model* m = (tuch_smpl_model*)calloc(1, sizeof(tuch_smpl_model));
+    tuch_smpl_model* m = new tuch_smpl_model();
     m->V = V;
     m->N3 = 3 * V;
     m->N3p = ceil_div(m->N3, 64) * 64;
@@ -1081,58 +1094,28 @@ extern "C" int tuch_smpl_model_create(tuch_smpl_model** out, int V, const float*
     memcpy(par, parents, sizeof(int32_t) * kJoints);
     par[0] = -1;
     par[kJoints] = 0;
-    m->max_depth = 0;
     for (int k = 1; k < kJoints; ++k) {               // parents come first: one pass
         par[kJoints + k] = par[kJoints + par[k]] + 1;
         m->max_depth = std::max(m->max_depth, (int)par[kJoints + k]);
     }
-    memcpy(m->parents_host, par, sizeof(int32_t) * kJoints);
-    int rc = upload(&m->blend, blend.data(), blend.size());
-    if (rc == TUCH_OK) rc = upload(&m->J_template, jt.data(), jt.size());
-    if (rc == TUCH_OK) rc = upload(&m->J_shapedirs, js.data(), js.size());
-    if (rc == TUCH_OK) rc = upload(&m->weights, lbs_weights, (size_t)V * kJoints);
-    if (rc == TUCH_OK) {
-        std::vector<float> wt((size_t)kJoints * V);
-        for (int v = 0; v < V; ++v)
-            for (int j = 0; j < kJoints; ++j) wt[(size_t)j * V + v] = lbs_weights[(size_t)v * kJoints + j];
-        rc = upload(&m->weights_t, wt.data(), wt.size());
-    }
-    if (rc == TUCH_OK) {
-        // sparse skinning tables: the non-zero weights of every vertex in ascending joint order
-        m->skin_nnz = 0;
-        for (int v = 0; v < V; ++v) {
-            int n = 0;
-            for (int j = 0; j < kJoints; ++j) n += lbs_weights[(size_t)v * kJoints + j] != 0.0f;
-            m->skin_nnz = std::max(m->skin_nnz, n);
-        }
-        const bool off = getenv("TUCH_SKIN_DENSE") && atoi(getenv("TUCH_SKIN_DENSE")) != 0;     // A/B, tests (read per model)
-        if (m->skin_nnz <= 4 && !off) {
-            std::vector<int32_t> sj((size_t)4 * V, 0);
-            std::vector<float> sw((size_t)4 * V, 0.f);
-            for (int v = 0; v < V; ++v) {
-                int n = 0;
-                for (int j = 0; j < kJoints; ++j)
-                    if (lbs_weights[(size_t)v * kJoints + j] != 0.0f) {
-                        sj[(size_t)n * V + v] = j;
-                        sw[(size_t)n * V + v] = lbs_weights[(size_t)v * kJoints + j];
-                        ++n;
-                    }
-            }
-            rc = upload(&m->skin_joint, sj.data(), sj.size());
-            if (rc == TUCH_OK) rc = upload(&m->skin_weight, sw.data(), sw.size());
-        }
-    }
-    if (rc == TUCH_OK) rc = upload(&m->Jrx, J_regressor_extra, (size_t)kExtra * V);
-    if (rc == TUCH_OK) rc = upload(&m->parents, par, 2 * kJoints);
-    if (rc == TUCH_OK) rc = upload(&m->extra_ids, extra_vertex_ids, kPicked);
-    if (rc == TUCH_OK) rc = upload(&m->joint_map, joint_map, kOutJoints);
-    if (rc != TUCH_OK) {
-        tuch_smpl_model_destroy(m);
-        *out = nullptr;
-        return rc;
-    }
-    *out = m;
-    return TUCH_OK;
+    tuch_tables& tb = m->tables;
+    tb.put(&m->blend, blend.data(), blend.size());
+    tb.put(&m->J_template, jt.data(), jt.size());
+    tb.put(&m->J_shapedirs, js.data(), js.size());
+    tb.put(&m->weights, lbs_weights, (size_t)V * kJoints);
+    std::vector<float> wt((size_t)kJoints * V);
+    for (int v = 0; v < V; ++v)
+        for (int j = 0; j < kJoints; ++j) wt[(size_t)j * V + v] = lbs_weights[(size_t)v * kJoints + j];
+    tb.put(&m->weights_t, wt.data(), wt.size());
+    put_sparse_skinning(m, lbs_weights);
+    tb.put(&m->Jrx, J_regressor_extra, (size_t)kExtra * V);
+    tb.put(&m->parents, par, 2 * kJoints);
+    tb.put(&m->extra_ids, extra_vertex_ids, kPicked);
+    tb.put(&m->joint_map, joint_map, kOutJoints);
+    const int rc = tb.rc;
+    *out = rc == TUCH_OK ? m : nullptr;
+    if (rc != TUCH_OK) tuch_smpl_model_destroy(m);
+    return rc;
 }
 
 extern "C" size_t tuch_smpl_forward_workspace_bytes(const tuch_smpl_model* m, int B)

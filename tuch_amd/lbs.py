@@ -27,10 +27,7 @@ class SmplDeviceModel:
         assert arrays[3].shape == (24, self.num_verts) and arrays[4].shape == (self.num_verts, 24)
         assert arrays[6].shape == (21,) and arrays[7].shape == (9, self.num_verts) and arrays[8].shape == (49,)
         handle = ctypes.c_void_p(0)
-        import contextlib
-        import os
-        host_tables = os.environ.get('TUCH_HOST_TABLES', '0') not in ('', '0')     # sanitizer runs of the table builders
-        with (contextlib.nullcontext() if host_tables else torch.cuda.device(self.device)):
+        with _C.create_context(self.device):
             _C.check(_C.lib().tuch_smpl_model_create(ctypes.byref(handle), self.num_verts,
                                                      *[a.ctypes.data_as(ctypes.c_void_p) for a in arrays]))
         self._handle = handle

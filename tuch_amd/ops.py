@@ -972,12 +972,9 @@ class ContactModel:
     def _handle(self):
         if self._h is None:
             keep, gm, num_caps, num_regions = self._host
-            host_tables = os.environ.get('TUCH_HOST_TABLES', '0') not in ('', '0')    # sanitizer runs of the table builders
-            if self.device.type != 'cuda' and not host_tables:
-                raise _C.TuchError('tuch_amd kernels need a HIP device, the model was created for %s' % self.device)
             p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a.size else ctypes.c_void_p(0)
             handle = ctypes.c_void_p(0)
-            with (contextlib.nullcontext() if host_tables else torch.cuda.device(self.device)):
+            with _C.create_context(self.device):
                 _C.check(_C.lib().tuch_contact_model_create(
                     ctypes.byref(handle), self.num_verts, self.num_faces, p(keep['faces']),
                     gm.ctypes.data_as(ctypes.c_void_p) if gm is not None else ctypes.c_void_p(0),
@@ -1259,8 +1256,7 @@ class HDModel:
             idx, w, face = self._host
             handle = ctypes.c_void_p(0)
             cm = self.contact_model._handle
-            host_tables = os.environ.get('TUCH_HOST_TABLES', '0') not in ('', '0')
-            with (contextlib.nullcontext() if host_tables else torch.cuda.device(self.contact_model.device)):
+            with _C.create_context(self.contact_model.device):
                 _C.check(_C.lib().tuch_hd_model_create_k(ctypes.byref(handle), cm, self.num_points, self.row_nnz,
                                                          idx.ctypes.data_as(ctypes.c_void_p), w.ctypes.data_as(ctypes.c_void_p),
                                                          face.ctypes.data_as(ctypes.c_void_p)))
