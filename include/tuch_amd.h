@@ -28,7 +28,12 @@ extern "C" {
 #endif
 
 const char* tuch_last_error(void);
+/* 2.  Since 1: one entry point per operation -- the superseded stage-2, nearest-vertex and body-model forms are gone,
+ * tuch_v2v_min_model, tuch_smpl_backward_split and tuch_smplify_stage2_fused take the argument lists given below. */
 int tuch_abi_version(void);
+
+/* per-model constants, see tuch_contact_model_create below */
+typedef struct tuch_contact_model tuch_contact_model;
 
 /* ---- tuch/utils/contact.py ------------------------------------------------------- */
 
@@ -179,55 +184,41 @@ int tuch_smplify_objective(const float* small_terms, const float* contact_terms,
 int tuch_smplify_objective_bwd(const float* grad_out, int B, int P, float contact_scale, float r2r_scale,
                                float* grad_small, float* grad_contact, float* grad_r2r, void* stream);
 
-/* Backward of the tail of the stage-2 objective (small terms + contact sums + region minima -> scalar) in one launch:
- * grad_contact [B,2] = contact_scale * g (0 for bodies with valid == 0), grad_r2r [B,P] = r2r_scale * g, and the unit
- * gradients left by tuch_smplify_small_terms (gj [B,NJ,3], gc [B,3], gp [B,69] or NULL) scaled by g = grad_out[0]. */
-int tuch_smplify_tail_bwd(const float* grad_out, const uint8_t* valid, const float* gj, const float* gc, const float* gp,
-                          int B, int NJ, int P, float contact_scale, float r2r_scale, float* grad_contact, float* grad_r2r,
-                          float* gj_out, float* gc_out, float* gp_out, void* stream);
-
-/* The same tail (tuch/smplify/losses.py:96-123) in one launch per direction: contact sums + the row of region minima per
- * body and the objective's total (the block that finishes last adds the bodies up); backward: upstream scalar -> vertex
- * gradient (contact terms and region minima, grad_points pre-zeroed) and the scaled unit gradients of the small terms.
- * share: [B] floats of scratch; ticket: one int, zero before the first call, left zero by every call. */
-/* tuch_smplify_stage2_finish and -- when grad_points is given -- tuch_smplify_stage2_bwd for a UNIT upstream gradient in
- * one launch: the objective is the root of the fit's autograd graph, so its vertex gradient can be written while the sums
- * are formed.  share: tuch_smplify_stage2_fused_scratch_floats(B) floats; ticket: one int, zero before the call;
- * grad_points [B,N,3] pre-zeroed or NULL; ij [B,P,2] from tuch_region_pair_min or NULL. */
+/* The tail of the stage-2 objective (tuch/smplify/losses.py:96-123) and its vertex gradient in one launch:
+ *   out[0] = sum_b [ small_terms[b,0] + small_terms[b,1] + contact_scale (interior_b + exterior_b) + r2r_scale sum_p d2[b,p] ]
+ * with the contact sums of tuch_contact_terms_fwd (0 for bodies with body_valid == 0; body_valid may be NULL) and d2 the
+ * region pairs' minima, decoded from pair_keys [B,P] (tuch_region_pair_keys of `model`; P = 0: NULL, no region term).
+ * The objective is the root of the fit's autograd graph, so the gradient for a UNIT upstream gradient is scattered while
+ * the sums are formed: into grad_points [B,N,3] (float atomics, pre-zeroed) or into grad_fixed_zeroed (deterministic
+ * mode, below); give at most one of the two, neither: the value alone.  out[0] is a fixed-order sum, the same bits in all
+ * three cases.  share: tuch_smplify_stage2_fused_scratch_floats(B) floats; ticket: one int, zero before the call, left
+ * zero.  The unit gradients of the small terms are tuch_smplify_small_terms' own outputs. */
 size_t tuch_smplify_stage2_fused_scratch_floats(int B);
 int tuch_smplify_stage2_fused(const float* points, const int32_t* partner, const uint8_t* exterior,
                               const uint8_t* body_valid, int B, int N, int mode, float euclthres,
-                              const float* small_terms, const float* r2r, const int32_t* ij, int P, float contact_scale,
-                              float r2r_scale, float* share, int* ticket, float* terms, float* out, float* grad_points,
-                              const tuch_contact_model* model, const void* pair_keys, void* grad_fixed_zeroed, void* stream);
+                              const float* small_terms, int P, float contact_scale, float r2r_scale, float* share,
+                              int* ticket, float* out, float* grad_points, const tuch_contact_model* model,
+                              const void* pair_keys, void* grad_fixed_zeroed, void* stream);
 /* Deterministic mode -- ON by default (TUCH_DETERMINISTIC=0 in the environment when the library is loaded, or
  * tuch_set_deterministic(0), selects float atomics: last-ulp run-to-run noise in the gradients): the gradient scatters of
- * tuch_smplify_stage2_fused (contact terms, region minima) and of tuch_smpl_backward (skinning adjoint) accumulate 64-bit
+ * tuch_smplify_stage2_fused (contact terms, region minima) and of tuch_smpl_backward_split (skinning adjoint) accumulate 64-bit
  * fixed-point numbers (2^-36) with integer atomics instead of floats -- sums that do not depend on the order of arrival,
  * so an SMPLify-DC fit reproduces bit for bit.  tuch_smplify_stage2_fused then wants grad_fixed_zeroed = B*N*3 zeroed
- * 64-bit words (NULL: float atomics, whatever the mode) and converts to grad_points with a second launch; with
- * grad_points = NULL the accumulators are the result (see g_verts_fixed of tuch_smpl_backward_split_add).
+ * 64-bit words (NULL: float atomics, whatever the mode): the accumulators are the result, read as they are by
+ * g_verts_fixed of tuch_smpl_backward_split or converted by tuch_fixed_to_float.
  * VALID RANGE of the fixed-point sums: |sum| < 2^27 = 1.3e8 (beyond, the unsigned 64-bit accumulator wraps silently) and
  * contributions below 2^-37 = 7e-12 round to zero.  Gradient magnitudes scale with contact_scale / r2r_scale: with the
  * reference's weights (10, 2000) and metre-scale bodies the per-vertex gradients are < 1e5. */
-/* n fixed-point sums -> floats (what tuch_smplify_stage2_fused does itself when grad_points is given) */
+/* n fixed-point sums -> floats */
 int tuch_fixed_to_float(const void* fixed, size_t n, float* out, void* stream);
 void tuch_set_deterministic(int on);
 int tuch_get_deterministic(void);
 
 /* The region-pair search of tuch_region_pair_min alone, for tuch_smplify_stage2_fused(model, pair_keys): keys [B,P]
  * 64-bit words, ZERO on entry (the caller clears them with whatever else it clears); no clearing and no finalize
- * launch.  pair_keys given: r2r / ij of tuch_smplify_stage2_fused are ignored. */
+ * launch. */
 int tuch_region_pair_keys(const tuch_contact_model* model, const float* verts, int B, const uint8_t* select,
                           int use_geomask, void* keys_zeroed, void* stream);
-int tuch_smplify_stage2_finish(const float* points, const int32_t* partner, const uint8_t* exterior,
-                               const uint8_t* body_valid, int B, int N, int mode, float euclthres,
-                               const float* small_terms, const float* r2r, int P, float contact_scale, float r2r_scale,
-                               float* share, int* ticket, float* terms, float* out, void* stream);
-int tuch_smplify_stage2_bwd(const float* grad_out, const uint8_t* body_valid, const float* points, const int32_t* partner,
-                            const uint8_t* exterior, int B, int N, int mode, float euclthres, float contact_scale,
-                            const int32_t* ij, int P, float r2r_scale, const float* gj, const float* gc, const float* gp,
-                            int NJ, float* grad_points, float* gj_out, float* gc_out, float* gp_out, void* stream);
 
 /* ---- per-model constants -------------------------------------------------------------
  * Host tables in, device copies kept by the handle.  Segments follow
@@ -235,8 +226,6 @@ int tuch_smplify_stage2_bwd(const float* grad_out, const uint8_t* body_valid, co
  * closed segment where cap vertex c (global numbering over all segments) has index V + c;
  * cap_* = the ordered boundary loops whose mean is the cap vertex.  Regions follow
  * ContactSigSMPL / classes (train_module.py:64-66): CSR vertex lists and [P,2] pairs. */
-typedef struct tuch_contact_model tuch_contact_model;
-
 int tuch_contact_model_create(tuch_contact_model** out, int V, int F, const int32_t* faces /* host [F,3] */,
                               const uint8_t* geomask /* host [V,V] bytes or NULL */,
                               int num_segments, const int32_t* seg_q_off, const int32_t* seg_q_vidx,
@@ -261,9 +250,6 @@ int tuch_contact_model_get_option(const tuch_contact_model* model, const char* n
 int tuch_contact_model_canary_hits(const tuch_contact_model* model, int* hits_host, int reset);
 int tuch_contact_model_canary_selftest(const tuch_contact_model* model, void* workspace, size_t workspace_bytes, void* stream);
 const uint64_t* tuch_contact_model_mask_bits(const tuch_contact_model* model);
-const int32_t* tuch_contact_model_faces(const tuch_contact_model* model);
-/* eight device ints, zero between calls: arrival counters for tuch_smplify_stage2_finish (one per stream in flight) */
-int32_t* tuch_contact_model_tickets(const tuch_contact_model* model);
 /* The geodesic mask packed in the cluster tree's vertex order (device, same layout as mask_bits with vertex v
  * replaced by its position in tuch_cluster_tree_export's qperm), or NULL without tree or mask: neighbouring
  * positions are neighbours on the surface, so a wavefront of nearby points touches few mask words. */
@@ -302,21 +288,18 @@ size_t tuch_v2v_model_workspace_bytes(const tuch_contact_model* model, int B);
  * iteration's partner is still admissible and almost as close, so nearly every box is pruned at once.  The result
  * does not depend on the hint (any content is safe); only the run time does.  Used only with a cluster tree. */
 size_t tuch_v2v_hint_bytes(const tuch_contact_model* model, int B);
-int tuch_v2v_min_model(const tuch_contact_model* model, const float* verts, int B, float* min_d2,
-                       int32_t* argmin, void* hint_inout, void* workspace, size_t workspace_bytes, void* stream);
-/* The same search for callers that run other kernels beside it on another stream (as ops.ContactModel.exterior_and_partner
- * does with the inside test): leave_room & 1 caps the walk's occupancy so that the neighbours' small kernels are not
- * starved of wave slots; leave_room & 2: the caller expects hint_inout to hold near-final partners (an iterative fit calling
- * again after a small parameter update) -- the search then uses fewer, longer wavefronts.  Same results either way. */
-int tuch_v2v_min_model_shared(const tuch_contact_model* model, const float* verts, int B, float* min_d2,
-                              int32_t* argmin, void* hint_inout, void* workspace, size_t workspace_bytes, int leave_room,
-                              void* stream);
-/* The same; additionally `zero` (16-byte aligned, zero_bytes a multiple of 16; or NULL / 0) is cleared by the call's first
- * kernel: on the stream, before anything the caller enqueues behind the call -- instead of a fill launch of its own
- * (SMPLify-DC stage 2: the vertex gradient its tail scatters into, the tail's arrival counter, the region pairs' keys). */
-int tuch_v2v_min_model_shared_zero(const tuch_contact_model* model, const float* verts, int B, float* min_d2, int32_t* argmin,
-                                   void* hint_inout, void* workspace, size_t workspace_bytes, int leave_room, void* zero,
-                                   size_t zero_bytes, void* stream);
+/* flags: for callers that run other kernels beside the search on another stream (as ops.ContactModel.exterior_and_partner
+ * does with the inside test), TUCH_V2V_LEAVE_ROOM caps the walk's occupancy so that the neighbours' small kernels are not
+ * starved of wave slots; TUCH_V2V_NEAR_FINAL: the caller expects hint_inout to hold near-final partners (an iterative
+ * fit calling again after a small parameter update) -- the search then uses fewer, longer wavefronts.  Same results
+ * whatever the flags.
+ * `zero` (16-byte aligned, zero_bytes a multiple of 16; or NULL / 0) is cleared by the call's first kernel: on the stream,
+ * before anything the caller enqueues behind the call -- instead of a fill launch of its own (SMPLify-DC stage 2: the
+ * vertex gradient its tail scatters into, the tail's arrival counter, the region pairs' keys). */
+enum { TUCH_V2V_LEAVE_ROOM = 1, TUCH_V2V_NEAR_FINAL = 2 };
+int tuch_v2v_min_model(const tuch_contact_model* model, const float* verts, int B, float* min_d2, int32_t* argmin,
+                       void* hint_inout, void* workspace, size_t workspace_bytes, int flags, void* zero, size_t zero_bytes,
+                       void* stream);
 
 /* Cluster tree over the faces of a closed mesh (host only, no device needed): the structure behind the
  * hierarchical evaluation of winding_numbers (tuch/utils/contact.py:112-147) inside tuch_exterior_flags.
@@ -444,41 +427,31 @@ int tuch_smpl_model_create(tuch_smpl_model** out, int V, const float* v_template
 void tuch_smpl_model_destroy(tuch_smpl_model* model);
 int tuch_smpl_model_info(const tuch_smpl_model* model, int* V);
 
-/* SMPL.forward(betas, body_pose, global_orient, pose2rot): betas [B,10]; pose [B,72] axis-angle
- * (pose2rot != 0) or [B,24,3,3] rotation matrices -> vertices [B,V,3], joints [B,49,3].
- * The forward workspace keeps the intermediates tuch_smpl_backward needs. */
+/* SMPL.forward(betas, body_pose, global_orient, pose2rot) with the pose as its caller holds it (tuch/models/smpl.py:44-47):
+ * betas [B,10]; global_orient [B,3] and body_pose [B,69] axis-angle (pose2rot != 0) or [B,1,3,3] and [B,23,3,3] rotation
+ * matrices, row strides in floats -> vertices [B,V,3], joints [B,49,3].  One concatenated pose [B,72] (w = 3) or
+ * [B,24,3,3] (w = 9): global_orient = pose, body_pose = pose + w, both strides 24 w.
+ * The forward workspace keeps the intermediates tuch_smpl_backward_split needs. */
 size_t tuch_smpl_forward_workspace_bytes(const tuch_smpl_model* model, int B);
-int tuch_smpl_forward(const tuch_smpl_model* model, const float* betas, const float* pose, int pose2rot, int B,
-                      float* verts, float* joints, void* workspace, size_t workspace_bytes, void* stream);
-/* The same with the pose as SMPL.forward's caller holds it (tuch/models/smpl.py:44-47: global_orient [B,3] / [B,1,3,3]
- * and body_pose [B,69] / [B,23,3,3], two tensors): no concatenated copy; row strides in floats, so views work too. */
 int tuch_smpl_forward_split(const tuch_smpl_model* model, const float* betas, const float* global_orient,
                             int global_orient_stride, const float* body_pose, int body_pose_stride, int pose2rot, int B,
                             float* verts, float* joints, void* workspace, size_t workspace_bytes, void* stream);
-/* Adjoint: g_verts [B,V,3] / g_joints [B,49,3] (either may be NULL) -> g_betas [B,10],
- * g_pose [B,72] or [B,24,3,3]. */
+/* Adjoint: g_verts [B,V,3] / g_joints [B,49,3] (either may be NULL) -> g_betas [B,10] and the pose gradient as the two
+ * tensors of the forward call (same shapes, row strides in floats).
+ * g_body_pose_add (same shape as g_body_pose, row stride in floats; or NULL): a gradient the caller already holds for
+ * body_pose, g_body_pose = this call's gradient + that one.  In SMPLify-DC body_pose feeds the body model and the pose
+ * prior (tuch/smplify/losses.py:63): autograd would add the two gradients in a separate launch.
+ * g_verts_fixed (here and in tuch_smpl_backward_split_adam; or NULL): [B,V,3] 64-bit fixed-point sums (2^-36, the
+ * accumulators tuch_smplify_stage2_fused leaves in deterministic mode) ADDED to g_verts where the skinning adjoint reads
+ * it -- the stage-2 tail's vertex gradient without a conversion launch on the step's serial tail. */
 size_t tuch_smpl_backward_workspace_bytes(const tuch_smpl_model* model, int B);
-int tuch_smpl_backward(const tuch_smpl_model* model, const float* pose, int pose2rot, int B,
-                       const void* fwd_workspace, const float* g_verts, const float* g_joints, float* g_betas,
-                       float* g_pose, void* workspace, size_t workspace_bytes, void* stream);
 int tuch_smpl_backward_split(const tuch_smpl_model* model, const float* global_orient, int global_orient_stride,
                              const float* body_pose, int body_pose_stride, int pose2rot, int B,
                              const void* fwd_workspace, const float* g_verts, const float* g_joints, float* g_betas,
                              float* g_global_orient, int g_global_orient_stride, float* g_body_pose,
-                             int g_body_pose_stride, void* workspace, size_t workspace_bytes, void* stream);
-/* The same with a gradient the caller already holds for body_pose (g_body_pose_add: same shape, row stride in floats; or
- * NULL): g_body_pose = this call's gradient + that one.  In SMPLify-DC body_pose feeds the body model and the pose prior
- * (tuch/smplify/losses.py:63): autograd would add the two gradients in a separate launch. */
-int tuch_smpl_backward_split_add(const tuch_smpl_model* model, const float* global_orient, int global_orient_stride,
-                                 const float* body_pose, int body_pose_stride, int pose2rot, int B,
-                                 const void* fwd_workspace, const float* g_verts, const float* g_joints, float* g_betas,
-                                 float* g_global_orient, int g_global_orient_stride, float* g_body_pose,
-                                 int g_body_pose_stride, const float* g_body_pose_add, int g_body_pose_add_stride,
-                                 void* workspace, size_t workspace_bytes, void* stream, const void* g_verts_fixed);
-/* g_verts_fixed (here and in tuch_smpl_backward_split_adam; or NULL): [B,V,3] 64-bit fixed-point sums (2^-36, the accumulators
- * tuch_smplify_stage2_fused leaves when it is called with grad_points = NULL in deterministic mode) ADDED to g_verts where the
- * skinning adjoint reads it -- the stage-2 tail's vertex gradient without a conversion launch on the step's serial tail. */
-/* tuch_smpl_backward_split_add (axis-angle poses) + torch.optim.Adam's update (tuch_adam_step's arithmetic) of the two pose
+                             int g_body_pose_stride, const float* g_body_pose_add, int g_body_pose_add_stride,
+                             void* workspace, size_t workspace_bytes, void* stream, const void* g_verts_fixed);
+/* tuch_smpl_backward_split (axis-angle poses) + torch.optim.Adam's update (tuch_adam_step's arithmetic) of the two pose
  * tensors themselves, applied by the last backward kernel to the rows whose gradient it has just written: for a fit whose
  * optimiser holds exactly [global_orient, body_pose] and whose whole gradient arrives through this call (SMPLify-DC stage 2,
  * tuch/smplify/smplifydc.py:149-183: the body model + the pose prior via g_body_pose_add) -- the optimiser's own launch at

@@ -9,6 +9,8 @@ Tolerances (see DESIGN.md "Parity"):
     much noise; ours are direct differences);
   * losses: 1e-4 relative (north_star), gradients 1e-4 relative + 1e-6 of the largest entry.
 """
+import contextlib
+
 import numpy as np
 import pytest
 import torch
@@ -362,6 +364,62 @@ def test_contact_fitting_loss_vs_reference(tag, eu, sg, full, fused_tail, monkey
     if full:
         grad_close(mj.grad.cpu().numpy(), g[key + '_grad_joints'], 1e-5, '%s %s grad joints' % (tag, key))
         grad_close(pose.grad.cpu().numpy(), g[key + '_grad_pose'], 1e-5, '%s %s grad pose' % (tag, key))
+
+
+@pytest.mark.parametrize('det', [True, False])
+def test_stage2_tail_value_float_and_fixed_paths(det):
+    """The three forms of the fused stage-2 tail (ops._Stage2Tail: value only, float atomics, fixed-point sums) on the
+    full objective of `small` (V = 122: 16 points per block, eight blocks per body; region pairs, segments, real prior
+    and confidences).  No golden of SMALL lists an ignored body, so the bit-for-bit properties are checked twice: with
+    the golden's ignore_idxs and with body 1 ignored; the comparison with the golden uses its own ignore_idxs."""
+    from tuch_amd import ops
+    from tuch_amd.smplify.losses import contact_fitting_loss
+    from tuch_amd.utils.segmentation import BatchBodySegment
+    tag, key = 'small', 'smplify_e2_seg_full'
+    g, gm = golden(tag), golden_mask(tag)
+    t, prior, conf = _fitting_inputs(g, True)
+    batch = g['verts'].shape[0]
+    regions, pairs = gio.unpack_regions(g)
+    assert len(pairs) > 0 and ((g['gt_contact'] == 1) & g['has_discrete_contact'][:, None]).any()
+    cdict = {'classes': [list(p) for p in pairs], 'csig': regions}
+    face_tensor = t(g['faces'])[None].repeat(batch, 1, 1)
+    segs = gio.unpack_segments(g)
+    segments = BatchBodySegment(list(segs.keys()), face_tensor[0], segs)
+    geomask = t(gm)
+    fixed_inputs = [t(g[k]) for k in ('global_orient', 'betas', 'camera_t', 'camera_center', 'joints_2d', 'gt_contact',
+                                      'has_discrete_contact')]
+    go, betas, cam_t, cam_c, j2d, gt, hdc = fixed_inputs
+
+    def call(ignore, grads):
+        verts, mj, pose = (t(g[k]).requires_grad_(True) for k in ('verts', 'model_joints', 'body_pose'))
+        with contextlib.nullcontext() if grads else torch.no_grad():
+            loss = contact_fitting_loss(
+                pose, go, None, None, betas, mj, geomask, float(g['euclthres']), cam_t, cam_c, j2d, conf, prior, cdict,
+                [gt, None], ignore, hdc, verts, face_tensor=face_tensor, focal_length=5000.,
+                contact_loss_weight=float(g['contact_loss_weight']), segments=segments)
+        assert loss.requires_grad == grads
+        if grads:
+            loss.backward()
+        return loss.detach(), verts.grad, mj.grad, pose.grad
+
+    ignored_1 = torch.zeros(batch, dtype=torch.bool, device=dev())
+    ignored_1[1] = True
+    with ops.deterministic_mode(det):
+        for ignore in (t(g['ignore_idxs']), ignored_1):
+            value = call(ignore, False)[0]
+            loss, gv, gj, gp = call(ignore, True)
+            # fixed-order sums: the value does not depend on whether the scatter runs
+            assert torch.equal(value, loss), (value.item(), loss.item())
+            if det:
+                again = call(ignore, True)[1]
+                assert gv.abs().max() > 0 and torch.equal(gv, again)
+        if not det:     # (the last pass of the loop was body 1 ignored: the golden's own ignore_idxs again)
+            loss, gv, gj, gp = call(t(g['ignore_idxs']), True)
+            n_sel = float(((g['gt_contact'] == 1) & g['has_discrete_contact'][:, None]).sum())
+            assert_close(loss.item(), g[key + '_loss'], 1e-4, 2000 * 1e-6 * n_sel, key)
+            grad_close(gv.cpu().numpy(), g[key + '_grad_verts'], 2e-6, '%s %s float atomics grad verts' % (tag, key))
+            grad_close(gj.cpu().numpy(), g[key + '_grad_joints'], 1e-5, '%s %s float atomics grad joints' % (tag, key))
+            grad_close(gp.cpu().numpy(), g[key + '_grad_pose'], 1e-5, '%s %s float atomics grad pose' % (tag, key))
 
 
 def _full_train(tag='full'):

@@ -17,6 +17,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('TUCH_AMD_LIB') or os.path.join(_HERE, 'libtuch_amd.so')
 _lib = None
 
+ABI_VERSION = 2      # tuch_abi_version() of the library _SIGNATURES was written for
+
 # name -> (restype, argtypes); mirrors include/tuch_amd.h
 _SIGNATURES = {
     'tuch_last_error': (c_char_p, []),
@@ -61,7 +63,6 @@ _SIGNATURES = {
     'tuch_smplify_objective': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_void_p, c_void_p]),
     'tuch_smplify_objective_bwd': (c_int, [c_void_p, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p,
                                            c_void_p]),
-    'tuch_smplify_tail_bwd': (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_float, c_float] + [c_void_p] * 6),
     'tuch_contact_model_create': (c_int, [POINTER(c_void_p), c_int, c_int, c_void_p, c_void_p,
                                           c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_int, c_void_p, c_void_p,
@@ -72,8 +73,6 @@ _SIGNATURES = {
     'tuch_contact_model_canary_hits': (c_int, [c_void_p, POINTER(c_int), c_int]),
     'tuch_contact_model_canary_selftest': (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     'tuch_contact_model_mask_bits': (c_void_p, [c_void_p]),
-    'tuch_contact_model_faces': (c_void_p, [c_void_p]),
-    'tuch_contact_model_tickets': (c_void_p, [c_void_p]),
     'tuch_contact_model_tree_mask_bits': (c_void_p, [c_void_p]),
     'tuch_contact_model_info': (c_int, [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_int),
                                         POINTER(c_int), POINTER(c_int)]),
@@ -102,11 +101,8 @@ _SIGNATURES = {
     'tuch_contact_model_tree_order': (c_int, [c_void_p, c_void_p, c_void_p]),
     'tuch_v2v_model_workspace_bytes': (c_size_t, [c_void_p, c_int]),
     'tuch_v2v_hint_bytes': (c_size_t, [c_void_p, c_int]),
-    'tuch_v2v_min_model': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    'tuch_v2v_min_model_shared': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int,
-                                          c_void_p]),
-    'tuch_v2v_min_model_shared_zero': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int,
-                                               c_void_p, c_size_t, c_void_p]),
+    'tuch_v2v_min_model': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int,
+                                   c_void_p, c_size_t, c_void_p]),
     'tuch_exterior_workspace_bytes': (c_size_t, [c_void_p, c_int]),
     'tuch_exterior_flags': (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_size_t, c_void_p]),
@@ -123,31 +119,18 @@ _SIGNATURES = {
     'tuch_smpl_model_info': (c_int, [c_void_p, POINTER(c_int)]),
     'tuch_smpl_forward_workspace_bytes': (c_size_t, [c_void_p, c_int]),
     'tuch_smpl_backward_workspace_bytes': (c_size_t, [c_void_p, c_int]),
-    'tuch_smpl_forward': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
-                                  c_size_t, c_void_p]),
-    'tuch_smpl_backward': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                   c_void_p, c_void_p, c_size_t, c_void_p]),
     'tuch_smplify_stage2_fused_scratch_floats': (c_size_t, [c_int]),
-    'tuch_smplify_stage2_fused': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p,
-                                           c_void_p, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+    'tuch_smplify_stage2_fused': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p,
+                                           c_int, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                                            c_void_p, c_void_p, c_void_p, c_void_p]),
     'tuch_set_deterministic': (None, [c_int]),
     'tuch_get_deterministic': (c_int, []),
     'tuch_region_pair_keys': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
-    'tuch_smplify_stage2_finish': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p,
-                                           c_void_p, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
-                                           c_void_p]),
-    'tuch_smplify_stage2_bwd': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float,
-                                        c_float, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
-                                        c_void_p, c_void_p, c_void_p, c_void_p]),
     'tuch_smpl_forward_split': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p,
                                         c_void_p, c_void_p, c_size_t, c_void_p]),
     'tuch_smpl_backward_split': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
-                                         c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_size_t,
-                                         c_void_p]),
-    'tuch_smpl_backward_split_add': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
-                                             c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
-                                             c_size_t, c_void_p, c_void_p]),
+                                         c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                         c_size_t, c_void_p, c_void_p]),
     'tuch_fixed_to_float': (c_int, [c_void_p, c_size_t, c_void_p, c_void_p]),
     'tuch_region_pair_min_bwd': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     'tuch_self_contact': (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_int] + [c_void_p] * 6),
@@ -174,6 +157,10 @@ def lib() -> ctypes.CDLL:
                 'libtuch_amd.so is not built (%s). Run `python -m tuch_amd._build` (needs hipcc); '
                 'there is no CPU fallback.' % LIB_PATH)
         L = ctypes.CDLL(LIB_PATH)
+        L.tuch_abi_version.restype = c_int
+        if L.tuch_abi_version() != ABI_VERSION:      # signatures differ between versions: calling on would corrupt arguments
+            raise RuntimeError('%s has ABI version %d, this binding is written for %d: rebuild it (`python -m tuch_amd._build`)'
+                               % (LIB_PATH, L.tuch_abi_version(), ABI_VERSION))
         for name, (res, args) in _SIGNATURES.items():
             fn = getattr(L, name)   # AttributeError if the ABI and the binding drift apart
             fn.restype = res

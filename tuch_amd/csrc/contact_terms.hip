@@ -177,130 +177,6 @@ __global__ __launch_bounds__(256) void contact_terms_ragged_bwd_kernel(
 }
 
 
-// ---- the tail of the SMPLify-DC stage-2 objective in two launches (tuch/smplify/losses.py:96-123) -------------------
-// Forward: one block per body adds up its contact terms (as contact_terms_fwd_kernel) and its row of region minima and
-// leaves the body's share of the objective; the block that finishes last adds the shares up in a fixed order
-//   total = sum_b [ reprojection_b + prior_b + contact_scale (interior_b + exterior_b) + r2r_scale sum_p r2r[b,p] ]
-// (objective_kernel's sum; a launch of its own for one block of additions cost 5 us of the serial tail).
-__global__ __launch_bounds__(kBlock) void stage2_finish_kernel(
-    const float* __restrict__ pts, const int32_t* __restrict__ partner, const uint8_t* __restrict__ exterior,
-    const uint8_t* __restrict__ body_valid, int N, int mode, float euclthres, const float* __restrict__ small,
-    const float* __restrict__ r2r, int P, float contact_scale, float r2r_scale, float* __restrict__ share,
-    int* __restrict__ ticket, float* __restrict__ terms, float* __restrict__ out)
-{
-    __shared__ float smem[kBlock / 64];
-    __shared__ bool last;
-    const int b = blockIdx.x;
-    float in_sum = 0.0f, ex_sum = 0.0f, r_sum = 0.0f;
-    if (!body_valid || body_valid[b]) {
-        const float* pb = pts + (size_t)b * N * 3;
-        // eight points per thread and pass (one pass at SMPL size): their partners first, then both endpoints of all of
-        // them -- two rounds of loads per pass instead of two per point (the sums are added in point order all the same)
-        constexpr int kPer = 8;
-        for (int i0 = threadIdx.x; i0 < N; i0 += kBlock * kPer) {
-            int pr[kPer];
-            uint8_t ex[kPer];
-#pragma unroll
-            for (int u = 0; u < kPer; ++u) {
-                const int i = min(i0 + u * kBlock, N - 1);
-                pr[u] = partner[(size_t)b * N + i];
-                ex[u] = exterior[(size_t)b * N + i];
-            }
-            float xi[kPer][3], xp[kPer][3];
-#pragma unroll
-            for (int u = 0; u < kPer; ++u) {
-                const int i = min(i0 + u * kBlock, N - 1);
-#pragma unroll
-                for (int c = 0; c < 3; ++c) { xi[u][c] = pb[3 * i + c]; xp[u][c] = pb[3 * pr[u] + c]; }
-            }
-#pragma unroll
-            for (int u = 0; u < kPer; ++u) {
-                if (i0 + u * kBlock >= N) break;
-                const float dx = xi[u][0] - xp[u][0], dy = xi[u][1] - xp[u][1], dz = xi[u][2] - xp[u][2];
-                const float d = __builtin_sqrtf(dx * dx + dy * dy + dz * dz);
-                const bool ext = ex[u] != 0;
-                const Term t = contact_term(d, ext, mode, euclthres);
-                if (ext) ex_sum += t.value; else in_sum += t.value;
-            }
-        }
-    }
-    if (r2r)
-        for (int p = threadIdx.x; p < P; p += kBlock) r_sum += r2r[(size_t)b * P + p];
-    const float a = block_sum(in_sum, smem);
-    const float c = block_sum(ex_sum, smem);
-    const float r = block_sum(r_sum, smem);
-    if (threadIdx.x == 0) {
-        if (terms) { terms[2 * b] = a; terms[2 * b + 1] = c; }
-        const float mine = (small[2 * b] + small[2 * b + 1]) + contact_scale * (a + c) + r2r_scale * r;
-        __hip_atomic_store(share + b, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1;
-    }
-    __syncthreads();
-    if (!last) return;
-    float acc = 0.0f;
-    for (int i = threadIdx.x; i < (int)gridDim.x; i += kBlock)
-        acc += __hip_atomic_load(share + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const float total = block_sum(acc, smem);
-    if (threadIdx.x == 0) {
-        out[0] = total;
-        __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // ready for the next call
-    }
-}
-
-// Backward: the upstream scalar g times the objective's constants, straight into the vertex gradient (pre-zeroed):
-// contact terms (contact_terms_bwd_kernel with the weight g contact_scale [body valid]) in the vertex blocks; the last
-// block of every body scatters the region minima (region_pair_min_bwd_kernel with weight g r2r_scale) and scales the
-// unit gradients small_terms_kernel left for the joints, the camera and the pose.  Three launches before.
-__global__ __launch_bounds__(256) void stage2_bwd_kernel(
-    const float* __restrict__ gout, const uint8_t* __restrict__ body_valid, const float* __restrict__ pts,
-    const int32_t* __restrict__ partner, const uint8_t* __restrict__ exterior, int N, int mode, float euclthres,
-    float contact_scale, const int32_t* __restrict__ ij, int P, float r2r_scale, const float* __restrict__ gj,
-    const float* __restrict__ gc, const float* __restrict__ gp, int NJ, float* __restrict__ grad,
-    float* __restrict__ gj_out, float* __restrict__ gc_out, float* __restrict__ gp_out)
-{
-    const int b = blockIdx.y;
-    const float g = gout[0];
-    const float* pb = pts + (size_t)b * N * 3;
-    float* gb = grad + (size_t)b * N * 3;
-    if (blockIdx.x == gridDim.x - 1) {
-        const float gr = r2r_scale * g;
-        if (ij && gr != 0.0f)
-            for (int p = threadIdx.x; p < P; p += 256) {
-                const size_t o = (size_t)b * P + p;
-                const int i = ij[2 * o], j = ij[2 * o + 1];
-                if (i < 0 || j < 0) continue;
-                for (int c = 0; c < 3; ++c) {
-                    const float d = 2.0f * gr * (pb[3 * i + c] - pb[3 * j + c]);
-                    atomicAdd(gb + 3 * i + c, d);
-                    atomicAdd(gb + 3 * j + c, -d);
-                }
-            }
-        for (int i = threadIdx.x; i < NJ * 3; i += 256) gj_out[(size_t)b * NJ * 3 + i] = g * gj[(size_t)b * NJ * 3 + i];
-        if (threadIdx.x < 3) gc_out[b * 3 + threadIdx.x] = g * gc[b * 3 + threadIdx.x];
-        if (gp && threadIdx.x < 69) gp_out[b * 69 + threadIdx.x] = g * gp[b * 69 + threadIdx.x];
-        return;
-    }
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= N) return;
-    // the point's own data is requested before the upstream gradient and the body's flag are looked at (one round of
-    // loads less on a kernel that is nothing but its load latencies)
-    const bool ext = exterior[(size_t)b * N + i] != 0;
-    const int p = partner[(size_t)b * N + i];
-    const float xi = pb[3 * i], yi = pb[3 * i + 1], zi = pb[3 * i + 2];
-    const float gs = (!body_valid || body_valid[b]) ? contact_scale * g : 0.0f;
-    if (gs == 0.0f) return;
-    const float dx = xi - pb[3 * p], dy = yi - pb[3 * p + 1], dz = zi - pb[3 * p + 2];
-    const float d = __builtin_sqrtf(dx * dx + dy * dy + dz * dz);
-    if (!(d > 0.0f)) return;
-    const Term t = contact_term(d, ext, mode, euclthres);
-    if (t.dd == 0.0f) return;
-    const float c = gs * t.dd / d;
-    float* gi = gb + 3 * (size_t)i;
-    float* gq = gb + 3 * (size_t)p;
-    atomicAdd(gi + 0, c * dx); atomicAdd(gi + 1, c * dy); atomicAdd(gi + 2, c * dz);
-    atomicAdd(gq + 0, -c * dx); atomicAdd(gq + 1, -c * dy); atomicAdd(gq + 2, -c * dz);
-}
-
 #ifdef TUCH_STAGE2_CLOCKS
 // diagnostic build only (tools/diag/stage2_clocks.py): s_memrealtime stamps (100 MHz) of block (0, 0) and of the block that
 // arrives last: [0] start, [1] loads done, [2] atomics issued, [3] block sums, [4] ticket taken; last block: [5] start of the
@@ -317,35 +193,32 @@ extern "C" int tuch_debug_stage2_clocks(unsigned long long* out)
 #define STAGE2_CLOCK_LAST(i) do { } while (0)
 #endif
 
-// Forward AND the unit-seed backward of the tail in ONE launch (stage2_finish + stage2_bwd with g = 1): the objective is
-// the root of the fit's autograd graph, its upstream gradient is the constant 1 (loss.backward()), so the vertex
-// gradient can be written while the sums are formed -- one kernel and one dependent launch less in the serial tail of
-// every iteration.  A caller whose upstream gradient is not 1 scales the outputs (ops._Stage2Tail.backward).
-// grid (kFusedSplits, B) x 256 threads: a body's points are shared out over kFusedSplits blocks (the scatter's atomics
-// want more than B workgroups); partial sums per (body, split), added up in a fixed order by the block that arrives last.
+// ---- the tail of the SMPLify-DC stage-2 objective and its vertex gradient in one launch (tuch/smplify/losses.py:96-123) ----
+//   total = sum_b [ reprojection_b + prior_b + contact_scale (interior_b + exterior_b) + r2r_scale sum_p d2[b,p] ]
+// reprojection_b, prior_b: small[b] (small_terms_kernel's output); interior_b, exterior_b: the body's contact sums as
+// contact_terms_fwd_kernel forms them (0 for a body that is not valid); d2[b,p]: the minimum of region pair p, decoded
+// from the raw keys of tuch_region_pair_keys with the model's region tables (a key of 0: no admissible pair, no term).
+// The objective is the root of the fit's autograd graph, its upstream gradient is the constant 1 (loss.backward()), so
+// the vertex gradient is scattered while the sums are formed: into grad (float atomics) or grad_fixed (deterministic
+// mode: 64-bit fixed-point accumulators, common.h), both pre-zeroed; neither: the value alone.  A caller whose upstream
+// gradient is not 1 scales the result (ops._Stage2Tail.backward).
+// grid (kFusedSplits, B) x 256 threads.  Every block: one share of a body's points (the scatter's atomics want more than
+// B workgroups) -- their contact terms, and the gradient of each to the point and its partner; split 0 of a body also
+// decodes the body's region pairs and scatters their gradient; then the block's three sums (interior, exterior, regions)
+// go to share[b][split] and the block takes a ticket.  The block that takes the last ticket adds the shares up -- bodies
+// in order, a body's splits in order: the total does not depend on which block that was or on whether the scatter ran --
+// writes out[0] and leaves the ticket zero for the next call.
 constexpr int kFusedSplits = 8;
 constexpr int kFusedBlock = 256;
-
-__device__ __forceinline__ float block_sum_256(float v, float* smem)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (lane == 0) smem[wave] = v;
-    __syncthreads();
-    const float r = smem[0] + smem[1] + smem[2] + smem[3];
-    __syncthreads();
-    return r;   // same value in every thread
-}
 
 __global__ __launch_bounds__(kFusedBlock) void stage2_fused_kernel(
     const float* __restrict__ pts, const int32_t* __restrict__ partner, const uint8_t* __restrict__ exterior,
     const uint8_t* __restrict__ body_valid, int N, int mode, float euclthres, const float* __restrict__ small,
-    const float* __restrict__ r2r, const int32_t* __restrict__ ij, int P, float contact_scale, float r2r_scale,
+    int P, float contact_scale, float r2r_scale,
     float* __restrict__ share,        // [B][kFusedSplits][3] scratch
-    int* __restrict__ ticket, float* __restrict__ terms, float* __restrict__ out,
-    float* __restrict__ grad,         // [B,N,3] pre-zeroed, or nullptr (value only)
-    // instead of (r2r, ij): the raw keys of tuch_region_pair_keys and the model's region tables
+    int* __restrict__ ticket, float* __restrict__ out,
+    float* __restrict__ grad,         // [B,N,3] pre-zeroed, or nullptr
+    // the raw keys of tuch_region_pair_keys [B,P] and the model's region tables, or nullptr (no region term)
     const unsigned long long* __restrict__ pair_keys, const int32_t* __restrict__ region_off,
     const int32_t* __restrict__ region_vidx, const int32_t* __restrict__ pairs,
     long long* __restrict__ grad_fixed)     // deterministic mode: [B,N,3] 64-bit fixed-point accumulators (zeroed) instead of grad
@@ -370,25 +243,19 @@ __global__ __launch_bounds__(kFusedBlock) void stage2_fused_kernel(
     // and which go to memory does not change the result; without it the mode paid the queueing again, +10 us per step)
     __shared__ int p_tag[kPartnerSlots];
     __shared__ long long p_acc[kPartnerSlots][3];       // float mode: the low words hold the float sums
-    const bool in_lds = want;
-    if (in_lds) {
+    if (want) {
         for (int k = threadIdx.x; k < kPartnerSlots; k += kFusedBlock) { p_tag[k] = -1; p_acc[k][0] = p_acc[k][1] = p_acc[k][2] = 0; }
         __syncthreads();
     }
     auto add3_partner = [&](int at, float x, float y, float z) {
-        if (in_lds) {
-            const int slot = at & (kPartnerSlots - 1);
-            const int old = atomicCAS(&p_tag[slot], -1, at);
-            if (old == -1 || old == at) {
-                if (fb) { fixed_add(&p_acc[slot][0], x); fixed_add(&p_acc[slot][1], y); fixed_add(&p_acc[slot][2], z); }
-                else {
-                    atomicAdd(reinterpret_cast<float*>(&p_acc[slot][0]), x); atomicAdd(reinterpret_cast<float*>(&p_acc[slot][1]), y);
-                    atomicAdd(reinterpret_cast<float*>(&p_acc[slot][2]), z);
-                }
-                return;
-            }
+        const int slot = at & (kPartnerSlots - 1);
+        const int old = atomicCAS(&p_tag[slot], -1, at);
+        if (old != -1 && old != at) { add3(at, x, y, z); return; }
+        if (fb) { fixed_add(&p_acc[slot][0], x); fixed_add(&p_acc[slot][1], y); fixed_add(&p_acc[slot][2], z); }
+        else {
+            atomicAdd(reinterpret_cast<float*>(&p_acc[slot][0]), x); atomicAdd(reinterpret_cast<float*>(&p_acc[slot][1]), y);
+            atomicAdd(reinterpret_cast<float*>(&p_acc[slot][2]), z);
         }
-        add3(at, x, y, z);
     };
     STAGE2_CLOCK(0);
     float in_sum = 0.0f, ex_sum = 0.0f, r_sum = 0.0f;
@@ -434,7 +301,7 @@ __global__ __launch_bounds__(kFusedBlock) void stage2_fused_kernel(
         }
     }
     STAGE2_CLOCK(2);
-    if (in_lds) {
+    if (want) {
         __syncthreads();
         for (int k = threadIdx.x; k < kPartnerSlots; k += kFusedBlock) {
             if (p_tag[k] < 0) continue;
@@ -446,33 +313,22 @@ __global__ __launch_bounds__(kFusedBlock) void stage2_fused_kernel(
                      *reinterpret_cast<float*>(&p_acc[k][2]));
         }
     }
-    if (s == 0 && (r2r || pair_keys)) {
+    if (s == 0 && pair_keys) {
         for (int p = threadIdx.x; p < P; p += kFusedBlock) {
-            const size_t o = (size_t)b * P + p;
-            int i = -1, j = -1;
-            if (pair_keys) {
-                const unsigned long long inv = pair_keys[o];
-                if (inv != 0ull) {                       // (d2 bits << 32 | flat index), complemented
-                    const unsigned long long key = ~inv;
-                    const int r1 = pairs[2 * p], r2 = pairs[2 * p + 1];
-                    const int n2 = region_off[r2 + 1] - region_off[r2];
-                    const int idx = (int)(unsigned int)key;
-                    r_sum += __uint_as_float((unsigned int)(key >> 32));
-                    i = region_vidx[region_off[r1] + idx / n2];
-                    j = region_vidx[region_off[r2] + idx % n2];
-                }
-            } else {
-                r_sum += r2r[o];
-                if (ij) { i = ij[2 * o]; j = ij[2 * o + 1]; }
-            }
+            const unsigned long long inv = pair_keys[(size_t)b * P + p];
+            if (inv == 0ull) continue;
+            const unsigned long long key = ~inv;         // (d2 bits << 32 | flat index), complemented
+            const int r1 = pairs[2 * p], r2 = pairs[2 * p + 1];
+            const int n2 = region_off[r2 + 1] - region_off[r2];
+            const int idx = (int)(unsigned int)key;
+            r_sum += __uint_as_float((unsigned int)(key >> 32));
             if (want && r2r_scale != 0.0f) {
-                if (i >= 0 && j >= 0) {
-                    const float k2 = 2.0f * r2r_scale;
-                    const float ex2 = k2 * (pb[3 * i] - pb[3 * j]), ey2 = k2 * (pb[3 * i + 1] - pb[3 * j + 1]),
-                                ez2 = k2 * (pb[3 * i + 2] - pb[3 * j + 2]);
-                    add3(i, ex2, ey2, ez2);
-                    add3(j, -ex2, -ey2, -ez2);
-                }
+                const int i = region_vidx[region_off[r1] + idx / n2], j = region_vidx[region_off[r2] + idx % n2];
+                const float k2 = 2.0f * r2r_scale;
+                const float ex2 = k2 * (pb[3 * i] - pb[3 * j]), ey2 = k2 * (pb[3 * i + 1] - pb[3 * j + 1]),
+                            ez2 = k2 * (pb[3 * i + 2] - pb[3 * j + 2]);
+                add3(i, ex2, ey2, ez2);
+                add3(j, -ex2, -ey2, -ez2);
             }
         }
     }
@@ -514,7 +370,6 @@ __global__ __launch_bounds__(kFusedBlock) void stage2_fused_kernel(
             ea += __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             ra += __hip_atomic_load(q + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        if (terms) { terms[2 * bb] = ia; terms[2 * bb + 1] = ea; }
         acc += (small[2 * bb] + small[2 * bb + 1]) + contact_scale * (ia + ea) + r2r_scale * ra;
     }
     // fixed-order sum over the block (B <= 256: one body per thread; more: a thread's bodies in order first)
@@ -542,39 +397,31 @@ __global__ __launch_bounds__(256) void fixed_to_float_kernel(const long long* __
 
 extern "C" size_t tuch_smplify_stage2_fused_scratch_floats(int B) { return (size_t)(B > 0 ? B : 0) * kFusedSplits * 3; }
 
-// tuch_smplify_stage2_finish and, when grad_points is given, tuch_smplify_stage2_bwd for a unit upstream gradient, in one
-// launch.  share: tuch_smplify_stage2_fused_scratch_floats(B) floats; ticket: one int, zero before the call (left zero);
-// grad_points [B,N,3] pre-zeroed or NULL; ij [B,P,2] from tuch_region_pair_min (needed for the gradient of the region
-// term) or NULL.  The unit gradients of the small terms are tuch_smplify_small_terms' own outputs.
+// out[0] = the total of stage2_fused_kernel's head comment, and its vertex gradient for a unit upstream gradient.
+// share: tuch_smplify_stage2_fused_scratch_floats(B) floats; ticket: one int, zero before the call (left zero); P > 0:
+// pair_keys [B,P] from tuch_region_pair_keys of `model`.  At most one of grad_points [B,N,3] (pre-zeroed floats, float
+// atomics) and grad_fixed_zeroed (B*N*3 zeroed 64-bit words: what deterministic mode -- tuch_deterministic() -- scatters
+// into; they are the result, read by tuch_smpl_backward_split's g_verts_fixed or converted by tuch_fixed_to_float);
+// neither: the value alone.  The unit gradients of the small terms are tuch_smplify_small_terms' own outputs.
 extern "C" int tuch_smplify_stage2_fused(const float* points, const int32_t* partner, const uint8_t* exterior,
                                          const uint8_t* body_valid, int B, int N, int mode, float euclthres,
-                                         const float* small_terms, const float* r2r, const int32_t* ij, int P,
-                                         float contact_scale, float r2r_scale, float* share, int* ticket, float* terms,
-                                         float* out, float* grad_points, const tuch_contact_model* model,
-                                         const void* pair_keys, void* grad_fixed_zeroed, void* stream)
+                                         const float* small_terms, int P, float contact_scale, float r2r_scale,
+                                         float* share, int* ticket, float* out, float* grad_points,
+                                         const tuch_contact_model* model, const void* pair_keys, void* grad_fixed_zeroed,
+                                         void* stream)
 {
     TUCH_REQUIRE(points && partner && exterior && small_terms && share && ticket && out,
                  "tuch_smplify_stage2_fused: null pointer");
     TUCH_REQUIRE(B > 0 && B <= 65535 && N > 0 && P >= 0 && (mode == 0 || mode == 1), "tuch_smplify_stage2_fused: bad arguments");
-    TUCH_REQUIRE(!pair_keys || (model && model->num_pairs == P && P > 0),
-                 "tuch_smplify_stage2_fused: pair keys need the model they were computed with (P = its number of pairs)");
+    TUCH_REQUIRE(pair_keys ? (model && model->num_pairs == P && P > 0) : P == 0,
+                 "tuch_smplify_stage2_fused: P pair keys need the model they were computed with (P = its number of pairs)");
+    TUCH_REQUIRE(!(grad_points && grad_fixed_zeroed), "tuch_smplify_stage2_fused: float and fixed-point gradient, give one");
     const bool raw = pair_keys != nullptr;
-    // deterministic mode (tuch_deterministic(): TUCH_DETERMINISTIC=1 / tuch_set_deterministic): the caller passes B*N*3
-    // zeroed 64-bit words; the scatter accumulates fixed-point integers there, a second launch converts to grad_points
-    // grad_points NULL with grad_fixed_zeroed given: the accumulators are the result (no conversion launch -- the consumer
-    // reads them: tuch_smpl_backward_split_add's g_verts_fixed; tuch_fixed_to_float converts on demand)
-    const bool fixed = grad_fixed_zeroed != nullptr;
     hipLaunchKernelGGL(stage2_fused_kernel, dim3(kFusedSplits, B), dim3(kFusedBlock), 0, (hipStream_t)stream, points, partner,
-                       exterior, body_valid, N, mode, euclthres, small_terms, (P > 0 && !raw ? r2r : (const float*)nullptr),
-                       (P > 0 && !raw ? ij : (const int32_t*)nullptr), P, contact_scale, r2r_scale, share, ticket, terms, out,
-                       fixed ? (float*)nullptr : grad_points, (const unsigned long long*)pair_keys,
+                       exterior, body_valid, N, mode, euclthres, small_terms, P, contact_scale, r2r_scale, share, ticket, out,
+                       grad_points, (const unsigned long long*)pair_keys,
                        raw ? (const int32_t*)model->region_off : nullptr, raw ? (const int32_t*)model->region_vidx : nullptr,
-                       raw ? (const int32_t*)model->pairs : nullptr, fixed ? (long long*)grad_fixed_zeroed : (long long*)nullptr);
-    if (fixed && grad_points) {
-        const size_t n = (size_t)B * N * 3;
-        hipLaunchKernelGGL(fixed_to_float_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                           (const long long*)grad_fixed_zeroed, grad_points, n);
-    }
+                       raw ? (const int32_t*)model->pairs : nullptr, (long long*)grad_fixed_zeroed);
     return tuch_check_launch("tuch_smplify_stage2_fused");
 }
 
@@ -708,39 +555,4 @@ extern "C" int tuch_contact_terms_ragged_bwd(const float* points, const int32_t*
     hipLaunchKernelGGL(contact_terms_ragged_bwd_kernel, dim3(ceil_div(N, 256)), dim3(256), 0, (hipStream_t)stream,
                        points, partner, exterior, body_of_point, grad_scale, N, mode, euclthres, grad_points);
     return tuch_check_launch("tuch_contact_terms_ragged_bwd");
-}
-
-// The stage-2 objective behind the inside test and the nearest-vertex search, and its backward pass, as one launch
-// each (see stage2_finish_kernel / stage2_bwd_kernel).  share: [B] floats of scratch; ticket: one int, zero before the
-// first call and left zero by every call (one per stream in flight); terms: [B,2] or NULL.
-extern "C" int tuch_smplify_stage2_finish(const float* points, const int32_t* partner, const uint8_t* exterior,
-                                          const uint8_t* body_valid, int B, int N, int mode, float euclthres,
-                                          const float* small_terms, const float* r2r, int P, float contact_scale,
-                                          float r2r_scale, float* share, int* ticket, float* terms, float* out,
-                                          void* stream)
-{
-    TUCH_REQUIRE(points && partner && exterior && small_terms && share && ticket && out,
-                 "tuch_smplify_stage2_finish: null pointer");
-    TUCH_REQUIRE(B > 0 && N > 0 && P >= 0 && (mode == 0 || mode == 1), "tuch_smplify_stage2_finish: bad arguments");
-    hipLaunchKernelGGL(stage2_finish_kernel, dim3(B), dim3(kBlock), 0, (hipStream_t)stream, points, partner, exterior,
-                       body_valid, N, mode, euclthres, small_terms, (P > 0 ? r2r : (const float*)nullptr), P,
-                       contact_scale, r2r_scale, share, ticket, terms, out);
-    return tuch_check_launch("tuch_smplify_stage2_finish");
-}
-
-extern "C" int tuch_smplify_stage2_bwd(const float* grad_out, const uint8_t* body_valid, const float* points,
-                                       const int32_t* partner, const uint8_t* exterior, int B, int N, int mode,
-                                       float euclthres, float contact_scale, const int32_t* ij, int P, float r2r_scale,
-                                       const float* gj, const float* gc, const float* gp, int NJ, float* grad_points,
-                                       float* gj_out, float* gc_out, float* gp_out, void* stream)
-{
-    TUCH_REQUIRE(grad_out && points && partner && exterior && gj && gc && grad_points && gj_out && gc_out &&
-                 (!gp || gp_out), "tuch_smplify_stage2_bwd: null pointer");
-    TUCH_REQUIRE(B > 0 && B <= 65535 && N > 0 && NJ > 0 && P >= 0 && (mode == 0 || mode == 1),
-                 "tuch_smplify_stage2_bwd: bad arguments");
-    hipLaunchKernelGGL(stage2_bwd_kernel, dim3(ceil_div(N, 256) + 1, B), dim3(256), 0, (hipStream_t)stream, grad_out,
-                       body_valid, points, partner, exterior, N, mode, euclthres, contact_scale,
-                       (P > 0 ? ij : (const int32_t*)nullptr), P, r2r_scale, gj, gc, gp, NJ, grad_points, gj_out, gc_out,
-                       gp_out);
-    return tuch_check_launch("tuch_smplify_stage2_bwd");
 }

@@ -118,7 +118,6 @@ struct tuch_contact_model {
     tuch_options opt;
     int V, F;
     int32_t* faces;            // [F,3]
-    int32_t* tickets;          // [8] arrival counters of "the last block adds up" kernels, zero between calls
     int32_t* canary_hits;      // [1] guard words found changed (option canary, workspace.h)
     uint64_t* mask_bits;       // [W][V] or nullptr
     // triangle strips over `faces` (built at create): stream of vertex ids with a per-element

@@ -60,10 +60,9 @@ bool mask_is_symmetric(const uint8_t* mask, int V)
 
 void build_mesh_tables(tuch_contact_model* m, const int32_t* faces)
 {
-    const int32_t zeros[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    const int32_t zero = 0;
     m->tables.put(&m->faces, faces, (size_t)m->F * 3);
-    m->tables.put(&m->tickets, zeros, 8);
-    m->tables.put(&m->canary_hits, zeros, 1);
+    m->tables.put(&m->canary_hits, &zero, 1);
 }
 
 void build_strip_tables(tuch_contact_model* m, const int32_t* faces)
@@ -175,7 +174,7 @@ void build_tree_mask_tables(tuch_contact_model* m, const tuch_cluster_tree& t, c
     // packed-row form: the leaves' rows in groups of four
     std::vector<int32_t> group(L + 1, 0);
     for (int k = 0; k < L; ++k) group[k + 1] = group[k] + (t.leaf_rows(k).count + 3) / 4;
-    // for the leaf-major search (v2v.hip: the `pairs` condition of tuch_v2v_min_model_shared_zero): a leaf's rows fit one
+    // for the leaf-major search (v2v.hip: the `pairs` condition of tuch_v2v_min_model): a leaf's rows fit one
     // 64-bit window of a column's mask row, and that row stands for the column's own admissible rows only if the mask is
     // symmetric
     for (int k = 0; k < L; ++k) m->tree_leaf_rows_max = std::max(m->tree_leaf_rows_max, t.leaf_rows(k).count);
@@ -559,8 +558,6 @@ extern "C" int tuch_contact_model_get_option(const tuch_contact_model* m, const 
 
 extern "C" const uint64_t* tuch_contact_model_mask_bits(const tuch_contact_model* m) { return m ? m->mask_bits : nullptr; }
 extern "C" const uint64_t* tuch_contact_model_tree_mask_bits(const tuch_contact_model* m) { return m ? m->tree_mask_bits : nullptr; }
-extern "C" int32_t* tuch_contact_model_tickets(const tuch_contact_model* m) { return m ? m->tickets : nullptr; }
-extern "C" const int32_t* tuch_contact_model_faces(const tuch_contact_model* m) { return m ? m->faces : nullptr; }
 
 extern "C" int tuch_contact_model_tree_order(const tuch_contact_model* m, int32_t* qperm_host, int32_t* face_leaf_host)
 {

@@ -1129,21 +1129,22 @@ extern "C" size_t tuch_smpl_backward_workspace_bytes(const tuch_smpl_model* m, i
 }
 
 // global_orient: [B,3] axis-angle (pose2rot) or [B,1,3,3]; body_pose: [B,69] or [B,23,3,3] -- the two tensors of
-// SMPL.forward (models/smpl.py:44-47), with row strides in floats so that views of one [B,72] pose work as well.
+// SMPL.forward (models/smpl.py:44-47), with row strides in floats.  One concatenated pose [B,72] (w = 3) or [B,24,3,3]
+// (w = 9) is passed as global_orient = pose, body_pose = pose + w, both strides 24 w.
 // The forward workspace holds the intermediates the backward pass needs and must be kept alive until then.
 extern "C" int tuch_smpl_forward_split(const tuch_smpl_model* m, const float* betas, const float* global_orient,
                                        int global_orient_stride, const float* body_pose, int body_pose_stride,
                                        int pose2rot, int B, float* verts, float* joints, void* workspace,
                                        size_t workspace_bytes, void* stream)
 {
-    TUCH_REQUIRE(m && betas && global_orient && body_pose && verts && joints, "tuch_smpl_forward: null pointer");
-    TUCH_REQUIRE(B > 0 && B <= 65535, "tuch_smpl_forward: bad batch %d", B);
+    TUCH_REQUIRE(m && betas && global_orient && body_pose && verts && joints, "tuch_smpl_forward_split: null pointer");
+    TUCH_REQUIRE(B > 0 && B <= 65535, "tuch_smpl_forward_split: bad batch %d", B);
     const int w = pose2rot ? 3 : 9;
-    TUCH_REQUIRE(global_orient_stride >= w && body_pose_stride >= 23 * w, "tuch_smpl_forward: bad pose strides %d, %d",
+    TUCH_REQUIRE(global_orient_stride >= w && body_pose_stride >= 23 * w, "tuch_smpl_forward_split: bad pose strides %d, %d",
                  global_orient_stride, body_pose_stride);
     const FwdLayout l = fwd_layout(m, B);
     if (!workspace || workspace_bytes < l.total) {
-        tuch_set_error("tuch_smpl_forward: workspace %zu < %zu bytes", workspace_bytes, l.total);
+        tuch_set_error("tuch_smpl_forward_split: workspace %zu < %zu bytes", workspace_bytes, l.total);
         return TUCH_ERR_WORKSPACE;
     }
     char* ws = (char*)workspace;
@@ -1176,45 +1177,10 @@ extern "C" int tuch_smpl_forward_split(const tuch_smpl_model* m, const float* be
     hipLaunchKernelGGL(assemble_joints_kernel, dim3(B), dim3(256), 0, s, (const float*)world, (const float*)verts,
                        (const float*)partial, (const int32_t*)m->extra_ids, (const int32_t*)m->joint_map, m->V,
                        ceil_div(m->V, kSkinBlock), joints);
-    return tuch_check_launch("tuch_smpl_forward");
+    return tuch_check_launch("tuch_smpl_forward_split");
 }
 
-// pose: [B,72] axis-angle (pose2rot) or [B,24,3,3] rotation matrices: the concatenated form of the above.
-extern "C" int tuch_smpl_forward(const tuch_smpl_model* m, const float* betas, const float* pose, int pose2rot,
-                                 int B, float* verts, float* joints, void* workspace, size_t workspace_bytes,
-                                 void* stream)
-{
-    TUCH_REQUIRE(pose, "tuch_smpl_forward: null pointer");
-    const int w = pose2rot ? 3 : 9;
-    return tuch_smpl_forward_split(m, betas, pose, kJoints * w, pose + w, kJoints * w, pose2rot, B, verts, joints,
-                                   workspace, workspace_bytes, stream);
-}
-
-extern "C" int tuch_smpl_backward_split_add(const tuch_smpl_model* m, const float* global_orient, int global_orient_stride,
-                                            const float* body_pose, int body_pose_stride, int pose2rot, int B,
-                                            const void* fwd_workspace, const float* g_verts, const float* g_joints,
-                                            float* g_betas, float* g_global_orient, int g_global_orient_stride,
-                                            float* g_body_pose, int g_body_pose_stride, const float* g_body_pose_add,
-                                            int g_body_pose_add_stride, void* workspace, size_t workspace_bytes, void* stream,
-                                            const void* g_verts_fixed);
-
-// g_verts [B,V,3] and/or g_joints [B,49,3] (either may be NULL) -> g_betas [B,10] and
-// the pose gradient, written as the two tensors of tuch_smpl_forward_split (same shapes, strides in floats).
-extern "C" int tuch_smpl_backward_split(const tuch_smpl_model* m, const float* global_orient, int global_orient_stride,
-                                        const float* body_pose, int body_pose_stride, int pose2rot, int B,
-                                        const void* fwd_workspace, const float* g_verts, const float* g_joints,
-                                        float* g_betas, float* g_global_orient, int g_global_orient_stride,
-                                        float* g_body_pose, int g_body_pose_stride, void* workspace,
-                                        size_t workspace_bytes, void* stream)
-{
-    return tuch_smpl_backward_split_add(m, global_orient, global_orient_stride, body_pose, body_pose_stride, pose2rot, B,
-                                        fwd_workspace, g_verts, g_joints, g_betas, g_global_orient, g_global_orient_stride,
-                                        g_body_pose, g_body_pose_stride, nullptr, 0, workspace, workspace_bytes, stream, nullptr);
-}
-
-// The same with a gradient the caller already holds for body_pose (g_body_pose_add, same shape, row stride in floats; or
-// NULL): g_body_pose = this call's gradient + that one -- what autograd would otherwise do in a separate add launch when
-// body_pose feeds the body model AND another term (SMPLify-DC: the pose prior, losses.py:63).
+// The one implementation behind the two backward entries (adam all zero: no update).
 static int backward_impl(const tuch_smpl_model* m, const float* global_orient, int global_orient_stride,
                          const float* body_pose, int body_pose_stride, int pose2rot, int B,
                          const void* fwd_workspace, const float* g_verts, const float* g_joints,
@@ -1224,19 +1190,19 @@ static int backward_impl(const tuch_smpl_model* m, const float* global_orient, i
                          const void* g_verts_fixed)
 {
     TUCH_REQUIRE(m && global_orient && body_pose && fwd_workspace && g_betas && g_global_orient && g_body_pose,
-                 "tuch_smpl_backward: null pointer");
-    TUCH_REQUIRE(B > 0 && B <= 65535, "tuch_smpl_backward: bad batch %d", B);
+                 "tuch_smpl_backward_split: null pointer");
+    TUCH_REQUIRE(B > 0 && B <= 65535, "tuch_smpl_backward_split: bad batch %d", B);
     const int w = pose2rot ? 3 : 9;
     TUCH_REQUIRE(global_orient_stride >= w && body_pose_stride >= 23 * w && g_global_orient_stride >= w &&
-                 g_body_pose_stride >= 23 * w, "tuch_smpl_backward: bad pose strides");
+                 g_body_pose_stride >= 23 * w, "tuch_smpl_backward_split: bad pose strides");
     const PoseRef pose{global_orient, body_pose, global_orient_stride, body_pose_stride};
-    TUCH_REQUIRE(!g_body_pose_add || g_body_pose_add_stride >= 23 * w, "tuch_smpl_backward: bad stride of the added gradient");
+    TUCH_REQUIRE(!g_body_pose_add || g_body_pose_add_stride >= 23 * w, "tuch_smpl_backward_split: bad stride of the added gradient");
     const PoseGrad g_pose{g_global_orient, g_body_pose, g_global_orient_stride, g_body_pose_stride, g_body_pose_add,
                           g_body_pose_add_stride};
     const FwdLayout f = fwd_layout(m, B);
     const BwdLayout l = bwd_layout(m, B);
     if (!workspace || workspace_bytes < l.total) {
-        tuch_set_error("tuch_smpl_backward: workspace %zu < %zu bytes", workspace_bytes, l.total);
+        tuch_set_error("tuch_smpl_backward_split: workspace %zu < %zu bytes", workspace_bytes, l.total);
         return TUCH_ERR_WORKSPACE;
     }
     const char* fw = (const char*)fwd_workspace;
@@ -1258,16 +1224,22 @@ static int backward_impl(const tuch_smpl_model* m, const float* global_orient, i
     hipLaunchKernelGGL(pose_bwd_kernel, dim3(B), dim3(256), 0, s, (const float*)gA_part, l.skin_blocks,
                        (const float*)feat_part, l.feat_chunks, l.bpad, g_joints, (const int32_t*)m->joint_map, R, J, world, pose,
                        pose2rot, (const float*)m->J_shapedirs, (const int32_t*)m->parents, m->max_depth, g_pose, g_betas, adam);
-    return tuch_check_launch("tuch_smpl_backward");
+    return tuch_check_launch("tuch_smpl_backward_split");
 }
 
-extern "C" int tuch_smpl_backward_split_add(const tuch_smpl_model* m, const float* global_orient, int global_orient_stride,
-                                            const float* body_pose, int body_pose_stride, int pose2rot, int B,
-                                            const void* fwd_workspace, const float* g_verts, const float* g_joints,
-                                            float* g_betas, float* g_global_orient, int g_global_orient_stride,
-                                            float* g_body_pose, int g_body_pose_stride, const float* g_body_pose_add,
-                                            int g_body_pose_add_stride, void* workspace, size_t workspace_bytes, void* stream,
-                                            const void* g_verts_fixed)
+// g_verts [B,V,3] and/or g_joints [B,49,3] (either may be NULL) -> g_betas [B,10] and the pose gradient, written as the
+// two tensors of tuch_smpl_forward_split (same shapes, strides in floats).  g_body_pose_add (same shape as g_body_pose, row
+// stride in floats; or NULL): a gradient the caller already holds for body_pose, g_body_pose = this call's gradient +
+// that one -- what autograd would otherwise do in a separate add launch when body_pose feeds the body model AND another
+// term (SMPLify-DC: the pose prior, losses.py:63).  g_verts_fixed ([B,V,3] 64-bit fixed-point sums, or NULL) is added
+// to g_verts where the skinning adjoint reads it.
+extern "C" int tuch_smpl_backward_split(const tuch_smpl_model* m, const float* global_orient, int global_orient_stride,
+                                        const float* body_pose, int body_pose_stride, int pose2rot, int B,
+                                        const void* fwd_workspace, const float* g_verts, const float* g_joints,
+                                        float* g_betas, float* g_global_orient, int g_global_orient_stride,
+                                        float* g_body_pose, int g_body_pose_stride, const float* g_body_pose_add,
+                                        int g_body_pose_add_stride, void* workspace, size_t workspace_bytes, void* stream,
+                                        const void* g_verts_fixed)
 {
     PoseAdam none;
     memset(&none, 0, sizeof(none));
@@ -1276,7 +1248,7 @@ extern "C" int tuch_smpl_backward_split_add(const tuch_smpl_model* m, const floa
                          g_body_pose_add, g_body_pose_add_stride, none, workspace, workspace_bytes, stream, g_verts_fixed);
 }
 
-// tuch_smpl_backward_split_add + torch.optim.Adam's update (tuch_adam_step's arithmetic) of the two pose tensors THEMSELVES,
+// tuch_smpl_backward_split + torch.optim.Adam's update (tuch_adam_step's arithmetic) of the two pose tensors THEMSELVES,
 // applied by the last backward kernel to the rows whose gradient it has just written (axis-angle poses only): for a fit
 // whose optimiser holds exactly [global_orient, body_pose] and whose whole gradient arrives through this call (SMPLify-DC
 // stage 2, smplifydc.py:149-183: the body model + the pose prior via g_body_pose_add).  param_*: the tensors the optimiser
@@ -1304,19 +1276,6 @@ extern "C" int tuch_smpl_backward_split_adam(const tuch_smpl_model* m, const flo
     return backward_impl(m, global_orient, global_orient_stride, body_pose, body_pose_stride, 1, B, fwd_workspace,
                          g_verts, g_joints, g_betas, g_global_orient, g_global_orient_stride, g_body_pose, g_body_pose_stride,
                          g_body_pose_add, g_body_pose_add_stride, adam, workspace, workspace_bytes, stream, g_verts_fixed);
-}
-
-// pose / g_pose: [B,72] or [B,24,3,3], the concatenated form.
-extern "C" int tuch_smpl_backward(const tuch_smpl_model* m, const float* pose, int pose2rot, int B,
-                                  const void* fwd_workspace, const float* g_verts, const float* g_joints,
-                                  float* g_betas, float* g_pose, void* workspace, size_t workspace_bytes,
-                                  void* stream)
-{
-    TUCH_REQUIRE(pose && g_pose, "tuch_smpl_backward: null pointer");
-    const int w = pose2rot ? 3 : 9;
-    return tuch_smpl_backward_split(m, pose, kJoints * w, pose + w, kJoints * w, pose2rot, B, fwd_workspace, g_verts,
-                                    g_joints, g_betas, g_pose, kJoints * w, g_pose + w, kJoints * w, workspace,
-                                    workspace_bytes, stream);
 }
 
 extern "C" int tuch_smpl_model_info(const tuch_smpl_model* m, int* V)

@@ -1439,33 +1439,16 @@ extern "C" size_t tuch_v2v_hint_bytes(const tuch_contact_model* m, int B)
     return (size_t)B * m->tree_qblocks * 2 * kTreeCols * sizeof(int32_t);
 }
 
-extern "C" int tuch_v2v_min_model_shared_zero(const tuch_contact_model* m, const float* verts, int B, float* min_d2,
-                                              int32_t* argmin, void* hint_inout, void* workspace, size_t workspace_bytes,
-                                              int leave_room, void* zero, size_t zero_bytes, void* stream);
-extern "C" int tuch_v2v_min_model_shared(const tuch_contact_model* m, const float* verts, int B, float* min_d2,
-                                         int32_t* argmin, void* hint_inout, void* workspace, size_t workspace_bytes,
-                                         int leave_room, void* stream)
-{
-    return tuch_v2v_min_model_shared_zero(m, verts, B, min_d2, argmin, hint_inout, workspace, workspace_bytes, leave_room, nullptr, 0,
-                                          stream);
-}
-
-extern "C" int tuch_v2v_min_model(const tuch_contact_model* m, const float* verts, int B, float* min_d2,
-                                  int32_t* argmin, void* hint_inout, void* workspace, size_t workspace_bytes, void* stream)
-{
-    return tuch_v2v_min_model_shared(m, verts, B, min_d2, argmin, hint_inout, workspace, workspace_bytes, 0, stream);
-}
-
-// zero / zero_bytes (multiple of 16, or NULL / 0): a caller buffer cleared by this call's FIRST kernel -- on the stream, before
-// anything enqueued behind the call (no fill launch of the caller's own).
-extern "C" int tuch_v2v_min_model_shared_zero(const tuch_contact_model* m, const float* verts, int B, float* min_d2,
-                                              int32_t* argmin, void* hint_inout, void* workspace, size_t workspace_bytes,
-                                              int leave_room, void* zero, size_t zero_bytes, void* stream)
+// flags: TUCH_V2V_LEAVE_ROOM (1) other kernels run beside the search on another stream, TUCH_V2V_NEAR_FINAL (2) the hints are
+// near-final.  zero / zero_bytes (multiple of 16, or NULL / 0): a caller buffer cleared by this call's FIRST kernel -- on
+// the stream, before anything enqueued behind the call (no fill launch of the caller's own).
+extern "C" int tuch_v2v_min_model(const tuch_contact_model* m, const float* verts, int B, float* min_d2, int32_t* argmin,
+                                  void* hint_inout, void* workspace, size_t workspace_bytes, int flags, void* zero,
+                                  size_t zero_bytes, void* stream)
 {
     TUCH_REQUIRE(m && verts && (min_d2 || argmin), "tuch_v2v_min_model: null pointer");
     TUCH_REQUIRE(m->mask_bits, "tuch_v2v_min_model: the model has no geodesic mask");
-    const bool iterative = (leave_room & 2) != 0;      // flags: 1 leave room for kernels on another stream, 2 bounds are near-final
-    leave_room &= 1;
+    const bool leave_room = (flags & 1) != 0, iterative = (flags & 2) != 0;
     TUCH_REQUIRE(B > 0 && B <= 65535, "tuch_v2v_min_model: bad batch %d", B);
     TUCH_REQUIRE((zero_bytes & 15) == 0 && (((uintptr_t)zero) & 15) == 0 && (zero || zero_bytes == 0),
                  "tuch_v2v_min_model: the buffer to clear must be 16-byte aligned and a multiple of 16 bytes");

@@ -99,11 +99,11 @@ class _SmplLBS(torch.autograd.Function):
         if ctx.full:
             # the kernel writes the two gradients with a row stride: one [B, 24 w] tensor takes both
             g_full = torch.empty(b, 24 * w, dtype=torch.float32, device=go.device)
-            _C.check(L.tuch_smpl_backward_split_add(ctx.dm._handle, _C.row_ptr(go), go.stride(0), _C.row_ptr(bp), bp.stride(0),
-                                                    int(ctx.pose2rot), b, _C.ptr(ws), _C.ptr(gv), _C.ptr(gj),
-                                                    _C.ptr(g_betas), _C.row_ptr(g_full[:, :w]), 24 * w,
-                                                    _C.row_ptr(g_full[:, w:]), 24 * w, None, 23 * w,
-                                                    _C.ptr(ws2), nbytes, _C.stream(), None))
+            _C.check(L.tuch_smpl_backward_split(ctx.dm._handle, _C.row_ptr(go), go.stride(0), _C.row_ptr(bp), bp.stride(0),
+                                                int(ctx.pose2rot), b, _C.ptr(ws), _C.ptr(gv), _C.ptr(gj),
+                                                _C.ptr(g_betas), _C.row_ptr(g_full[:, :w]), 24 * w,
+                                                _C.row_ptr(g_full[:, w:]), 24 * w, None, 23 * w,
+                                                _C.ptr(ws2), nbytes, _C.stream(), None))
             return g_betas, None, None, None, None, g_full
         g_go = torch.empty(go.shape, dtype=torch.float32, device=go.device)
         g_bp = torch.empty(bp.shape, dtype=torch.float32, device=go.device)
@@ -145,10 +145,10 @@ class _SmplLBS(torch.autograd.Function):
                 _C.ptr(ws2), nbytes, _C.stream(), _C.ptr(fixed)))
             adam._applied = True
             return g_betas, g_go.view(ctx.shapes[0]), g_bp.view(ctx.shapes[1]), None, None, None
-        _C.check(L.tuch_smpl_backward_split_add(ctx.dm._handle, _C.row_ptr(go), go.stride(0), _C.row_ptr(bp), bp.stride(0),
-                                                int(ctx.pose2rot), b, _C.ptr(ws), _C.ptr(gv), _C.ptr(gj),
-                                                _C.ptr(g_betas), _C.ptr(g_go), w, _C.ptr(g_bp), 23 * w,
-                                                _C.ptr(extra), 23 * w, _C.ptr(ws2), nbytes, _C.stream(), _C.ptr(fixed)))
+        _C.check(L.tuch_smpl_backward_split(ctx.dm._handle, _C.row_ptr(go), go.stride(0), _C.row_ptr(bp), bp.stride(0),
+                                            int(ctx.pose2rot), b, _C.ptr(ws), _C.ptr(gv), _C.ptr(gj),
+                                            _C.ptr(g_betas), _C.ptr(g_go), w, _C.ptr(g_bp), 23 * w,
+                                            _C.ptr(extra), 23 * w, _C.ptr(ws2), nbytes, _C.stream(), _C.ptr(fixed)))
         return g_betas, g_go.view(ctx.shapes[0]), g_bp.view(ctx.shapes[1]), None, None, None
 
 

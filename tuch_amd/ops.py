@@ -764,9 +764,9 @@ class _Stage2Tail(torch.autograd.Function):
         # is not the plain `objective.backward()` of a fit.  gv (zeros nobody writes in this mode) is what autograd carries.
         fixed = _extra[1] if want_grad else None
         _C.check(L.tuch_smplify_stage2_fused(_C.ptr(v), _C.ptr(partner), _C.ptr(exterior), _C.ptr(valid), b, v.shape[1],
-                                             MODE_SMPLIFY, float(const['euclthres']), _C.ptr(small), None, None, p,
+                                             MODE_SMPLIFY, float(const['euclthres']), _C.ptr(small), p,
                                              float(const['contact_scale']), float(const['r2r_scale']), _C.ptr(share),
-                                             _C.ptr(_extra[7]), None, _C.ptr(out), _C.ptr(gv) if fixed is None else None,
+                                             _C.ptr(_extra[7]), _C.ptr(out), _C.ptr(gv) if fixed is None else None,
                                              model._handle if p else None, _C.ptr(_extra[0]),
                                              _C.ptr(fixed), _C.stream()))
         if want_grad:
@@ -1054,7 +1054,7 @@ class ContactModel:
         e.g. the region pairs) runs on a second stream so that its tail fills the gaps of the long winding
         walk (option overlap = 0 keeps everything on the current stream).
         zero_floats > 0: a float32 buffer of (at least) that many ZEROS is handed to ``also(buffer)`` -- cleared by the
-        search's first kernel (tuch_v2v_min_model_shared_zero), not by a fill launch.
+        search's first kernel (tuch_v2v_min_model), not by a fill launch.
         iterative: the caller is an iterative fit (the previous call's partners, kept as hints, are almost this call's):
         the search then uses fewer, longer wavefronts (see v2v_min).  Results never depend on it."""
         zero = torch.empty((int(zero_floats) + 3) // 4 * 4, dtype=torch.float32, device=verts.device) if zero_floats > 0 else None
@@ -1133,10 +1133,10 @@ class ContactModel:
 
     # K1
     def v2v_min(self, verts: torch.Tensor, leave_room: bool = False, zero: Optional[torch.Tensor] = None, iterative: bool = False):
-        """leave_room: other kernels run beside the search on another stream (tuch_v2v_min_model_shared).
+        """leave_room: other kernels run beside the search on another stream (TUCH_V2V_LEAVE_ROOM of tuch_v2v_min_model).
         iterative: the hints are expected to be near-final (SMPLify-DC's loops): a quarter of the wavefronts, each over more
         leaves -- faster with good bounds (0.412 against 0.426 ms per stage-2 step at batch 64), slower on new bodies.
-        zero: a caller tensor (numel * itemsize a multiple of 16) cleared by the call's first kernel (..._shared_zero)."""
+        zero: a caller tensor (numel * itemsize a multiple of 16) cleared by the call's first kernel."""
         if not self.has_mask:
             raise _C.TuchError('ContactModel was created without a geodesic mask')
         verts = _f32(verts)
@@ -1149,8 +1149,8 @@ class ContactModel:
         ws = _workspace(nbytes, verts.device)
         flags = int(bool(leave_room)) | (2 if iterative else 0)
         zbytes = zero.numel() * zero.element_size() if zero is not None else 0
-        _C.check(L.tuch_v2v_min_model_shared_zero(self._handle, _C.ptr(verts), b, _C.ptr(mn), _C.ptr(arg),
-                                                  _C.ptr(self._v2v_hint(b)), _C.ptr(ws), nbytes, flags, _C.ptr(zero), zbytes, _C.stream()))
+        _C.check(L.tuch_v2v_min_model(self._handle, _C.ptr(verts), b, _C.ptr(mn), _C.ptr(arg),
+                                      _C.ptr(self._v2v_hint(b)), _C.ptr(ws), nbytes, flags, _C.ptr(zero), zbytes, _C.stream()))
         return mn, arg
 
     def _v2v_hint(self, batch: int) -> Optional[torch.Tensor]:
