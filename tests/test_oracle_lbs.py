@@ -78,3 +78,59 @@ def test_autograd_matches_finite_differences(body):
         e[0, idx] = 1e-6
         fd = (f(bp, be + e) - f(bp, be - e)) / 2e-6
         assert_close(be_.grad[0, idx].item(), fd.item(), 1e-5, 1e-7, 'd/dbeta')
+
+
+@pytest.mark.parametrize('pose2rot', [True, False])
+def test_float32_oracle_tracks_float64_per_body_on_the_edge_poses(pose2rot):
+    """The premise of the device tests (tests/test_gpu_lbs.py): on the 362-vertex body, with rest / tiny / small /
+    near-pi / beyond-pi / every-other-joint-zero poses on the first, seam and last rows of a batch of 65, the float32
+    oracle stays far inside the LBS bounds PER BODY (scale = that body's own largest float64 entry) -- so a kernel that
+    exceeds them is wrong, not merely float32.  Measured: verts and joints <= 4.7e-7 of the maximum, g_betas <= 6.3e-7 and
+    g_pose <= 8.8e-7 of the body's maximum, EXCEPT g_pose of the 'tiny' class (every joint at 1e-4 rad) under pose2rot:
+    3.5e-5, float32's 1 - cos(t) next to t = 0 in the reference's own formula.  Nothing fixed is asserted of that body: its
+    error is lbs_cases.e_tiny(), which the device test takes its floor from."""
+    import lbs_cases as lc
+    from helpers import report_value
+    batch = 65
+    c64, c32 = lc.edge_case(batch, pose2rot), lc.edge_case(batch, pose2rot, 'both', torch.float32)
+    classes = c64['classes']
+    assert set(classes) == set(lc.CLASSES) | {'random'}
+    assert [classes[r] for r in (0, 1, 15, 16, 31, 32, 62, 63, 64)] == [
+        'rest', 'tiny', 'near_pi', 'rest', 'mixed_zero', 'beyond_pi', 'rest', 'near_pi', 'mixed_zero']
+    v32, j32, gp32, gb32 = c32['ref']
+    v64, j64, gp64, gb64 = c64['ref']
+    what = 'oracle f32 vs f64 ico6 B=%d pose2rot=%s' % (batch, pose2rot)
+    lc.forward_close_per_class(v32, v64, classes, what + ' verts')
+    lc.forward_close_per_class(j32, j64, classes, what + ' joints')
+    lc.grad_close_per_body(gb32, gb64, lc.GRAD_FLOOR, classes, what + ' grad betas')
+    # the 'tiny' bodies under pose2rot: whatever the float32 formula gives (reported); everywhere else the project's bound
+    tiny = lc.e_tiny(batch) if pose2rot else {}
+    floors = np.full(batch, lc.GRAD_FLOOR)
+    for r, e in tiny.items():
+        report_value(what + ' e_tiny (body %d)' % r, e)
+        assert np.isfinite(e)
+        floors[r] = np.inf
+    assert sorted(tiny) == ([1] if pose2rot else [])
+    lc.grad_close_per_body(gp32, gp64, floors, classes, what + ' grad pose')
+    # more than 20x room everywhere else
+    _, ratio = lc.body_ratio(gp32, gp64, floors)
+    assert ratio.max() < 0.05, ratio.max()
+
+
+def test_edge_poses_places_the_classes_on_the_seams():
+    import lbs_cases as lc
+    for batch in (1, 5, 8, 9, 16, 17, 33, 65):
+        full, be, classes = lc.edge_poses(batch, 3)
+        assert full.shape == (batch, 72) and full.dtype == np.float32 and be.shape == (batch, 10) and len(classes) == batch
+        assert classes[:6] == list(lc.CLASSES)[:batch]
+        if batch >= 9:
+            assert classes[-3:] == list(lc.TAIL)
+        ang = np.linalg.norm(full.reshape(batch, 24, 3).astype(np.float64), axis=2)
+        for r, name in enumerate(classes):
+            if name in lc.ANGLE:
+                assert np.allclose(ang[r], lc.ANGLE[name], rtol=1e-6, atol=0), (batch, r, name)
+            elif name == 'rest':
+                assert not full[r].any()
+            elif name == 'mixed_zero':
+                assert not ang[r, ::2].any() and ang[r, 1::2].all()
+    assert lc.edge_poses(33, 3)[2][15:17] == ['near_pi', 'rest'] and lc.edge_poses(17, 3)[2][14:] == list(lc.TAIL)
