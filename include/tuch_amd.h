@@ -177,6 +177,28 @@ int tuch_adam_step(int count, float* const* params, const float* const* grads, f
                    float* const* exp_avg_sq, const int* sizes, const float* betas, float* step, float lr, float eps,
                    void* stream);
 
+/* ---- tuch/utils/smplxtosmpl_mtp.py: fitting the body model to target meshes in correspondence ------------------ */
+
+/* The data term of one iteration (:100-101) in one launch.  verts, target [B,V,3], transl [B,3], weights [V] or NULL
+ * (all ones: the reference's term), weight_sum = sum_v w_v (V without weights; never 0):
+ *   d_v = verts_v + transl - target_v,   loss[b] = sum_v w_v |d_v| / weight_sum,   total[0] = sum_b loss[b]
+ * and the gradients of total for a unit upstream gradient: grad_verts [B,V,3] = w_v d_v / (|d_v| weight_sum) -- a zero
+ * row where |d_v| = 0 (torch.norm's convention) and where w_v = 0 (such a vertex is not read: its target may be
+ * non-finite) -- and grad_transl [B,3] = sum_v grad_verts.  The four per-body sums and the total are fixed-order sums,
+ * the same bits on every call in either mode of tuch_set_deterministic.  scratch: tuch_vertex_fit_scratch_floats(B, V)
+ * floats; ticket: one int, zero before the first call and left zero by every call. */
+size_t tuch_vertex_fit_scratch_floats(int B, int V);
+int tuch_vertex_fit_terms(const float* verts, const float* transl, const float* target, const float* weights, int B,
+                          int V, float weight_sum, float* scratch, int* ticket, float* loss, float* total,
+                          float* grad_verts, float* grad_transl, void* stream);
+
+/* out[b,i,:] = sum_k data[k] src[b, indices[k], :] over the CSR row k in [indptr[i], indptr[i+1]) (:58 with the
+ * [6890 x 10475] SMPL-X -> SMPL matrix).  src [B,num_src,3] -> out [B,num_rows,3]; indptr [num_rows+1] int32, indices
+ * int32 in [0, num_src) -- the CALLER checks the range when it builds the table --, data float32.  A row's entries are
+ * added in float32 in the order they are stored (deterministic); a row may hold any number, none gives zeros. */
+int tuch_mesh_transfer(const int* indptr, const int* indices, const float* data, const float* src, int B, int num_rows,
+                       int num_src, float* out, void* stream);
+
 /* Objective assembly of losses.py:120-123 as one deterministic reduction:
  * out[0] = sum(small_terms [B,2]) + contact_scale * sum(contact_terms [B,2]) + r2r_scale * sum(r2r [B,P]). */
 int tuch_smplify_objective(const float* small_terms, const float* contact_terms, const float* r2r, int B, int P,

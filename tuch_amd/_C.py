@@ -60,6 +60,9 @@ _SIGNATURES = {
     'tuch_smplify_stage1_terms': (c_int, [c_void_p] * 7 + [c_int, c_int, c_int, c_float, c_float, c_float, c_float] + [c_void_p] * 7),
     'tuch_adam_step': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
                                 c_void_p]),
+    'tuch_vertex_fit_scratch_floats': (c_size_t, [c_int, c_int]),
+    'tuch_vertex_fit_terms': (c_int, [c_void_p] * 4 + [c_int, c_int, c_float] + [c_void_p] * 7),
+    'tuch_mesh_transfer': (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_void_p, c_void_p]),
     'tuch_smplify_objective': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_void_p, c_void_p]),
     'tuch_smplify_objective_bwd': (c_int, [c_void_p, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p,
                                            c_void_p]),

@@ -24,6 +24,8 @@ _DEFAULT_PATHS = {
     'SEGMENT_DIR': 'data/essentials/segments/smpl',
     'STATIC_FITS_DIR': 'data/static_fits',
     'DSC_ROOT': '//tuch/dsc/release',
+    # tuch/utils/smplxtosmpl_mtp.py:43 hard-codes a cluster path; the file is SMPL-X's published model_transfer download
+    'SMPLX_TO_SMPL': 'data/models_utils/smplx_to_smpl.pkl',
 }
 
 

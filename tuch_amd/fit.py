@@ -1,0 +1,124 @@
+"""Fit SMPL to target meshes in correspondence: the optimisation loop of the reference's ``tuch/utils/smplxtosmpl_mtp.py``
+(:63-105), batched and on the device.
+
+The reference fits ``body_pose``, ``betas`` and ``transl`` of ONE body with Adam (lr 1e-2, 5000 iterations) against
+``torch.norm(target - verts, dim=2).mean()`` and starts over for every file.  Here a batch of bodies is fitted at once: the
+objective is the SUM of the bodies' terms, so every body's gradient -- and with Adam's element-wise update its whole
+trajectory -- is that of the reference's batch-1 loop.  One iteration is the body model's forward pass, the data term with
+its gradients as one launch (ops.vertex_fit), the backward pass from the cached unit seed (ops.backward_scalar) and Adam as
+one launch (optim.make_adam); the loop is run by the package's one loop runner (SMPLifyDC._Stage: three eager
+iterations, capture, replay as a hipGraph), and sessions -- the static tensors plus the captured loop -- are kept between
+calls like SMPLifyDC's.  ``TUCH_GRAPH_STRICT`` and ``TUCH_SMPLIFY_SESSIONS`` mean what they mean there.
+
+Constructing needs no device; calling does.  There is no host fallback.
+"""
+from __future__ import annotations
+
+import contextlib
+import os
+from collections import namedtuple
+
+import torch
+
+from . import ops
+from .smplify.smplifydc import SMPLifyDC
+
+MeshFit = namedtuple('MeshFit', ['global_orient', 'body_pose', 'betas', 'transl', 'vertices', 'loss'])
+
+
+class MeshFitter:
+    """``MeshFitter(smpl)(target_vertices, global_orient)`` -> MeshFit.  ``vertices`` [B,V,3] include the translation,
+    ``loss`` [B] is every body's term after the last update.  ``global_orient`` is held fixed (the reference passes it in
+    on every call, :95-98) unless ``fit_global_orient`` is set.  Inputs are never modified."""
+
+    def __init__(self, smpl, step_size=1e-2, num_iters=5000, fit_global_orient=False, use_graph=True, record_history=False):
+        self.smpl = smpl
+        self.step_size = step_size
+        self.num_iters = num_iters
+        self.fit_global_orient = fit_global_orient
+        self.use_graph = use_graph
+        # measurement / test aid: the objective and the parameters *before* every update are kept in self.history['fit'],
+        # the parameters in the optimiser's order: body_pose, betas, transl (, global_orient)
+        self.record_history = record_history
+        self.graph_strict = os.environ.get('TUCH_GRAPH_STRICT', '0') == '1'
+        self.keep_sessions = os.environ.get('TUCH_SMPLIFY_SESSIONS', '1') != '0'
+        self.history = None
+        self.graph_replayed = {}
+        self._sessions = {}
+
+    def _session(self, batch, num_verts, vertex_weights, device):
+        """(key, session): the static tensors, the iteration closure and the loop of a fit with these constants."""
+        # everything the captured loop bakes in; the session keeps the weights alive, so their id cannot be reused
+        key = (batch, num_verts, id(vertex_weights) if vertex_weights is not None else None, device.index,
+               float(self.step_size), bool(self.fit_global_orient), bool(self.record_history))
+        sess = self._sessions.get(key)
+        if sess is not None:
+            return key, sess
+        z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=device)
+        t = dict(body_pose=z(batch, 69), betas=z(batch, 10), transl=z(batch, 3), global_orient=z(batch, 3),
+                 target=z(batch, num_verts, 3))
+        weights = None if vertex_weights is None else ops.fit_weights(vertex_weights, num_verts, device)
+        smpl = self.smpl
+
+        def iteration():
+            out = smpl(global_orient=t['global_orient'], body_pose=t['body_pose'], betas=t['betas'])
+            total, _ = ops.vertex_fit(out.vertices, t['transl'], t['target'], weights)
+            return total, out.vertices
+        params = [t['body_pose'], t['betas'], t['transl']] + ([t['global_orient']] if self.fit_global_orient else [])   # :82-85
+        for p in params:
+            p.requires_grad = True
+        sess = dict(t=t, weights=weights, keys_alive=(vertex_weights,), stage=SMPLifyDC._Stage(self, 'fit', params, iteration, {}))
+        return key, sess
+
+    def __call__(self, target_vertices, global_orient, body_pose=None, betas=None, transl=None, vertex_weights=None):
+        smpl_verts = int(self.smpl.v_template.shape[0])
+        if target_vertices.dim() != 3 or tuple(target_vertices.shape[1:]) != (smpl_verts, 3) or target_vertices.shape[0] == 0:
+            raise ValueError('MeshFitter: target_vertices must be [B,%d,3] (the body model\'s topology), got %s'
+                             % (smpl_verts, tuple(target_vertices.shape)))
+        batch = target_vertices.shape[0]
+        for name, value, width in (('global_orient', global_orient, 3), ('body_pose', body_pose, 69), ('betas', betas, 10),
+                                   ('transl', transl, 3)):
+            if value is not None and tuple(value.shape) != (batch, width):
+                raise ValueError('MeshFitter: %s has shape %s, expected %s' % (name, tuple(value.shape), (batch, width)))
+        device = target_vertices.device
+        if device.type != 'cuda':
+            raise RuntimeError('MeshFitter runs on a HIP device (there is no host fallback); got tensors on %s' % device)
+        if self.smpl.v_template.device != device:
+            self.smpl = self.smpl.to(device)
+        on_gpu = bool(self.use_graph)
+        capture = on_gpu and self.num_iters > 4
+        if self.record_history:
+            self.history = {'fit': []}
+        # graph replays never run on the NULL stream (ops.py)
+        with ops.off_default_stream(device) if on_gpu else contextlib.nullcontext():
+            key, sess = self._session(batch, smpl_verts, vertex_weights, device)
+            t, weights = sess['t'], sess['weights']
+            with torch.no_grad():
+                t['target'].copy_(target_vertices)
+                t['global_orient'].copy_(global_orient)
+                for name, value in (('body_pose', body_pose), ('betas', betas)):
+                    t[name].zero_() if value is None else t[name].copy_(value)
+                if transl is not None:
+                    t['transl'].copy_(transl)
+                else:                          # :70-71, over the vertices that carry weight (their targets may be non-finite)
+                    verts = self.smpl(global_orient=t['global_orient'], body_pose=t['body_pose'], betas=t['betas']).vertices
+                    if weights is None:
+                        t['transl'].copy_(t['target'].mean(1) - verts.mean(1))
+                    else:
+                        used = (weights.tensor != 0)[None, :, None]
+                        gap = torch.where(used, t['target'] - verts, torch.zeros_like(verts))
+                        t['transl'].copy_(gap.sum(1) / used.sum())
+            captured = sess['stage'].run(self.num_iters, None, capture)
+            # a captured loop is kept for the next call; a session that ran eagerly (or lost its capture) is dropped
+            if not (captured and self.keep_sessions):
+                self._sessions.pop(key, None)
+            elif key not in self._sessions:
+                while len(self._sessions) >= 4:
+                    self._sessions.pop(next(iter(self._sessions)))
+                self._sessions[key] = sess
+            with torch.no_grad():
+                verts = self.smpl(global_orient=t['global_orient'], body_pose=t['body_pose'], betas=t['betas']).vertices
+                _, loss = ops.vertex_fit(verts, t['transl'], t['target'], weights)
+                vertices = verts + t['transl'][:, None]
+            own = lambda x: x.detach().clone()
+            return MeshFit(own(t['global_orient']), own(t['body_pose']), own(t['betas']), own(t['transl']), vertices, loss)
