@@ -527,6 +527,56 @@ int tuch_pose_metrics(const float* pred_vertices, const float* gt_vertices, cons
                       const float* J_regressor, const int32_t* joint_map, int B, int V, int R, int J, int pelvis_index,
                       float* mpjpe, float* pa_mpjpe, float* v2v, float* joints, void* stream);
 
+/* ---- the regressor's input: batched crops and augmentation (csrc/image_crop.hip) ---------------------
+ * tuch_crop_batch: tuch/utils/imutils.py:67-106 (crop) and tuch/datasets/base_dataset.py:192-205 (rgb_processing) for B
+ * samples in one launch: out [B,channels,R,R] float32 (normalised) and, optionally, raw [B,channels,R,R] in [0,1].
+ *
+ * Per sample (one tuch_crop_record, built on the host in float64: tuch_amd/ops.py crop_records): a source image, HWC,
+ * 1 or 3 channels, uint8 (type 0) or float32 (type 1), `height` x `width` texels, rows `stride` BYTES apart, its first
+ * texel `offset` bytes into `buffer`; centre, scale, rot (degrees), flip and the per-channel pixel noise pn.
+ *
+ * THE RESAMPLING RULE.
+ * Box: the reference's integer box, ul = transform([1,1], invert=1) - 1, br = transform([R+1,R+1], invert=1) - 1, both
+ * truncated toward zero (imutils.py:73-77), bw = br.x - ul.x, bh = br.y - ul.y (they can differ by one); the pad
+ * p = int(|br - ul| / 2 - bh / 2) when rot != 0, else 0 (imutils.py:80-83).  The padded box P has its origin at
+ * (ox, oy) = ul - p and the size (pw, ph) = (bw + 2p, bh + 2p).
+ * Map: a pixel spans [k, k+1).  A point (xo, yo) of the output, in [0,R)^2, goes to the box, (xo bw / R, yo bh / R), is
+ * shifted by p, rotated by +rot about the centre (pw / 2, ph / 2) of P with [[cos, -sin], [sin, cos]] in (x right, y
+ * down), and 0.5 is subtracted: texel-index coordinates inside P; adding (ox, oy) gives image texels.  This is the
+ * inverse map skimage's rotate and resize compose.  flip mirrors the output: xo -> R - xo.
+ * Samples: K = clamp(ceil(max(bw, bh) / R), 1, 16); output pixel (i, j) is the equal-weight mean of the K x K samples at
+ * (j + (2u+1) / 2K, i + (2v+1) / 2K), rows v outermost, each a bilinear fetch.  K = 1 is plain bilinear (what the
+ * reference does when enlarging); K > 1 stands in for the Gaussian pre-filter skimage applies when shrinking -- a
+ * stated deviation.
+ * Exact positions: with the integer grid coordinates (gx, gy) = (2K j + 2u + 1, 2K i + 2v + 1), gx -> 2KR - gx under flip,
+ *     X = (ax[0] gx + ax[1] gy + ax[2]) >> 16,   Y = (ay[0] gx + ay[1] gy + ay[2]) >> 16      (64-bit, arithmetic shift)
+ * are the position in units of 2^-16 px: the coefficients carry 32 fractional bits, round-to-nearest is folded into the
+ * constant term, and X deviates from the float64 map by less than 2^-12 px anywhere on the grid (R <= 1024).  The texel is
+ * X >> 16, the weight (X & 65535) / 65536: no float decides which texel is read.
+ * Fetch: the texel index and its +1 neighbour are clamped into [0, pw-1] x [0, ph-1] (the edge of P is replicated; the
+ * reference reflects there), then moved by (ox, oy); a texel outside the image reads 0.  Nothing outside
+ * [offset, offset + (height-1) stride + row bytes) is addressed; a record for which that range leaves
+ * [0, buffer_bytes), or whose fields are out of range, yields zeros (the binding refuses it on the host before).
+ * Value, float32 with every operation spelled out: top = fma(t01, wx, t00 (1-wx)), bottom likewise, sample =
+ * fma(bottom, wy, top (1-wy)), summed in sample order, divided by K^2; v = clamp(mean pn_c, 0, 255)
+ * (base_dataset.py:200-202); raw = v / 255; out = (raw - mean_c) / std_c.  A float32 source is treated the same way.  A
+ * 1-channel source fills every output channel; a 3-channel source needs channels = 3.
+ * A box that misses the image gives an all-zero crop (raw = 0), where the reference raises -- a stated deviation.
+ *
+ * mean / std: `channels` host floats, read during the call.  One launch on `stream`, no allocation, no synchronisation:
+ * capturable.  B = 0 is a no-op.  A sample's output does not depend on the batch it is in. */
+typedef struct tuch_crop_record {
+    int64_t offset, stride;          /* bytes */
+    int64_t ax[3], ay[3];            /* the integer affine above */
+    int32_t height, width, channels, type;
+    int32_t pw, ph, ox, oy;          /* P: size and origin in image texels */
+    int32_t K, flip;
+    float pn[3];
+    int32_t reserved;                /* 120 bytes */
+} tuch_crop_record;
+int tuch_crop_batch(const void* buffer, size_t buffer_bytes, const tuch_crop_record* records, int B, int res, int channels,
+                    const float* mean, const float* std, float* out, float* raw, void* stream);
+
 /* ---- the HD-mesh branch of RegressorLoss.contact_loss, tuch/train/loss.py:274-301, as one device pipeline ----
  * (csrc/hd_contact.hip).  tuch_hd_model holds the HD vertex regressor (loss.py:81-83) as its three non-zeros per
  * row -- hd_idx / hd_w [N,3] -- and faces_vert_is_sampled_from (loss.py:85-87) -- hd_face [N]; all host arrays, copied.

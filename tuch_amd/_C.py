@@ -145,6 +145,8 @@ _SIGNATURES = {
     'tuch_contact_vertex_colors_workspace_bytes': (c_size_t, [c_int] * 3),
     'tuch_contact_vertex_colors': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
                                            c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'tuch_crop_batch': (c_int, [c_void_p, c_size_t, c_void_p, c_int, c_int, c_int, POINTER(c_float), POINTER(c_float),
+                                c_void_p, c_void_p, c_void_p]),
 }
 
 

@@ -35,8 +35,8 @@ _MAP = {
     'tuch.eft.loss': 'tuch_amd.eft.loss',
 }
 
-# mapped only on request (install_renderer): after a plain install() the name keeps coming from the checkout
-_OPTIONAL = {'tuch.utils.renderer': 'tuch_amd.utils.renderer'}
+# mapped only on request (install_renderer, install_imutils): after a plain install() the names keep coming from the checkout
+_OPTIONAL = {'tuch.utils.renderer': 'tuch_amd.utils.renderer', 'tuch.utils.imutils': 'tuch_amd.utils.imutils'}
 _enabled = {}
 
 _PACKAGES = ('tuch', 'tuch.utils', 'tuch.smplify', 'tuch.models', 'tuch.train', 'tuch.eft')
@@ -146,13 +146,25 @@ def install_renderer():
     """Opt in: `tuch.utils.renderer` -> tuch_amd.utils.renderer (the device rasteriser; no pyrender / OpenGL).  install()
     alone leaves that name to the reference checkout, whose file needs pyrender, trimesh and torchvision; call this
     after it (or instead of it: the packages are registered here too).  uninstall() undoes it."""
+    return _install_optional('tuch.utils.renderer')
+
+
+def install_imutils():
+    """Opt in: `tuch.utils.imutils` -> tuch_amd.utils.imutils (crops on the device; no skimage / cv2 / scipy.misc), for
+    the reference's datasets, demo and fitting scripts.  install() alone leaves that name to the reference checkout,
+    whose file needs those packages.  uninstall() undoes it."""
+    return _install_optional('tuch.utils.imutils')
+
+
+def _install_optional(*names):
     if _finder not in sys.meta_path:
         sys.meta_path.insert(0, _finder)
     for pkg in ('tuch', 'tuch.utils'):
         if pkg not in sys.modules:
             _package(pkg)
     installed = []
-    for ref_name, our_name in _OPTIONAL.items():
+    for ref_name in names:
+        our_name = _OPTIONAL[ref_name]
         mod = importlib.import_module(our_name)
         _enabled[ref_name] = our_name
         sys.modules[ref_name] = mod
@@ -164,7 +176,7 @@ def install_renderer():
 
 
 def uninstall():
-    """Undo install() and install_renderer(): the finder, the registered packages and the mapped names (tests)."""
+    """Undo install(), install_renderer() and install_imutils(): the finder, the registered packages and the mapped names (tests)."""
     _enabled.clear()
     if _finder in sys.meta_path:
         sys.meta_path.remove(_finder)
