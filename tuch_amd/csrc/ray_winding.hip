@@ -121,12 +121,39 @@ __device__ __forceinline__ uint32_t half_above(float x)
 __device__ __host__ __forceinline__ size_t near_records_at(int B, int L) { return (size_t)B * kNearSlabs * L; }
 __device__ __host__ __forceinline__ size_t near_centres_at(int B, int L) { return near_records_at(B, L) + (size_t)B * L * 8; }
 
+// ---- the crossing walk's filter box of one strip element -------------------------------------------------------------
+// (x'min, x'max, y'min, y'max) of the triangle (p0, p1, p2) the element closes, in the sheared frame and in the stream's
+// own floats, widened by kBoxPad.  The walk tests a (ray, element) pair exactly only if the ray's origin (q'x, q'y) lies
+// in the box (inclusive); see the walk's header (above ray_exact) for why a pair outside it can never count.  Three kinds of element get a box
+// that decides nothing:
+//   priming elements (no triangle)                 : the empty box (+inf, -inf, +inf, -inf);
+//   a corner beyond kBoxRange in x' or y', or NaN  : the full box (-inf, +inf, -inf, +inf);
+//   slivers in projection                          : the full box -- the projected triangle's smallest altitude is at
+//     most kBoxSliver (2 area <= kBoxSliver * sqrt 2 * longest edge in the max norm, which is >= the Euclidean edge / sqrt 2).
+constexpr float kBoxRange = 16.0f;                      // |x'|, |y'| of corners AND origins the filter decides for
+constexpr float kBoxPad = 0x1p-13f;                     // 0.12 mm; >> ulp(kBoxRange) = 2^-19, the rounding of min - pad
+constexpr float kBoxSliver = 0x1p-14f;                  // = 2^-18 kBoxRange, see the walk's header
+__device__ __forceinline__ float4 ray_elem_box(const RayElem& p0, const RayElem& p1, const RayElem& p2)
+{
+    const float inf = __builtin_inff();
+    if ((__float_as_int(p2.sign) & 0xffffff) == 0) return make_float4(inf, -inf, inf, -inf);
+    const float x0 = fminf(fminf(p0.x, p1.x), p2.x), x1 = fmaxf(fmaxf(p0.x, p1.x), p2.x);
+    const float y0 = fminf(fminf(p0.y, p1.y), p2.y), y1 = fmaxf(fmaxf(p0.y, p1.y), p2.y);
+    const float ax = p1.x - p0.x, ay = p1.y - p0.y, bx = p2.x - p0.x, by = p2.y - p0.y;
+    const float area2 = fabsf(ax * by - ay * bx);
+    const float edge = fmaxf(fmaxf(x1 - x0, y1 - y0), 0.0f);      // longest edge in the max norm = the larger box side
+    const bool in_range = fmaxf(fmaxf(fabsf(x0), fabsf(x1)), fmaxf(fabsf(y0), fabsf(y1))) <= kBoxRange;
+    const bool solid = area2 > kBoxSliver * 1.4142137f * edge;     // false when a coordinate is NaN (area2 is NaN then)
+    if (!in_range || !solid) return make_float4(-inf, inf, -inf, inf);
+    return make_float4(x0 - kBoxPad, x1 + kBoxPad, y0 - kBoxPad, y1 + kBoxPad);
+}
+
 template <bool kPose>
 __global__ __launch_bounds__(kBoundsBlock) void ray_leaf_bounds_kernel(
     const RayElem* __restrict__ stream, int T, const TreeNode* __restrict__ nodes, int N,
     const int32_t* __restrict__ height_off, const int32_t* __restrict__ height_nodes, float* __restrict__ bounds,
     const float* __restrict__ verts, const int32_t* __restrict__ vidx, const float* __restrict__ sign, int V, int Lexact,
-    RayElem* __restrict__ stream_out, uint4* __restrict__ zeroed, size_t zeroed_n)
+    RayElem* __restrict__ stream_out, uint4* __restrict__ zeroed, size_t zeroed_n, float4* __restrict__ boxes)
 {
     const int b = blockIdx.y;
     const RayElem* st = stream + (size_t)b * T;
@@ -142,18 +169,28 @@ __global__ __launch_bounds__(kBoundsBlock) void ray_leaf_bounds_kernel(
         if (blockIdx.x == 0)                            // the padding behind the last run (three readable elements past the end)
             for (int p = Lexact + (int)threadIdx.x; p < T; p += kBoundsBlock) stream_out[(size_t)b * T + p] = RayElem{0.f, 0.f, 0.f, 0.f};
     }
+    if (blockIdx.x == 0)                                // ... and its boxes: empty (the walk reads three boxes ahead)
+        for (int p = Lexact + (int)threadIdx.x; p < T; p += kBoundsBlock)
+            boxes[(size_t)b * T + p] = make_float4(__builtin_inff(), -__builtin_inff(), __builtin_inff(), -__builtin_inff());
+    auto posed = [&](int p) {                           // element p of the posed, sheared stream: the same floats either way
+        RayElem e;
+        if (kPose) {
+            const float* c = verts + ((size_t)b * V + vidx[p]) * 3;
+            e.x = shear_x(c[0], c[2]); e.y = shear_y(c[1], c[2]); e.z = c[2]; e.sign = sign[p];
+        } else {
+            e = st[p];
+        }
+        return e;
+    };
     float lo[kSlabs], nhi[kSlabs];                      // minima of the projections and of their negatives
 #pragma unroll
     for (int k = 0; k < kSlabs; ++k) { lo[k] = 3.0e38f; nhi[k] = 3.0e38f; }
     for (int p = sub; p < len; p += 16) {
-        RayElem e;
-        if (kPose) {
-            const float* c = verts + ((size_t)b * V + vidx[off + p]) * 3;
-            e.x = shear_x(c[0], c[2]); e.y = shear_y(c[1], c[2]); e.z = c[2]; e.sign = sign[off + p];
-            stream_out[(size_t)b * T + off + p] = e;
-        } else {
-            e = st[off + p];
-        }
+        const RayElem e = posed(off + p);
+        if (kPose) stream_out[(size_t)b * T + off + p] = e;
+        // the box of the triangle the element closes (its two predecessors lie in the same run: a run starts with the two
+        // priming elements of its first strip, whose boxes are empty whatever is read for them)
+        boxes[(size_t)b * T + off + p] = ray_elem_box(posed(off + max(p - 2, 0)), posed(off + max(p - 1, 0)), e);
         float pr[kSlabs];
         slab_project(e.x, e.y, e.z, pr);
 #pragma unroll
@@ -253,16 +290,6 @@ __device__ __forceinline__ int crossing_with_ties(const P3 a, const P3 b, const 
     return crossing(a, b, c, ea, eb, ec);
 }
 
-// One leaf strip, elements [off, off+len), len % 3 == 0, three readable elements past the end.  Register slots are
-// rotated by position modulo 3 like the solid-angle walk; e[k] = edge function of the edge opposite slot k in
-// stream order (p-2 -> p-1 -> p).  Per element: two new edge functions, the depth determinant, and a branch-free
-// +-1 (the rays of a wavefront all pass the leaf's slabs, so most elements are hit by SOME lane: a "does any lane
-// hit" branch would almost always be taken).  Lanes with an exact tie take the careful form.
-// kSeg: `em` = the segments that list the element's triangle as a face (bit s, s < 8); qmask = the segments the lane's
-// query vertex belongs to: the crossing also goes into per-segment counts (the segment test of winding.hip needs, for
-// every segment vertex, its crossings with the faces of its own segments only).  Eight counters as biased bytes of two
-// words: bits 0-3 of (em & qmask) are spread to the byte positions by one multiplication.
-constexpr uint32_t kSegBias = 0x80808080u;
 // a strip vertex relative to the query, (x, y) as a register pair: the two products of an edge function are ONE packed
 // multiplication with crossed halves (v_pk_mul_f32 rounds each product like v_mul_f32: the same bits, still exactly
 // antisymmetric), and the subtraction of the query is one packed add
@@ -277,71 +304,243 @@ __device__ __forceinline__ float edge_fn(const S3& p, const S3& q)
 }
 __device__ __forceinline__ P3 p3(const S3& a) { return P3{a.xy.x, a.xy.y, a.z}; }
 
-template <int A, bool kSkipIncident, bool kSeg>
-__device__ __forceinline__ void ray_step(const RayElem el, S3 (&s)[3], float (&e)[3], v2f qxy, float qz, int& count,
-                                         int qmask, uint32_t& pa, uint32_t& pb)
+// ---- the walk of one leaf strip: box filter for every (ray, element), exact test for the candidates ------------------------
+// A wavefront holds up to 64 rays (one per lane) and steps through the strip run [off, off + len), len % 3 == 0.  Of the
+// ~145 (ray, element) pairs a ray meets in the leaves it passes, ~10 have the ray's origin inside the projected triangle's
+// bounding box at all -- per LANE: almost every element is hit by some lane of the wavefront, so a "does any lane hit"
+// branch around the exact test saves nothing.  Hence two stages:
+//   filter : the elements' boxes (ray_elem_box, written where the strips are posed) are staged in LDS, see ray_run; four
+//            compares per lane set one bit of the lane's mask; after 30 elements the lanes append their candidates
+//            (element, lane) to the wavefront's queue in LDS;
+//   exact  : whenever the queue holds 64 entries, and at the end of the tile, every lane takes ONE entry: it fetches the
+//            entry's ray (ds_bpermute) and the stream elements p-2, p-1, p (from the chunk's copy in LDS), forms the
+//            relative coordinates and the SAME three edge functions, determinant, min/max classification and tie path the
+//            walk always used; non-zero crossings are added to the ray's counter in LDS, which the ray's own lane
+//            flushes once per tile.
+// The edge shared with the previous triangle is recomputed from the same floats instead of carried: the same bits.
+// Integer sums in any order: the result does not depend on the order of the queue.
+//
+// Bounds: the ring has kRingSize = 128 entries and is indexed modulo 128.  Before an append it holds at most 63 entries
+// (a round of 64 is taken out as soon as it holds 64), an append adds at most 64 (every lane, one entry): at most 127.
+// Entries are read back through `& 63` (lane) and a clamp to [0, kBoxChunk + 1] (position in the chunk's 64 elements).
+// LDS: 512 B ring + 256 B crossings + 512 B segment counters + 1 KB boxes + 1 KB elements = 3328 B per wavefront (5 KB
+// would still fit 32 wavefronts per CU).
+//
+// WHY THE FILTER NEVER DROPS A PAIR THE FLOAT TEST COUNTS (ties included).  Take a pair the filter rejects, say by
+// q'x < box.x (the other three sides are mirror images).  The box is decisive (not full), so all corners and the origin
+// have |x'|, |y'| <= kBoxRange, and box.x = fl(xmin - kBoxPad) < xmin (kBoxPad >> ulp(kBoxRange)).
+//  (1) Relative coordinates are rounded differences: s.x = fl(v'x - q'x) with v'x - q'x > kBoxPad / 2 for all three
+//      corners, and rounding is monotone: all three s.x > 0 (no reliance on denormals: the pad keeps them normal).
+//      So the three relative corners a, b, c lie in the open half plane x > 0; let theta in (-pi/2, pi/2) be their
+//      polar angles as seen from the origin, and |s| <= 2 sqrt 2 kBoxRange =: D.
+//  (2) An edge function is e(P,Q) = fl(fl(Px Qy) - fl(Py Qx)).  Rounding is monotone and a difference of two distinct
+//      floats is not zero, so e > 0 implies Px Qy > Py Qx exactly, i.e. theta(Q) > theta(P).  If e == 0 the two products
+//      rounded to the same float: |Px Qy - Py Qx| <= 2^-24 (|Px Qy| + |Py Qx|) + 2^-148 <= (2^-23 + 2^-100) |P| |Q|
+//      (|P| |Q| >= Px Qx >= 2^-28), i.e. |sin(theta(Q) - theta(P))| <= 2^-23 (1 + 2^-70): rounding can turn a strictly
+//      negative edge function into 0, never into a positive one.  Either way
+//          left_of(e(P,Q), P, Q)  implies  theta(Q) >= theta(P) - eps,   sin eps <= 2^-23 (1 + 2^-70),
+//      whatever the lexicographic tie rule answers.
+//      In the same way  !left_of(e(P,Q), P, Q)  implies  theta(Q) <= theta(P) + eps.
+//  (3) The test counts +-1 only if left_of holds for all of b -> c, c -> a, a -> b, or fails for all of them.  By (2)
+//      the three angles then lie within 2 eps of each other: the relative triangle lies in a wedge of
+//      half-angle eps at the origin, within D sin eps of its bisector, so its width across the bisector, and with it its
+//      smallest altitude, is at most 2 D 2^-23 (1 + 2^-70) < 2^-16.4.
+//  (4) The relative corners differ from (corner - origin) by at most 2^-24 * 2 kBoxRange = 2^-19 per coordinate, which
+//      changes a width by at most 2 sqrt 2 * 2^-19 = 2^-17.5; ray_elem_box computes the altitude of the stream's floats
+//      with an error below 2^-16 (its 2 area is off by at most 8 * 2^-24 times the product of two edges, each at most
+//      2 kBoxRange; divided by the longest edge).  So ray_elem_box sees an altitude below
+//      2^-16.4 + 2^-17.5 + 2^-16 < 2^-14.9 < kBoxSliver = 2^-14 -- and gave that element the FULL box, which rejects
+//      nothing.  Contradiction: a rejected pair counts 0 in the float test.
+// Slivers in projection (triangles nearly parallel to the ray, whose line passes through the origin while the origin lies
+// beyond their end, two edge functions rounding to zero) are exactly the case of (3); corners or origins beyond kBoxRange,
+// NaN included, never reach a decisive compare: such an element has the full box, such a lane compares NaN (passes all).
+// The comparisons are inclusive and written as negations so that NaN passes; pad, range and sliver bound are parts of
+// this argument, not tuning knobs.
+constexpr int kRingSize = 128;
+struct RayQueue {
+    uint32_t ring[kRingSize];                  // (element's position in the chunk << 6) | lane
+    int32_t cross[kRayQueries];                // crossings of the tile's rays
+    uint32_t seg[2][kRayQueries];              // kSeg: per-segment crossings, four byte counters per word (see below)
+    float4 box[64];                            // the boxes of the kBoxChunk elements being filtered (+ 3 readable behind them)
+    RayElem elem[64];                          // ... and the elements themselves, from two before the chunk
+};
+constexpr int kBoxChunk = 60;
+// what a lane knows about its own ray
+struct RayLane { float fx, fy, qx, qy, qz; int qmask; bool active; };
+
+// kSeg: the element's word holds the segments that list its triangle as a face (bits 24-31), qmask the segments the
+// ray's query vertex belongs to: the crossing also goes into per-segment counts (the segment test of winding.hip needs,
+// for every segment vertex, its crossings with the faces of its own segments only).  Eight counters as bytes of two
+// words: bits 0-3 of (em & qmask) are spread to the byte positions by one multiplication; a running word may borrow
+// across its bytes, the final word is the exact sum all the same (seg_leaf_count).
+template <bool kSkipIncident, bool kSeg>
+__device__ __forceinline__ void ray_exact(RayQueue& q, uint32_t& head, int n, const RayLane& me, int lane)
 {
-    constexpr int Bq = (A + 1) % 3, Cq = (A + 2) % 3;            // slots of stream positions p-2 and p-1
-    s[A].xy = (v2f){el.x, el.y} - qxy;
-    s[A].z = el.z - qz;
-    // e[A] = e(Bq -> Cq) is carried over from the previous triangle; the two edges at the new vertex:
-    e[Bq] = edge_fn(s[Cq], s[A]);
-    e[Cq] = edge_fn(s[A], s[Bq]);
-    // the element's fourth word: orientation (integer, bits 0-23) and segments (bits 24-31), see RayElem.  gfx950 has no
-    // scalar float compare -- `sign > 0` and `sign != 0` on the wave-uniform element cost a vector compare each
-    const int word = __float_as_int(el.sign);
-    if ((word & 0xffffff) != 0) {                                 // wave-uniform: the two priming vertices of a strip
-        // triangle (Bq, Cq, A): det = sum of (edge function opposite a corner) x (that corner's depth)
-        const float numz = __builtin_fmaf(e[A], s[A].z, __builtin_fmaf(e[Cq], s[Cq].z, e[Bq] * s[Bq].z));
-        const float mn = __builtin_fminf(__builtin_fminf(e[0], e[1]), e[2]);
-        const float mx = __builtin_fmaxf(__builtin_fmaxf(e[0], e[1]), e[2]);
-        // generic position: the origin is inside the projection iff the edge functions have one sign, the hit is in
-        // front iff det has that sign too; +1 (leaving through the front) for the positive orientation, -1 for the
-        // negative one.  The faces around a query vertex (two edge functions through the origin, det exactly 0)
-        // count 0 here, as they must.
-        int c = (int)(__builtin_fminf(mn, numz) > 0.0f) - (int)(__builtin_fmaxf(mx, numz) < 0.0f);
-        // exact ties: some edge function is zero (mn * mx == 0: all are >= 0 or all <= 0 then) and det is not, i.e. the
-        // ray passes through an edge or a corner of a triangle that does not contain the query
-        const bool edge_zero = mn * mx == 0.0f;
-        if (__builtin_amdgcn_ballot_w64(edge_zero)) {             // the wavefronts of a query's own leaf; else rare
-            const bool tie = edge_zero & (numz != 0.0f);
-            if (__builtin_amdgcn_ballot_w64(tie)) {
-                if (tie) c = crossing_with_ties<kSkipIncident>(p3(s[Bq]), p3(s[Cq]), p3(s[A]), e[Bq], e[Cq], e[A]);
-            }
-        }
-        // one full-rate instruction (left to the compiler, c * sign + count becomes a 64-bit multiply-add: quarter rate);
-        // the 24-bit multiply reads bits 0-23 of the word: the orientation
-        asm("v_mad_i32_i24 %0, %1, %2, %0" : "+v"(count) : "v"(c), "s"(word));
-        if (kSeg && ((uint32_t)word >> 24) != 0) {                // wave-uniform
-            // few lanes belong to one of the element's segments AND cross it: the counters' arithmetic (32-bit integer
-            // multiplications: quarter rate) only when some lane has something to add
-            const uint32_t t = ((uint32_t)word >> 24) & (uint32_t)qmask;
-            if (__builtin_amdgcn_ballot_w64((t != 0) & (c != 0))) {
-                uint32_t cs;
-                asm("v_mul_i32_i24 %0, %1, %2" : "=v"(cs) : "v"(c), "s"(word));
-                pa += cs * (((t & 15u) * 0x00204081u) & 0x01010101u);
-                pb += cs * ((((t >> 4) & 15u) * 0x00204081u) & 0x01010101u);
-            }
+    __syncthreads();                                              // (one wavefront per workgroup) the appends are visible
+    const bool valid = lane < n;
+    const uint32_t ent = q.ring[(head + (uint32_t)lane) & (kRingSize - 1)];
+    head += (uint32_t)n;
+    const int r = (int)(ent & 63u);
+    const uint32_t k = min(ent >> 6, (uint32_t)(kBoxChunk + 1));       // elem[k + 2] is the element, elem[k], elem[k + 1] its predecessors
+    // the entry's ray: every lane is active here (a bpermute from an inactive lane reads 0)
+    const float ox = __int_as_float(__builtin_amdgcn_ds_bpermute(r << 2, __float_as_int(me.qx)));
+    const float oy = __int_as_float(__builtin_amdgcn_ds_bpermute(r << 2, __float_as_int(me.qy)));
+    const float oz = __int_as_float(__builtin_amdgcn_ds_bpermute(r << 2, __float_as_int(me.qz)));
+    const int om = kSeg ? __builtin_amdgcn_ds_bpermute(r << 2, me.qmask) : 0;
+    const RayElem el0 = q.elem[k], el1 = q.elem[k + 1], el2 = q.elem[k + 2];
+    const v2f oxy = {ox, oy};
+    S3 s0, s1, s2;
+    s0.xy = (v2f){el0.x, el0.y} - oxy; s0.z = el0.z - oz;
+    s1.xy = (v2f){el1.x, el1.y} - oxy; s1.z = el1.z - oz;
+    s2.xy = (v2f){el2.x, el2.y} - oxy; s2.z = el2.z - oz;
+    // edge function of the edge opposite each corner, in stream order p-2 -> p-1 -> p
+    const float e0 = edge_fn(s1, s2), e1 = edge_fn(s2, s0), e2 = edge_fn(s0, s1);
+    // triangle (p-2, p-1, p): det = sum of (edge function opposite a corner) x (that corner's depth)
+    const float numz = __builtin_fmaf(e2, s2.z, __builtin_fmaf(e1, s1.z, e0 * s0.z));
+    const float mn = __builtin_fminf(__builtin_fminf(e0, e1), e2);
+    const float mx = __builtin_fmaxf(__builtin_fmaxf(e0, e1), e2);
+    // generic position: the origin is inside the projection iff the edge functions have one sign, the hit is in
+    // front iff det has that sign too; +1 (leaving through the front) for the positive orientation, -1 for the
+    // negative one.  The faces around a query vertex (two edge functions through the origin, det exactly 0)
+    // count 0 here, as they must.
+    int c = (int)(__builtin_fminf(mn, numz) > 0.0f) - (int)(__builtin_fmaxf(mx, numz) < 0.0f);
+    // exact ties: some edge function is zero (mn * mx == 0: all are >= 0 or all <= 0 then) and det is not, i.e. the
+    // ray passes through an edge or a corner of a triangle that does not contain the query
+    const bool tie = (mn * mx == 0.0f) & (numz != 0.0f);
+    if (__builtin_amdgcn_ballot_w64(tie)) {
+        if (tie) c = crossing_with_ties<kSkipIncident>(p3(s0), p3(s1), p3(s2), e0, e1, e2);
+    }
+    // the element's fourth word: orientation (integer, bits 0-23; 0 for a priming element, which then adds nothing) and
+    // segments (bits 24-31), see RayElem
+    const int word = __float_as_int(el2.sign);
+    const int cs = c * ((word << 8) >> 8);
+    if (valid && cs != 0) {
+        atomicAdd(&q.cross[r], cs);
+        if (kSeg) {
+            const uint32_t t = ((uint32_t)word >> 24) & (uint32_t)om;
+            if (t & 15u) atomicAdd(&q.seg[0][r], (uint32_t)cs * (((t & 15u) * 0x00204081u) & 0x01010101u));
+            if (t >> 4) atomicAdd(&q.seg[1][r], (uint32_t)cs * ((((t >> 4) & 15u) * 0x00204081u) & 0x01010101u));
         }
     }
 }
 
-template <bool kSkipIncident, bool kSeg>
-__device__ __forceinline__ void ray_run(const RayElem* __restrict__ st, int off, int len,
-                                        S3 (&s)[3], float (&e)[3], v2f qxy, float qz, int& count,
-                                        int qmask, uint32_t& pa, uint32_t& pb)
+__device__ __forceinline__ uint32_t lanes_below(unsigned long long m)
 {
-    const RayElem* p = st + off;
-    RayElem n0 = p[0], n1 = p[1], n2 = p[2];
-    // (a 32-bit count, opaque to the loop optimiser: compared on the scalar unit; the pointer form `p < end` is a 64-bit
-    // VECTOR compare on gfx950)
-    for (int left = len; left > 0; left -= 3, p += 3) {
-        asm("" : "+s"(left));
-        const RayElem e0 = n0, e1 = n1, e2 = n2;
-        n0 = p[3]; n1 = p[4]; n2 = p[5];
-        ray_step<0, kSkipIncident, kSeg>(e0, s, e, qxy, qz, count, qmask, pa, pb);
-        ray_step<1, kSkipIncident, kSeg>(e1, s, e, qxy, qz, count, qmask, pa, pb);
-        ray_step<2, kSkipIncident, kSeg>(e2, s, e, qxy, qz, count, qmask, pa, pb);
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+
+// The filter of one element: bit K of the lane's mask is set iff the lane's origin lies in the element's box.  Four
+// compares that narrow EXEC and one OR under what is left of it: five
+// vector instructions, one scalar one (EXEC back to `all`, the wavefront's lanes) and no branch per element.  Inclusive
+// and written as negations -- !(lo > f), !(hi < f): NaN passes.
+template <int K>
+__device__ __forceinline__ void ray_filter(const float4 box, unsigned long long all, float fx, float fy, uint32_t& mask)
+{
+    asm volatile("v_cmpx_ngt_f32 vcc, %[lox], %[fx]\n\t"
+                 "v_cmpx_nlt_f32 vcc, %[hix], %[fx]\n\t"
+                 "v_cmpx_ngt_f32 vcc, %[loy], %[fy]\n\t"
+                 "v_cmpx_nlt_f32 vcc, %[hiy], %[fy]\n\t"
+                 "v_or_b32 %[m], %[bit], %[m]\n\t"
+                 "s_mov_b64 exec, %[sv]"
+                 : [m] "+v"(mask)
+                 : [lox] "v"(box.x), [hix] "v"(box.y), [loy] "v"(box.z), [hiy] "v"(box.w), [bit] "n"(1u << K), [sv] "s"(all),
+                   [fx] "v"(fx), [fy] "v"(fy)
+                 : "vcc");
+}
+
+// the lanes' candidate bits of the chunk's elements base .. base + 29 go to the queue: per trip every lane that has one left
+// appends its lowest (the trips: the largest number of candidates any one ray has in the chunk, ~2.3 on average)
+template <bool kSkipIncident, bool kSeg>
+__device__ __forceinline__ void ray_append(uint32_t mask, int base, RayQueue& q, uint32_t& head, uint32_t& tail,
+                                           const RayLane& me, int lane)
+{
+    unsigned long long m;
+    while ((m = __builtin_amdgcn_ballot_w64(mask != 0u)) != 0ull) {
+        if (mask != 0u) {
+            const int k = __builtin_ctz(mask);
+            mask &= mask - 1u;
+            q.ring[(tail + lanes_below(m)) & (kRingSize - 1)] = ((uint32_t)(base + k) << 6) | (uint32_t)lane;
+        }
+        tail += (uint32_t)__builtin_popcountll(m);
+        if (tail - head >= 64u) ray_exact<kSkipIncident, kSeg>(q, head, 64, me, lane);
+    }
+}
+
+// One leaf strip, elements [off, off+len), len % 3 == 0.  The wavefront was waiting, not computing: with the boxes (before:
+// the elements) fetched three at a time one trip ahead, every trip waited for a round trip to the L2.  So the boxes of up
+// to kBoxChunk = 60 elements, and the elements from two before them, are fetched by ONE load each, a box and an element
+// per lane (`pre`, `pre_el`: the tile's first chunk, fetched with the tile's record while the previous tile was walked)
+// and put into LDS: the filter reads the boxes back from there, all lanes the same three per trip and one trip ahead,
+// and the exact test its three elements; the filter's verdicts on 30 elements are bits 0-29 of one register per lane.
+template <bool kSkipIncident, bool kSeg>
+__device__ __forceinline__ void ray_run(const RayElem* __restrict__ st, const float4* __restrict__ boxes, int off, int len, int T,
+                                        RayQueue& q, uint32_t& head, uint32_t& tail, const RayLane& me, int lane,
+                                        bool have_pre, const float4 pre, const RayElem pre_el)
+{
+    const unsigned long long all = __builtin_amdgcn_read_exec();     // every lane of the wavefront: the walk is not divergent
+    for (int c0 = 0; c0 < len; c0 += kBoxChunk) {
+    float4 mine = pre;
+    RayElem mine_el = pre_el;
+    if (!(have_pre && c0 == 0)) {
+        mine = boxes[min(off + c0 + lane, T - 1)];
+        mine_el = st[min(max(off + c0 - 2 + lane, 0), T - 1)];
+    }
+    // the queue's entries name positions in the chunk that is about to go (only runs of more than kBoxChunk elements
+    // and the block-major order get here with entries queued)
+    while (tail != head) ray_exact<kSkipIncident, kSeg>(q, head, (int)min(tail - head, 64u), me, lane);
+    __syncthreads();                                    // (one wavefront per workgroup) the last chunk has been read
+    q.box[lane] = mine;
+    q.elem[lane] = mine_el;
+    __syncthreads();
+    const float4* p = q.box;
+    float4 n0 = p[0], n1 = p[1], n2 = p[2];
+    int at = 0, left = min(len - c0, kBoxChunk);
+    // three elements: bits 3 J .. 3 J + 2; the next three boxes are read meanwhile.  Unrolled by hand: the bits are
+    // literals, the boxes stay where their loads put them, and a 32-bit count is compared on the scalar unit
+#define TUCH_RAY_TRIPLE(J)                                                         \
+    {                                                                              \
+        const float4 b0 = n0, b1 = n1, b2 = n2;                                    \
+        n0 = p[3]; n1 = p[4]; n2 = p[5];                                           \
+        ray_filter<3 * J>(b0, all, me.fx, me.fy, mask);                            \
+        ray_filter<3 * J + 1>(b1, all, me.fx, me.fy, mask);                        \
+        ray_filter<3 * J + 2>(b2, all, me.fx, me.fy, mask);                        \
+        left -= 3; p += 3;                                                         \
+        asm("" : "+s"(left));                                                      \
+    }
+    while (left > 0) {
+        uint32_t mask = 0u;
+        do {
+            TUCH_RAY_TRIPLE(0) if (left <= 0) break;
+            TUCH_RAY_TRIPLE(1) if (left <= 0) break;
+            TUCH_RAY_TRIPLE(2) if (left <= 0) break;
+            TUCH_RAY_TRIPLE(3) if (left <= 0) break;
+            TUCH_RAY_TRIPLE(4) if (left <= 0) break;
+            TUCH_RAY_TRIPLE(5) if (left <= 0) break;
+            TUCH_RAY_TRIPLE(6) if (left <= 0) break;
+            TUCH_RAY_TRIPLE(7) if (left <= 0) break;
+            TUCH_RAY_TRIPLE(8) if (left <= 0) break;
+            TUCH_RAY_TRIPLE(9)
+        } while (false);
+        if (!me.active) mask = 0u;                      // a padding lane repeats another lane's ray
+        ray_append<kSkipIncident, kSeg>(mask, at, q, head, tail, me, lane);
+        at += 30;
+    }
+    }
+#undef TUCH_RAY_TRIPLE
+}
+
+// the end of a tile: the rest of the queue, then every lane takes its own ray's sums and leaves the counters zero
+template <bool kSkipIncident, bool kSeg>
+__device__ __forceinline__ void ray_flush(RayQueue& q, uint32_t& head, uint32_t tail, const RayLane& me, int lane,
+                                          int& crossings, uint32_t& pa, uint32_t& pb)
+{
+    while (tail != head) ray_exact<kSkipIncident, kSeg>(q, head, (int)min(tail - head, 64u), me, lane);
+    __syncthreads();
+    crossings = q.cross[lane];
+    q.cross[lane] = 0;
+    if (kSeg) {
+        pa = q.seg[0][lane]; pb = q.seg[1][lane];
+        q.seg[0][lane] = 0u; q.seg[1][lane] = 0u;
     }
 }
 
@@ -762,21 +961,23 @@ __global__ __launch_bounds__(kTilesFillBlock) void ray_tiles_fill_kernel(
 // fourth word -- tree_sign_word --, the vertices' in seg_vmask).
 template <bool kVerts, bool kCount, bool kSeg>
 __global__ __launch_bounds__(64) void ray_leaf_kernel(
-    const float* __restrict__ pts, const RayElem* __restrict__ stream, const RayTile* __restrict__ tiles,
-    const RayBody* __restrict__ body, const int32_t* __restrict__ pairs, const RayEntry* __restrict__ lists,
+    const float* __restrict__ pts, const RayElem* __restrict__ stream, const float4* __restrict__ boxes,
+    const RayTile* __restrict__ tiles, const RayBody* __restrict__ body, const int32_t* __restrict__ pairs, const RayEntry* __restrict__ lists,
     const int32_t* __restrict__ list_len, const TreeNode* __restrict__ nodes, int num_leaves,
     const int32_t* __restrict__ qperm, const int32_t* __restrict__ counts, int Q, int T, int qblocks, int num_bodies,
     int cap, int max_tiles, int32_t* __restrict__ count, unsigned long long* __restrict__ stats,
     const int32_t* __restrict__ vmask, int32_t* __restrict__ seg_count)
 {
     const int lane = threadIdx.x;
-    struct Work { int b, off, len, slot, qmask; bool active; float qx, qy, qz; };     // b < 0: nothing left; len < 0: block-major tile `off`
+    struct Work { int b, off, len, slot, qmask; bool active; float qx, qy, qz; float4 pre; RayElem pre_el; };     // b < 0: nothing left; len < 0: block-major tile `off`
     // The tiles of the column's bodies x, x + G, ... form one sequence; wavefront y takes every gridDim.y-th of it (a
     // work counter instead serialises: ~100 ns per atomic on one address, measured).
     int b_cur = blockIdx.x, base = 0, g = blockIdx.y;       // current body, tiles before it, next position in the sequence
     auto fetch = [&]() {
         Work w;
         w.b = -1; w.off = w.len = w.slot = 0; w.qmask = 0; w.active = false; w.qx = w.qy = w.qz = 0.0f;
+        w.pre = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        w.pre_el = RayElem{0.0f, 0.0f, 0.0f, 0.0f};
         while (b_cur < num_bodies) {
             const int b = b_cur;
             const int nt = __builtin_amdgcn_readfirstlane(body[b].tiles);
@@ -794,6 +995,8 @@ __global__ __launch_bounds__(64) void ray_leaf_kernel(
                 i0 = kVerts ? qperm[w.slot] : w.slot;
                 w.off = __builtin_amdgcn_readfirstlane(tile.ex_off);
                 w.len = __builtin_amdgcn_readfirstlane(tile.ex_len);
+                w.pre = boxes[(size_t)b * T + min(w.off + lane, T - 1)];      // the run's first chunk of boxes, one per lane
+                w.pre_el = stream[(size_t)b * T + min(max(w.off - 2 + lane, 0), T - 1)];
             } else {
                 const int nq = kVerts ? Q : (counts ? counts[b] : Q);
                 w.slot = (t / kFallbackChunks) * kRayQueries + lane;
@@ -811,20 +1014,27 @@ __global__ __launch_bounds__(64) void ray_leaf_kernel(
         return w;
     };
     int walked = 0;
+    __shared__ RayQueue queue;
+    queue.cross[lane] = 0;
+    queue.seg[0][lane] = 0u; queue.seg[1][lane] = 0u;
+    queue.ring[lane] = 0u; queue.ring[lane + 64] = 0u;
+    uint32_t head = 0u, tail = 0u;                          // wave-uniform; tail - head = entries queued
     Work next = fetch();
     while (next.b >= 0) {
         const Work w = next;
         next = fetch();
-        S3 s[3];
-        float e[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { s[k].xy = (v2f){0.0f, 0.0f}; s[k].z = 0.0f; e[k] = 0.0f; }
-        const v2f qxy = {w.qx, w.qy};
+        RayLane me;
+        me.qx = w.qx; me.qy = w.qy; me.qz = w.qz; me.qmask = w.qmask; me.active = w.active;
+        // an origin beyond the range the boxes decide for (or NaN) is compared as NaN: it passes every box
+        const bool near = (__builtin_fabsf(w.qx) <= kBoxRange) & (__builtin_fabsf(w.qy) <= kBoxRange);
+        me.fx = near ? w.qx : __builtin_nanf("");
+        me.fy = near ? w.qy : __builtin_nanf("");
         int crossings = 0;
-        uint32_t pa = kSegBias, pb = kSegBias;
+        uint32_t pa = 0u, pb = 0u;
         const RayElem* st = stream + (size_t)w.b * T;
+        const float4* bx = boxes + (size_t)w.b * T;
         if (w.len >= 0) {
-            ray_run<kVerts, kSeg>(st, w.off, w.len, s, e, qxy, w.qz, crossings, w.qmask, pa, pb);
+            ray_run<kVerts, kSeg>(st, bx, w.off, w.len, T, queue, head, tail, me, lane, true, w.pre, w.pre_el);
             if (kCount) walked += w.len;
         } else {
             const int qb = w.off / kFallbackChunks, c = w.off % kFallbackChunks;
@@ -832,17 +1042,19 @@ __global__ __launch_bounds__(64) void ray_leaf_kernel(
             const RayEntry* list = lists + ((size_t)w.b * qblocks + qb) * num_leaves;
             for (int j = c; j < cnt; j += kFallbackChunks) {
                 const TreeNode nd = nodes[__builtin_amdgcn_readfirstlane(list[j].node)];
-                ray_run<kVerts, kSeg>(st, nd.ex_off, nd.ex_len, s, e, qxy, w.qz, crossings, w.qmask, pa, pb);
+                ray_run<kVerts, kSeg>(st, bx, nd.ex_off, nd.ex_len, T, queue, head, tail, me, lane, false, w.pre, w.pre_el);
                 if (kCount) walked += nd.ex_len;
             }
         }
+        // (the queue is emptied per tile: its entries name lanes of THIS tile's rays and elements of this tile's body)
+        ray_flush<kVerts, kSeg>(queue, head, tail, me, lane, crossings, pa, pb);
         if (w.active && crossings != 0) atomicAdd(&count[((size_t)w.b * qblocks) * kRayQueries + w.slot], crossings);
-        if (kSeg && w.active && (pa != kSegBias || pb != kSegBias)) {             // few lanes
-            // two words of four byte-wide counters per ray; a tile's (biased) byte sums are added as ONE integer: the
+        if (kSeg && w.active && (pa != 0u || pb != 0u)) {                         // few lanes
+            // two words of four byte-wide counters per ray; a tile's byte sums are added as ONE integer: the
             // running word may borrow across its bytes, the final word is the exact sum all the same (seg_leaf_count)
             int32_t* sc = seg_count + 2 * (((size_t)w.b * qblocks) * kRayQueries + w.slot);
-            if (pa != kSegBias) atomicAdd(sc, (int32_t)(pa - kSegBias));
-            if (pb != kSegBias) atomicAdd(sc + 1, (int32_t)(pb - kSegBias));
+            if (pa != 0u) atomicAdd(sc, (int32_t)pa);
+            if (pb != 0u) atomicAdd(sc + 1, (int32_t)pb);
         }
     }
     if (kCount && lane == 0) atomicAdd(stats, (unsigned long long)walked);
@@ -1329,7 +1541,7 @@ __global__ __launch_bounds__(kBlock) void segment_ray_finalize_kernel(
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct RayLayout {
-    size_t stream, bounds, lists, list_len, zeroed, zeroed_bytes, leaf_cnt, leaf_fill, count, leaf_off, tiles, body, pairs,
+    size_t stream, boxes, bounds, lists, list_len, zeroed, zeroed_bytes, leaf_cnt, leaf_fill, count, leaf_off, tiles, body, pairs,
         stats, total;
     int T, qblocks, cap, max_tiles, workers, columns;
     size_t seg_count;        // per-segment crossing counts of the vertices (models with seg_elem_mask), zeroed with `count`
@@ -1669,6 +1881,7 @@ static RayLayout full_layout(const tuch_contact_model* m, int B, int Q, bool ver
     l.body = tuch_ws_take(o, (size_t)B * sizeof(RayBody));
     l.pairs = tuch_ws_take(o, (size_t)B * l.cap * sizeof(int32_t));
     l.stats = tuch_ws_take(o, 256);
+    l.boxes = tuch_ws_take(o, (size_t)B * l.T * sizeof(float4));     // the walk's filter box of every strip element
     l.total = o;
     return l;
 }
@@ -1699,7 +1912,7 @@ static void launch_ray_boxes(const tuch_contact_model* m, const RayLayout& l, co
                            s, (const RayElem*)st, l.T, (const TreeNode*)m->tree_node, m->tree_nodes,
                            (const int32_t*)m->tree_height_off, (const int32_t*)m->tree_height_nodes, bounds, verts,
                            (const int32_t*)m->tree_vidx, (const float*)m->tree_sign_word, m->V, m->tree_exact_len, st,
-                           (uint4*)(ws + l.zeroed), l.zeroed_bytes / sizeof(uint4));
+                           (uint4*)(ws + l.zeroed), l.zeroed_bytes / sizeof(uint4), (float4*)(ws + l.boxes));
         return;
     }
     hipLaunchKernelGGL(ray_stream_kernel, dim3(ceil_div(l.T, kBlock), B), dim3(kBlock), 0, s, verts,
@@ -1708,8 +1921,8 @@ static void launch_ray_boxes(const tuch_contact_model* m, const RayLayout& l, co
     hipLaunchKernelGGL(ray_leaf_bounds_kernel<false>, dim3(ceil_div(m->tree_leaves, kBoundsBlock / 16), B), dim3(kBoundsBlock), 0, s,
                        (const RayElem*)st, l.T, (const TreeNode*)m->tree_node, m->tree_nodes,
                        (const int32_t*)m->tree_height_off, (const int32_t*)m->tree_height_nodes, bounds,
-                       (const float*)nullptr, (const int32_t*)nullptr, (const float*)nullptr, 0, 0, (RayElem*)nullptr,
-                       (uint4*)nullptr, (size_t)0);
+                       (const float*)nullptr, (const int32_t*)nullptr, (const float*)nullptr, 0, m->tree_exact_len, (RayElem*)nullptr,
+                       (uint4*)nullptr, (size_t)0, (float4*)(ws + l.boxes));
 }
 
 // near leaves -> rays per leaf -> tiles -> crossing counts (count[b][slot])
@@ -1759,7 +1972,7 @@ static int launch_ray_counts(const tuch_contact_model* m, const RayLayout& l, co
     int32_t* seg_count = (int32_t*)(ws + l.seg_count);
 #define TUCH_LAUNCH_RAY_LEAF(COUNT, SEG)                                                                                      \
     hipLaunchKernelGGL((ray_leaf_kernel<kVerts, COUNT, SEG>), grid, dim3(64), 0, s, queries, (const RayElem*)(ws + l.stream),  \
-                       (const RayTile*)tiles, (const RayBody*)body, (const int32_t*)pairs, (const RayEntry*)lists,            \
+                       (const float4*)(ws + l.boxes), (const RayTile*)tiles, (const RayBody*)body, (const int32_t*)pairs, (const RayEntry*)lists,            \
                        (const int32_t*)list_len, nodes, L, qperm, counts, Q, l.T, l.qblocks, B, l.cap, l.max_tiles,           \
                        (int32_t*)(ws + l.count), stats, vmask, seg_count)
     if (stats) {
