@@ -363,6 +363,40 @@ int tuch_winding_points(const tuch_contact_model* model, const float* verts, con
                         const int32_t* counts, int B, int Q, float thresh, float* w, uint8_t* exterior,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* Closest point on the posed surface (csrc/closest_point.hip).  For every real query p of points [B,Q,3]: d2 [B,Q] is
+ * the squared distance to the nearest point c of the model's mesh posed by verts [B,V,3], face [B,Q] a face that
+ * attains it, bary [B,Q,3] the weights with c = sum_k bary[k] * verts[faces[face][k]], each in [0,1], their sum 1
+ * within rounding.  A face without area (coincident or collinear corners) counts as its edges: the nearest point of the
+ * segment or the point, finite outputs.
+ *   The rule: the squared distance of a (query, triangle) pair is one fixed instruction sequence, independent of group,
+ * lane, batch and visiting order; the winner is the smallest d2, among faces whose d2 have the same bits the smallest
+ * face index (a packed minimum of d2 bits << 32 | face).  So a query gives the same bits alone or in any batch, for any
+ * order of the queries, eager or replayed.  Groups of faces (the cluster tree's leaves, or runs of 64 faces for a mesh
+ * without a tree) are skipped by their posed boxes only when no face of them can produce a smaller or equal key: the
+ * float32 box bound carries a margin of 64 * 2^-24 times the squared distance to the box's farthest corner (derivation
+ * in the source file), and the outputs equal an unpruned sweep bit for bit.
+ *   counts [B] device ints or NULL: real queries per body (clamped to [0, Q]); entries at or beyond counts[b] get
+ * d2 = +inf, face = -1, bary = 0.  Every index read from the tables is clamped before it is used as an address.  A
+ * body with NaN or Inf vertices or points changes no other body's bits and yields face indices in [-1, F).  B = 0 or
+ * Q = 0: nothing is done.  No allocation, no synchronisation, capturable; the workspace (boxes [B,G,8] and the posed
+ * corners in group order [B,F,9]) is guarded under option canary. */
+size_t tuch_closest_point_workspace_bytes(const tuch_contact_model* model, int B, int Q);
+int tuch_closest_point(const tuch_contact_model* model, const float* verts /* [B,V,3] */,
+                       const float* points /* [B,Q,3] */, const int32_t* counts /* [B] or NULL */, int B, int Q,
+                       float* d2 /* [B,Q] */, int32_t* face /* [B,Q] */, float* bary /* [B,Q,3] */,
+                       void* workspace, size_t workspace_bytes, void* stream);
+/* Its adjoint in the envelope form (the weights held fixed: exact wherever the closest feature is locally constant):
+ * grad_points [B,Q,3] = 2 g (p - c) is WRITTEN (0 for padded entries and face = -1, which contribute nothing), and
+ * -2 g bary[k] (p - c) is added to the rows of the winning face's three corners -- with grad_verts_fixed_zeroed
+ * (deterministic mode, as tuch_contact_terms_bwd_fixed) as 64-bit fixed-point integers, grad_verts [B,V,3] then being
+ * written from the sums if given; without it as float atomics into a grad_verts the caller has zeroed.  face and bary
+ * are tuch_closest_point's outputs; face indices outside [0, F) are skipped. */
+int tuch_closest_point_bwd(const tuch_contact_model* model, const float* verts, const float* points,
+                           const int32_t* face, const float* bary, const float* grad_d2 /* [B,Q] */, int B, int Q,
+                           float* grad_points /* [B,Q,3] written, or NULL */,
+                           void* grad_verts_fixed_zeroed /* B*V*3 zeroed 64-bit words, or NULL */,
+                           float* grad_verts /* [B,V,3], or NULL */, void* stream);
+
 /* region-pair minima: TUCH.contact_from_verts, train_module.py:69-91 (select NULL, unmasked)
  * and the region-to-region term, losses.py:107-117 (select = gt_contact & has_discrete_contact,
  * geodesically masked).  out_min [B,P] (0 where not selected), out_ij [B,P,2] arg-min vertices. */

@@ -112,6 +112,10 @@ _SIGNATURES = {
     'tuch_winding_points_workspace_bytes': (c_size_t, [c_void_p, c_int, c_int]),
     'tuch_winding_points': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p,
                                     c_void_p, c_size_t, c_void_p]),
+    'tuch_closest_point_workspace_bytes': (c_size_t, [c_void_p, c_int, c_int]),
+    'tuch_closest_point': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_size_t, c_void_p]),
+    'tuch_closest_point_bwd': (c_int, [c_void_p] * 6 + [c_int, c_int] + [c_void_p] * 4),
     'tuch_contact_terms_ragged_fwd': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p,
                                               c_void_p]),
     'tuch_contact_terms_ragged_bwd': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float,

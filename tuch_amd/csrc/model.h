@@ -162,6 +162,12 @@ struct tuch_contact_model {
     std::vector<int32_t> tree_frontier_off_host;   // [tree_num_frontiers+1]
     std::vector<int32_t> tree_face_leaf_host;      // [F] leaf (preorder sequence number) of every face (or empty)
     std::vector<int32_t> tree_qperm_host;          // [tree_qblocks*128] host copy of tree_qperm (or empty)
+    // face groups of the closest-point query (closest_point.hip): the faces of group g are cp_face_list[cp_group_off[g] ..
+    // cp_group_off[g + 1]), at most 64 -- the cluster tree's leaves (a larger leaf in runs of 64), or, without a tree,
+    // runs of 64 consecutive faces; every face is in exactly one group
+    int cp_groups;
+    int32_t* cp_group_off;     // [cp_groups + 1]
+    int32_t* cp_face_list;     // [F]
     // ordered one-ring of every vertex (closed manifold meshes only, else nullptr): ring_vidx[ring_off[v] + j] = r_j
     // with the faces around v being (v, r_j, r_{j+1}) in their own orientation, j cyclic (ray_winding.hip)
     int32_t* ring_off;         // [V+1]

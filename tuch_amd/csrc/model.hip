@@ -75,6 +75,23 @@ void build_strip_tables(tuch_contact_model* m, const int32_t* faces)
     m->tables.put(&m->strip_sign, ss.data(), ss.size());
 }
 
+// Face groups of the closest-point query: the faces ordered by their leaf (index order within a leaf; without a tree
+// every face counts as leaf 0), cut wherever the leaf changes or a group has 64 faces.
+void build_closest_point_tables(tuch_contact_model* m)
+{
+    const int F = m->F, kGroup = 64;
+    const std::vector<int32_t>& leaf = m->tree_face_leaf_host;
+    std::vector<int32_t> list(F), off;
+    for (int f = 0; f < F; ++f) list[f] = f;
+    if (!leaf.empty()) std::stable_sort(list.begin(), list.end(), [&](int32_t a, int32_t b) { return leaf[a] < leaf[b]; });
+    for (int i = 0; i < F; ++i)
+        if (i == 0 || i - off.back() == kGroup || (!leaf.empty() && leaf[list[i]] != leaf[list[i - 1]])) off.push_back(i);
+    m->cp_groups = (int)off.size();
+    off.push_back(F);
+    m->tables.put(&m->cp_face_list, list.data(), list.size());
+    m->tables.put(&m->cp_group_off, off.data(), off.size());
+}
+
 // do the leaves' strip runs tile the exact part of the stream?  (ray_winding.hip poses the strip leaf by leaf)
 bool leaf_runs_tile(const tuch_cluster_tree& t)
 {
@@ -471,6 +488,7 @@ extern "C" int tuch_contact_model_create(
     const tuch_cluster_tree tree = build_tree_tables(m, faces);
     if (tree.num_nodes > 0 && geomask) build_tree_mask_tables(m, tree, geomask);
     if (tree.num_nodes > 0) build_ring_tables(m, faces);
+    build_closest_point_tables(m);
     if (geomask) {      // bits[w][j], bit k = geomask[j][64 w + k]
         const std::vector<uint64_t> bits = pack_mask(geomask, V, tuch_geomask_words(V), nullptr);
         m->tables.put(&m->mask_bits, bits.data(), bits.size());

@@ -1349,6 +1349,34 @@ class ContactModel:
                                        _C.ptr(w), _C.ptr(ext), _C.ptr(ws), nbytes, _C.stream()))
         return w, ext
 
+    def closest_point(self, verts: torch.Tensor, points: torch.Tensor, counts: Optional[torch.Tensor] = None) -> 'ClosestPoint':
+        """The nearest point of this mesh posed by verts [B,V,3] for arbitrary points [B,Q,3] (csrc/closest_point.hip):
+        ``ClosestPoint(d2 [B,Q], face [B,Q] int32, bary [B,Q,3])`` with the nearest point = sum_k bary[k] *
+        verts[faces[face][k]].  counts [B] int32 marks how many points per body are real; the others get d2 = inf,
+        face = -1, bary = 0.  The same bits for a query alone or in any batch and for any order of the queries; any order
+        is exact, blocks of 64 consecutive points that are close in space are fast (a wavefront visits the face groups
+        any of its 64 queries needs).  d2 is differentiable with respect to verts and points with the weights held fixed
+        (exact wherever the closest feature does not change), bit-reproducibly under ``deterministic()``; face and bary
+        are not differentiable."""
+        if verts.dim() != 3 or points.dim() != 3 or verts.shape[0] != points.shape[0] or verts.shape[1] != self.num_verts:
+            raise _C.TuchError('closest_point: verts [B,%d,3] and points [B,Q,3] expected, got %s and %s'
+                               % (self.num_verts, tuple(verts.shape), tuple(points.shape)))
+        if counts is not None:
+            counts = counts.to(torch.int32).contiguous()
+        return ClosestPoint(*_ClosestPoint.apply(verts, points, self, counts))
+
+    def signed_distance(self, verts: torch.Tensor, points: torch.Tensor, counts: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Distance [B,Q] from points [B,Q,3] to this mesh posed by verts, negative where the point is interior
+        (``winding_points(..., flags_only=True)``); +inf for entries beyond counts.  Only the magnitude is differentiable
+        (the gradient is zero at a point on the surface).  Needs a closed mesh: a model without a cluster tree raises."""
+        if self.tree_positions() is None:
+            raise _C.TuchError('signed_distance: the model has no cluster tree (an open or non-manifold mesh has no inside)')
+        d2 = self.closest_point(verts, points, counts).d2
+        _, exterior = self.winding_points(verts, points, counts, flags_only=True)
+        off = d2 > 0
+        dist = torch.where(off, torch.sqrt(torch.where(off, d2, torch.ones_like(d2))), torch.zeros_like(d2))
+        return torch.where(exterior.bool(), dist, -dist)
+
     def v2v_min_indexed(self, points: torch.Tensor, vertex_ids: torch.Tensor, offsets: torch.Tensor,
                         max_points: int, tree_order: bool = False, mfma: bool = False):
         """Ragged masked nearest neighbour (HD points, loss.py:288-291).  points [N,3], vertex_ids [N]
@@ -1393,6 +1421,53 @@ class ContactModel:
     # K5
     def region_pair_min(self, verts: torch.Tensor, select: Optional[torch.Tensor] = None, masked: bool = False):
         return _RegionPairMin.apply(verts, self, select, masked)
+
+
+class ClosestPoint(NamedTuple):
+    d2: torch.Tensor
+    face: torch.Tensor
+    bary: torch.Tensor
+
+
+class _ClosestPoint(torch.autograd.Function):
+    """ContactModel.closest_point: tuch_closest_point forward, tuch_closest_point_bwd (the envelope form) backward."""
+
+    @staticmethod
+    def forward(ctx, verts, points, model: ContactModel, counts):
+        v, pts = _f32(verts), _f32(points)
+        b, q, _ = pts.shape
+        L = _C.lib()
+        d2 = torch.empty(b, q, dtype=torch.float32, device=pts.device)
+        face = torch.empty(b, q, dtype=torch.int32, device=pts.device)
+        bary = torch.empty(b, q, 3, dtype=torch.float32, device=pts.device)
+        nbytes = L.tuch_closest_point_workspace_bytes(model._handle, b, q)
+        ws = _workspace(nbytes, pts.device)
+        if b and q:
+            _C.check(L.tuch_closest_point(model._handle, _C.ptr(v), _C.ptr(pts), _C.ptr(counts), b, q, _C.ptr(d2), _C.ptr(face),
+                                          _C.ptr(bary), _C.ptr(ws), nbytes, _C.stream()))
+        ctx.save_for_backward(v, pts, face, bary)
+        ctx.model = model
+        ctx.mark_non_differentiable(face, bary)
+        return d2, face, bary
+
+    @staticmethod
+    def backward(ctx, grad_d2, _grad_face, _grad_bary):
+        v, pts, face, bary = ctx.saved_tensors
+        b, q, _ = pts.shape
+        want_v, want_p = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if b == 0 or q == 0 or not (want_v or want_p):
+            return (torch.zeros_like(v) if want_v else None), (torch.zeros_like(pts) if want_p else None), None, None
+        g = grad_d2.to(torch.float32).contiguous()
+        gp = torch.empty_like(pts) if want_p else None
+        gv = fixed = None
+        if want_v and deterministic():
+            fixed = torch.zeros(v.numel(), dtype=torch.int64, device=v.device)
+            gv = torch.empty_like(v)
+        elif want_v:
+            gv = torch.zeros_like(v)
+        _C.check(_C.lib().tuch_closest_point_bwd(ctx.model._handle, _C.ptr(v), _C.ptr(pts), _C.ptr(face), _C.ptr(bary),
+                                                 _C.ptr(g), b, q, _C.ptr(gp), _C.ptr(fixed), _C.ptr(gv), _C.stream()))
+        return gv, gp, None, None
 
 
 class HDModel:
