@@ -758,16 +758,14 @@ def test_v2v_tree_walk_matches_flat_search(tag, batch, monkeypatch):
     model.set_option('v2v_tree', 0)
     mn_f, arg_f = model.v2v_min(verts)
     model.set_option('v2v_tree', 1)
-    # leaf_form 2: lanes over the subtree's leaves first (v2v_scan_kernel, the default); 0: the stackless walk
-    # (v2v_tree_kernel).  (Two more forms -- leaf boxes four at a time, aligned row tiles on the matrix cores -- gave the
-    # same keys and were slower; removed in round 4, DESIGN.md section 3 keeps their measurements.)
-    # pairs (round 5, scan only): a leaf in reach of fewer columns of a wavefront than this is not walked row by row; its
+    # the search: lanes over the subtree's leaves first (v2v_scan_kernel).  (Other forms -- a stackless walk, leaf boxes
+    # four at a time, aligned row tiles on the matrix cores -- gave the same keys and were slower; removed, DESIGN.md
+    # section 3 keeps their measurements.)
+    # pairs (round 5): a leaf in reach of fewer columns of a wavefront than this is not walked row by row; its
     # (leaf, column) pairs are queued and evaluated one per lane -- 0: off (round 4's scan), 24: the default, 33: nearly all
-    for waves, leaf_form, pairs in (('1', 2, 24), ('4096', 2, 24), ('1000000', 2, 24), ('1', 2, 0), ('4096', 2, 0), ('4096', 2, 4),
-                                    ('4096', 2, 33), ('1', 2, 33), ('1', 0, 24), ('4096', 0, 24), ('1000000', 0, 24)):
+    for waves, pairs in (('1', 24), ('4096', 24), ('1000000', 24), ('1', 0), ('4096', 0), ('4096', 4), ('4096', 33), ('1', 33)):
         model.set_option('v2v_waves', int(waves))        # one subtree ... as many as the model has
         model.set_option('v2v_pairs', pairs)
-        model.set_option('v2v_flat', leaf_form)
         mn_t, arg_t = model.v2v_min(verts)
         assert torch.equal(mn_t, mn_f)
         diff = (arg_t != arg_f).nonzero()
@@ -780,9 +778,42 @@ def test_v2v_tree_walk_matches_flat_search(tag, batch, monkeypatch):
     # repeatable despite the atomics
     mn_again, arg_again = model.v2v_min(verts)
     assert torch.equal(mn_again, mn_t) and torch.equal(arg_again, arg_t)
-    model.set_option('v2v_flat', 2)
     model.set_option('v2v_waves', 0)
     model.set_option('v2v_pairs', 24)
+
+
+@pytest.mark.parametrize('tag', ['small', 'ico_small'])
+@pytest.mark.parametrize('batch', [1, 5])
+def test_v2v_heads_under_guard_words(tag, batch):
+    """Both heads of the tree search -- rows and seed in one launch from the previous call's partners (v2v_hint = 1), two
+    launches with the seed from the leaf boxes (v2v_hint = 0) -- alone and beside other work (leave_room), with guard words
+    between the regions of the workspace: minima bit for bit those of the all-rows kernel, partners differing only between
+    exactly tied rows, no guard word touched."""
+    g, gm = golden(tag), golden_mask(tag)
+    model = make_model(g, gm, False, False)
+    base = torch.tensor(g['verts'], device=dev())
+    verts = base[torch.arange(batch, device=dev()) % base.shape[0]].contiguous()
+    k = (torch.arange(batch, device=dev(), dtype=torch.float32) - (base.shape[0] - 1)).clamp(min=0).view(-1, 1)
+    verts[:, :, 0] += 0.05 * k * verts[:, :, 1]
+    model.set_option('canary', 1)
+    model.set_option('v2v_tree', 0)
+    mn_f, arg_f = model.v2v_min(verts)
+    model.set_option('v2v_tree', 1)
+    v = verts.double()
+    for hint in (0, 1):
+        model.set_option('v2v_hint', hint)
+        for leave_room in (False, True):
+            for _ in range(2):          # (with hints the second call starts from the first one's partners)
+                mn_t, arg_t = model.v2v_min(verts, leave_room=leave_room)
+                assert torch.equal(mn_t, mn_f)
+                diff = (arg_t != arg_f).nonzero()
+                for b, i in diff.tolist():
+                    d_t = ((v[b, i] - v[b, arg_t[b, i]]) ** 2).sum()
+                    d_f = ((v[b, i] - v[b, arg_f[b, i]]) ** 2).sum()
+                    assert abs(float(d_t - d_f)) < 1e-9 and gm[int(arg_t[b, i]), i]
+                assert len(diff) <= 2
+            assert model.canary_hits() == 0, (hint, leave_room)
+    assert model.canary_selftest() > 0          # (a silent mechanism cannot pass)
 
 
 @pytest.mark.parametrize('tag', ['medium', 'ico_medium'])

@@ -49,15 +49,12 @@ struct tuch_contact_model;
 struct tuch_options {
     int winding_ray = 1;        // 0: never by ray crossings, 1: when only the flags are wanted, 2: also for w (crossings - fan)
     int winding_tree = 1;       // 0: flat strip walk instead of the cluster tree
-    int winding_strips = 1;     // 0: per-triangle kernel
     int tree_waves = 32768;     // frontier choice of the solid-angle walk (128-query blocks)
     int ray_pair_cap = 16;      // (ray, leaf) pairs per query the pair list has room for
     int ray_waves = 32768;      // wavefronts of the crossing kernel
-    int v2v_tree = 1;           // 0: flat nearest-vertex search
+    int v2v_tree = 1;           // 0: all-rows nearest-vertex search (v2v_partial_kernel), the reference of the tests
     int v2v_waves = 0;          // frontier choice of the search (wavefronts aimed at; 0: the form's own default)
-    int v2v_flat = 2;           // search: 2 lanes over a subtree's leaves first (v2v_scan_kernel), 0 the stackless walk (v2v_tree_kernel)
     int v2v_pairs = 24;         // scan: a leaf in reach of FEWER columns of the wavefront than this is not walked row by row for all 64 lanes; its (leaf, column) pairs are queued and evaluated one per lane (round 5); 0: every leaf row by row (round 4)
-    int v2v_lds = -1;           // search beside the inside test: -1 capped at 7 wavefronts per SIMD by register count (-4 / -5 / -6: at that many; round 4, lighter scan: 7 0.487, 6 0.494, 5 0.512, 4 0.530 ms per step), > 0 by an LDS allocation of that many bytes per workgroup (6400: round 2), 0 uncapped
     int seg_splits = 16;        // face splits of the solid-angle segment kernel
     int seg_assist = 1;         // 0: the segment pass counts its body-face crossings itself (read at create only)
     int seg_fused = 1;          // the segment filter behind the body test: 1 one launch (segment_one_kernel, round 4), 0 the general six-launch pass (A/B, tests)
@@ -139,7 +136,8 @@ struct tuch_contact_model {
     int32_t* tree_launch_order;
     int32_t* tree_ancestors;   // [frontier_total][8]
     int32_t* tree_rows;        // [tree_nodes][2]
-    int32_t* tree_v2v_info;    // [tree_nodes][2]: skip pointer | leaf: first row + (rows << 20), inner node: -1; or nullptr
+    int tree_rows_pack;        // 1: a leaf's rows pack as first | count << 20 (V < 2^20, every leaf under 2^11 rows): what the
+                               // search's leaf boxes carry (v2v.hip)
     // geodesic mask in the tree's vertex order: tree_mask_bits[w][j'], bit k = geomask[qperm[j']][qperm[64 w + k]],
     // w < 2 * tree_qblocks, j' < V; tree_masked[w][node] bit k: column 64 w + k has an allowed row below the node
     // (0: the mask rules the whole node out for the wavefront that owns these columns)

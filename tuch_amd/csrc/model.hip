@@ -28,7 +28,7 @@ struct SegmentLists {
     std::vector<int32_t> elem_mask;                // seg_elem_mask (empty without the leaf-assisted form)
 };
 
-// TUCH_DEBUG: why a model does without the leaf-assisted segment pass
+// TUCH_DEBUG: why a model does without the leaf-assisted segment pass or the tree search
 void debug_note(const char* fmt, ...)
 {
     if (!getenv("TUCH_DEBUG")) return;
@@ -65,14 +65,18 @@ void build_mesh_tables(tuch_contact_model* m, const int32_t* faces)
     m->tables.put(&m->canary_hits, &zero, 1);
 }
 
-void build_strip_tables(tuch_contact_model* m, const int32_t* faces)
+// The strip stream is what the flat form of the inside test walks: every model has one (tuch_build_strips opens a strip
+// of at least three elements for every face not yet in one, so F >= 1 gives a non-empty stream).
+int build_strip_tables(tuch_contact_model* m, const int32_t* faces)
 {
     std::vector<int32_t> sv;
     std::vector<float> ss;
     tuch_build_strips(faces, m->F, sv, ss, &m->num_strips);
+    TUCH_REQUIRE(!sv.empty(), "tuch_contact_model_create: no triangle strips for %d faces", m->F);
     m->strip_len = (int)sv.size();
     m->tables.put(&m->strip_vidx, sv.data(), sv.size());
     m->tables.put(&m->strip_sign, ss.data(), ss.size());
+    return TUCH_OK;
 }
 
 // Face groups of the closest-point query: the faces ordered by their leaf (index order within a leaf; without a tree
@@ -140,21 +144,15 @@ tuch_cluster_tree build_tree_tables(tuch_contact_model* m, const int32_t* faces)
     tb.put(&m->tree_launch_order, t.launch_order.data(), t.launch_order.size());
     tb.put(&m->tree_ancestors, t.ancestors.data(), t.ancestors.size());
     tb.put(&m->tree_rows, t.rows.data(), t.rows.size());
-    // what the nearest-vertex walk needs of a node besides its box (rides in the box's padding, v2v.hip)
-    std::vector<int32_t> info((size_t)t.num_nodes * 2);
+    // the search's leaf boxes carry a leaf's rows as first | count << 20 (v2v.hip)
     bool fits = V < (1 << 20);
-    for (int i = 0; i < t.num_nodes; ++i) {
-        const tuch_rows r = t.rows_of(i);
-        fits = fits && (!t.is_leaf(i) || r.count < (1 << 11));
-        info[2 * i] = t.skip(i);
-        info[2 * i + 1] = t.is_leaf(i) ? (r.first | (r.count << 20)) : -1;
-    }
-    if (fits) tb.put(&m->tree_v2v_info, info.data(), info.size());
+    for (int k = 0; k < t.num_leaves(); ++k) fits = fits && t.leaf_rows(k).count < (1 << 11);
+    m->tree_rows_pack = fits ? 1 : 0;
     return t;
 }
 
-// The mask in the tree's vertex order, and which (query block, node) pairs it rules out entirely; then the two flat
-// forms of the search (model.h).
+// The mask in the tree's vertex order, and which (query block, node) pairs it rules out entirely; then the leaf tables
+// of the search (model.h).
 void build_tree_mask_tables(tuch_contact_model* m, const tuch_cluster_tree& t, const uint8_t* geomask)
 {
     const int V = m->V, Wp = 2 * t.num_qblocks, N = t.num_nodes, L = t.num_leaves();
@@ -173,10 +171,16 @@ void build_tree_mask_tables(tuch_contact_model* m, const tuch_cluster_tree& t, c
     }
     tb.put(&m->tree_mask_bits, bits.data(), bits.size());
     tb.put(&m->tree_masked, lanes.data(), lanes.size());
-    // flat form: leaves by their preorder sequence (= their position among the height-0 nodes, which are
-    // listed in ascending node order); a subtree's leaves are a contiguous range of it
+    // The search's tables: leaves by their preorder sequence (= their position among the height-0 nodes); a subtree's
+    // leaves are a contiguous range of it.  That needs height_nodes[0 .. L) in ascending node order, which the tree
+    // builder gives by construction (cluster_tree.hip fills every height's nodes in one pass over i = 0 .. N).  A tree
+    // that does not keep it gets none of the tables below, and a model without them has no tree search: the search runs
+    // over all rows, as for a model without a tree (v2v.hip: use_v2v_tree).
     for (int k = 1; k < L; ++k)
-        if (t.leaf_node(k) <= t.leaf_node(k - 1)) return;
+        if (t.leaf_node(k) <= t.leaf_node(k - 1)) {
+            debug_note("search: leaf %d out of node order, no tree search\n", k);
+            return;
+        }
     std::vector<int32_t> before(N + 1, 0), sub;            // before[i]: the leaves among the nodes ahead of node i
     for (int i = 0; i < N; ++i) before[i + 1] = before[i] + (t.is_leaf(i) ? 1 : 0);
     for (int lo : t.frontier_nodes) {
@@ -484,7 +488,10 @@ extern "C" int tuch_contact_model_create(
     m->F = F;
     tuch_options_from_env(&m->opt);          // the only place the hot calls' switches are read from the environment
     build_mesh_tables(m, faces);
-    build_strip_tables(m, faces);
+    if (const int rc = build_strip_tables(m, faces)) {
+        tuch_contact_model_destroy(m);
+        return rc;
+    }
     const tuch_cluster_tree tree = build_tree_tables(m, faces);
     if (tree.num_nodes > 0 && geomask) build_tree_mask_tables(m, tree, geomask);
     if (tree.num_nodes > 0) build_ring_tables(m, faces);
@@ -512,9 +519,9 @@ namespace {
 struct OptionName { const char* name; int tuch_options::*field; };
 const OptionName kOptions[] = {
     {"winding_ray", &tuch_options::winding_ray}, {"winding_tree", &tuch_options::winding_tree},
-    {"winding_strips", &tuch_options::winding_strips}, {"tree_waves", &tuch_options::tree_waves},
+    {"tree_waves", &tuch_options::tree_waves},
     {"ray_pair_cap", &tuch_options::ray_pair_cap}, {"ray_waves", &tuch_options::ray_waves},
-    {"v2v_tree", &tuch_options::v2v_tree}, {"v2v_flat", &tuch_options::v2v_flat}, {"v2v_pairs", &tuch_options::v2v_pairs}, {"v2v_waves", &tuch_options::v2v_waves}, {"v2v_lds", &tuch_options::v2v_lds},
+    {"v2v_tree", &tuch_options::v2v_tree}, {"v2v_pairs", &tuch_options::v2v_pairs}, {"v2v_waves", &tuch_options::v2v_waves},
     {"seg_splits", &tuch_options::seg_splits}, {"seg_assist", &tuch_options::seg_assist}, {"seg_fused", &tuch_options::seg_fused},
     {"canary", &tuch_options::canary}, {"hd_search", &tuch_options::hd_search}, {"hd_search_waves", &tuch_options::hd_search_waves}, {"hd_overlap", &tuch_options::hd_overlap},
 };

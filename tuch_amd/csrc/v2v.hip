@@ -443,16 +443,15 @@ __global__ __launch_bounds__(64 * kIndexedWaves) void v2v_indexed_kernel(
 // Same result as v2v_partial/merge, but most rows are never touched.  Vertices are renumbered in
 // the cluster tree's order (cluster_tree.hip: the vertices of a leaf are consecutive, a block of 128
 // columns is a compact patch) and the mask is packed in that numbering.  A wavefront owns 64
-// columns and walks the tree: a node is skipped when the mask rules out every (column, row) pair
-// below it (static, per model) or when no column can improve, i.e. for every lane the squared
-// distance from its column to the node's posed box exceeds that column's current minimum
-// (exact: the box distance is a lower bound of every row distance below the node).  Minima start
+// columns and scans the leaves of one subtree: a leaf is skipped when the mask rules out every
+// (column, row) pair in it (static, per model) or when no column can improve, i.e. for every lane
+// the squared distance from its column to the leaf's posed box exceeds that column's current minimum
+// (exact: the box distance is a lower bound of every row distance in the leaf).  Minima start
 // from a seed (the nearest admissible leaf by box distance) and are shared between the subtree
-// walks of a body through 64-bit (distance bits, row) keys merged with atomicMin, so the final
+// scans of a body through 64-bit (distance bits, row) keys merged with atomicMin, so the final
 // key is the lexicographic minimum over all rows attaining the minimum: deterministic, ties go
 // to the smallest row in tree order.
 constexpr int kTreeCols = 64;
-constexpr float kPruneSlack = 0.999999f;      // lower bounds are deflated by 1e-6: rounding of the two sums
 
 #ifdef TUCH_SCAN_COUNTS
 // diagnostic build only (tools/diag/scan_counts.py builds a second library with -DTUCH_SCAN_COUNTS): where the scan's
@@ -460,6 +459,7 @@ constexpr float kPruneSlack = 0.999999f;      // lower bounds are deflated by 1e
 // their rows (per-column test), [4] trips of eight rows, [5] of them skipped by the mask words, [6] of them taking the
 // update branch, [7] trips of four, [8] skipped, [9] taking, [10] wavefronts that return at once (no admissible row)
 __device__ unsigned long long g_scan_counts[32];
+constexpr float kPruneSlack = 0.999999f;      // lower bounds deflated by 1e-6 (rounding of the two sums) in the what-if counts
 #define SCAN_COUNT(i) do { if (threadIdx.x == 0) atomicAdd(&g_scan_counts[i], 1ull); } while (0)
 extern "C" int tuch_debug_scan_counts(unsigned long long* out, int reset)
 {
@@ -513,14 +513,13 @@ __device__ __forceinline__ float row_min(float v)
 __device__ __forceinline__ void v2v_rows_body(
     int bx, const float* __restrict__ verts, int V, int Vp, const int32_t* __restrict__ qperm,
     const int32_t* __restrict__ rows, const int32_t* __restrict__ height_off,
-    const int32_t* __restrict__ height_nodes, int N,
+    const int32_t* __restrict__ height_nodes,
     float* __restrict__ prow,                    // [B,Vp,3]
-    float* __restrict__ bounds,                  // [B,N,8]
-    float* __restrict__ leafbox,                 // [B,L,8] or nullptr: the leaf boxes once more, by leaf index, with the
-                                                 // leaf's row range (first | count << 20) in the last padding word
-    const int32_t* __restrict__ leaf_group,      // with prow_g: first group of four rows of every leaf ([L + 1])
-    float* __restrict__ prow_g, int G)           // [B,G,12] or nullptr: the rows once more, every leaf's rows padded to
-{                                                // groups of four, a group = x[4] y[4] z[4]; box word [3] = first group
+    float* __restrict__ leafbox,                 // [B,L,8]: the leaf boxes by leaf index, with the leaf's row range
+                                                 // (first | count << 20) in the last padding word
+    const int32_t* __restrict__ leaf_group,      // first group of four rows of every leaf ([L + 1])
+    float* __restrict__ prow_g, int G)           // [B,G,12]: the rows once more, every leaf's rows padded to groups of
+{                                                // four, a group = x[4] y[4] z[4]; box word [3] = first group
     const int b = blockIdx.y;
     const int group = threadIdx.x >> 4, sub = threadIdx.x & 15;
     const int i = height_off[0] + bx * (kBoundsBlock / 16) + group;
@@ -535,46 +534,37 @@ __device__ __forceinline__ void v2v_rows_body(
     const int node = height_nodes[real ? i : height_off[0]];
     const int off = rows[2 * node], len = real ? rows[2 * node + 1] : 0;
     float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, nhi[3] = {3.0e38f, 3.0e38f, 3.0e38f};
-    const int g0 = prow_g && real ? leaf_group[i - height_off[0]] : 0;
-    float* pg = prow_g ? prow_g + ((size_t)b * G + g0) * 12 : nullptr;
-    if (prow_g)                                  // the padding rows of the last group (their mask words are 0)
-        for (int k = len + sub; k < ((len + 3) & ~3); k += 16) {
-            float* o = pg + (k >> 2) * 12 + (k & 3);
-            o[0] = 0.0f; o[4] = 0.0f; o[8] = 0.0f;
-        }
+    const int g0 = real ? leaf_group[i - height_off[0]] : 0;
+    float* pg = prow_g + ((size_t)b * G + g0) * 12;
+    for (int k = len + sub; k < ((len + 3) & ~3); k += 16) {      // the padding rows of the last group (their mask words are 0)
+        float* o = pg + (k >> 2) * 12 + (k & 3);
+        o[0] = 0.0f; o[4] = 0.0f; o[8] = 0.0f;
+    }
     for (int j = off + sub; j < off + len; j += 16) {
         const int v = qperm[j];
         const float x = vb[3 * v], y = vb[3 * v + 1], z = vb[3 * v + 2];
         pb[3 * j] = x; pb[3 * j + 1] = y; pb[3 * j + 2] = z;
-        if (prow_g) {
-            float* o = pg + ((j - off) >> 2) * 12 + ((j - off) & 3);
-            o[0] = x; o[4] = y; o[8] = z;
-        }
+        float* o = pg + ((j - off) >> 2) * 12 + ((j - off) & 3);
+        o[0] = x; o[4] = y; o[8] = z;
         lo[0] = fminf(lo[0], x); lo[1] = fminf(lo[1], y); lo[2] = fminf(lo[2], z);
         nhi[0] = fminf(nhi[0], -x); nhi[1] = fminf(nhi[1], -y); nhi[2] = fminf(nhi[2], -z);
     }
 #pragma unroll
     for (int k = 0; k < 3; ++k) { lo[k] = row_min(lo[k]); nhi[k] = row_min(nhi[k]); }
     if (real && sub == 0) {
-        float* o = bounds + ((size_t)b * N + node) * 8;
-        o[0] = lo[0]; o[1] = lo[1]; o[2] = lo[2]; o[3] = 0.0f;
-        o[4] = -nhi[0]; o[5] = -nhi[1]; o[6] = -nhi[2]; o[7] = 0.0f;
-        if (leafbox) {
-            const int L = height_off[1] - height_off[0];
-            float* q = leafbox + ((size_t)b * L + (i - height_off[0])) * 8;
-            q[0] = lo[0]; q[1] = lo[1]; q[2] = lo[2]; q[3] = __int_as_float(g0);
-            q[4] = -nhi[0]; q[5] = -nhi[1]; q[6] = -nhi[2]; q[7] = __int_as_float(off | (len << 20));
-        }
+        const int L = height_off[1] - height_off[0];
+        float* q = leafbox + ((size_t)b * L + (i - height_off[0])) * 8;
+        q[0] = lo[0]; q[1] = lo[1]; q[2] = lo[2]; q[3] = __int_as_float(g0);
+        q[4] = -nhi[0]; q[5] = -nhi[1]; q[6] = -nhi[2]; q[7] = __int_as_float(off | (len << 20));
     }
 }
 
 __global__ __launch_bounds__(kBoundsBlock) void v2v_rows_kernel(
     const float* __restrict__ verts, int V, int Vp, const int32_t* __restrict__ qperm, const int32_t* __restrict__ rows,
-    const int32_t* __restrict__ height_off, const int32_t* __restrict__ height_nodes, int N, float* __restrict__ prow,
-    float* __restrict__ bounds, float* __restrict__ leafbox, const int32_t* __restrict__ leaf_group, float* __restrict__ prow_g,
-    int G)
+    const int32_t* __restrict__ height_off, const int32_t* __restrict__ height_nodes, float* __restrict__ prow,
+    float* __restrict__ leafbox, const int32_t* __restrict__ leaf_group, float* __restrict__ prow_g, int G)
 {
-    v2v_rows_body(blockIdx.x, verts, V, Vp, qperm, rows, height_off, height_nodes, N, prow, bounds, leafbox, leaf_group, prow_g, G);
+    v2v_rows_body(blockIdx.x, verts, V, Vp, qperm, rows, height_off, height_nodes, prow, leafbox, leaf_group, prow_g, G);
 }
 
 // One column per lane (64 columns per wavefront): the union of the columns' search balls is smaller for 64
@@ -744,26 +734,15 @@ __device__ __forceinline__ void v2v_rows_packed(Column& c, const float* __restri
     }
 }
 
-// squared distance from the lane's column to a box
-__device__ __forceinline__ float box_dist2(const Column& c, const float* __restrict__ box)
-{
-    const float ex = __builtin_fmaxf(__builtin_fmaxf(box[0] - c.px, c.px - box[4]), 0.0f);
-    const float ey = __builtin_fmaxf(__builtin_fmaxf(box[1] - c.py, c.py - box[5]), 0.0f);
-    const float ez = __builtin_fmaxf(__builtin_fmaxf(box[2] - c.pz, c.pz - box[6]), 0.0f);
-    return __builtin_fmaf(ez, ez, __builtin_fmaf(ey, ey, ex * ex));
-}
-
-// seed: descend to the admissible leaf nearest to the block's box, evaluate its rows.
-// grid (B, 64-column blocks); the static mask table is kept per 64-column block.
+// seed of a call without hints: the rows of the admissible leaf nearest to the block's box, and the box of the block's
+// columns for the scan.  grid (B, 64-column blocks); the static mask tables are kept per 64-column block.
 __global__ __launch_bounds__(64) void v2v_seed_kernel(
     const float* __restrict__ prow, int V, int Vp, const uint64_t* __restrict__ bits,
-    const TreeNode* __restrict__ nodes, const int32_t* __restrict__ rows, const float* __restrict__ bounds,
     const uint64_t* __restrict__ masked, int N,
-    const int32_t* __restrict__ hint,            // [B,Vp] a row per column (tree order) from an earlier call, or nullptr
     uint64_t* __restrict__ keys,                 // [B,Vp]
-    float* __restrict__ colbox,                  // [B][column blocks][8] or nullptr: the box of the block's 64 columns
+    float* __restrict__ colbox,                  // [B][column blocks][8]: the box of the block's 64 columns
     const float* __restrict__ leafbox,           // [B][L][8] + masked_leaf [column blocks][L]: the leaf to seed from is found
-    const uint64_t* __restrict__ masked_leaf, int L)   // among the leaves themselves (no inner boxes needed), or nullptr
+    const uint64_t* __restrict__ masked_leaf, int L)   // among the leaves themselves (no inner boxes needed)
 {
     const int b = blockIdx.x, qb = blockIdx.y, lane = threadIdx.x;
     const float* pb = prow + (size_t)b * Vp * 3;
@@ -772,107 +751,52 @@ __global__ __launch_bounds__(64) void v2v_seed_kernel(
     c.px = pb[3 * i0]; c.py = pb[3 * i0 + 1]; c.pz = pb[3 * i0 + 2];
     c.best = __builtin_inff();
     c.arg = 0;
-    if (colbox) {
-        float lo[3] = {c.px, c.py, c.pz}, hi[3] = {c.px, c.py, c.pz};
+    float lo[3] = {c.px, c.py, c.pz}, hi[3] = {c.px, c.py, c.pz};
 #pragma unroll
-        for (int m = 32; m >= 1; m >>= 1)
+    for (int m = 32; m >= 1; m >>= 1)
 #pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                lo[k] = fminf(lo[k], __shfl_xor(lo[k], m));
-                hi[k] = fmaxf(hi[k], __shfl_xor(hi[k], m));
-            }
-        if (lane == 0) {
-            float* o = colbox + ((size_t)b * gridDim.y + qb) * 8;
-            o[0] = lo[0]; o[1] = lo[1]; o[2] = lo[2]; o[3] = 0.0f; o[4] = hi[0]; o[5] = hi[1]; o[6] = hi[2]; o[7] = 0.0f;
+        for (int k = 0; k < 3; ++k) {
+            lo[k] = fminf(lo[k], __shfl_xor(lo[k], m));
+            hi[k] = fmaxf(hi[k], __shfl_xor(hi[k], m));
         }
-    }
-    const uint64_t* mk = masked + (size_t)qb * N;     // per node: the lanes with an allowed row below it
-    bool have = false;
-    if (hint) {
-        // the partner found for this column by an earlier call (e.g. the previous iteration of a fit): still an
-        // admissible row, so its current distance is a valid -- and usually almost final -- upper bound
-        const int j = hint[(size_t)b * Vp + i0];
-        if (j >= 0 && j < V && ((bits[(size_t)qb * V + j] >> lane) & 1)) {
-            const float dx = c.px - pb[3 * j], dy = c.py - pb[3 * j + 1], dz = c.pz - pb[3 * j + 2];
-            c.best = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
-            c.arg = j;
-            have = true;
-        }
-    }
-    // Every column that has an allowed row at all already holds a bound: the descent to the nearest admissible leaf and
-    // its rows would add nothing the walk does not find (22 -> 8 us at the head of the search's chain in an iterative fit).
-    if ((mk[0] & ~__builtin_amdgcn_ballot_w64(have)) != 0) {
-        float lo[3] = {c.px, c.py, c.pz}, hi[3] = {c.px, c.py, c.pz};
+    const uint64_t need = masked[(size_t)qb * N];     // the lanes with an allowed row below the root
+    if (need != 0) {
+        // one leaf per lane, the nearest of those that hold an allowed row for one of the columns (any admissible rows
+        // make a valid seed; the leaf scans do not need the inner nodes' boxes at all)
+        const float inf = __builtin_inff();
+        float gbest = inf;
+        int lbest = 0x7fffffff;
+        for (int base = 0; base < L; base += 64) {
+            const int li = base + lane;
+            float g = inf;
+            if (li < L && (masked_leaf[(size_t)qb * L + li] & need) != 0) {
+                const float* box = leafbox + ((size_t)b * L + li) * 8;
+                g = 0.0f;
 #pragma unroll
-        for (int m = 32; m >= 1; m >>= 1)
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                lo[k] = fminf(lo[k], __shfl_xor(lo[k], m));
-                hi[k] = fmaxf(hi[k], __shfl_xor(hi[k], m));
-            }
-        if (leafbox) {
-            // flat form: one leaf per lane, the nearest of those that hold an allowed row for a column still without a
-            // bound (any admissible rows make a valid seed; the leaf scans do not need the inner nodes' boxes at all, so
-            // tree_inner_bounds_kernel is no longer in their chain)
-            const uint64_t need = mk[0] & ~__builtin_amdgcn_ballot_w64(have);
-            const float inf = __builtin_inff();
-            float gbest = inf;
-            int lbest = 0x7fffffff;
-            for (int base = 0; base < L; base += 64) {
-                const int li = base + lane;
-                float g = inf;
-                if (li < L && (masked_leaf[(size_t)qb * L + li] & need) != 0) {
-                    const float* box = leafbox + ((size_t)b * L + li) * 8;
-                    g = 0.0f;
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) {
-                        const float e = fmaxf(fmaxf(box[k] - hi[k], lo[k] - box[4 + k]), 0.0f);
-                        g = fmaf(e, e, g);
-                    }
+                for (int k = 0; k < 3; ++k) {
+                    const float e = fmaxf(fmaxf(box[k] - hi[k], lo[k] - box[4 + k]), 0.0f);
+                    g = fmaf(e, e, g);
                 }
-                if (g < gbest) { gbest = g; lbest = li; }
             }
-            float gmin = gbest;
-#pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) gmin = fminf(gmin, __shfl_xor(gmin, m));
-            if (gmin < inf) {
-                int pick = gbest == gmin ? lbest : 0x7fffffff;          // the smallest leaf index among the nearest
-#pragma unroll
-                for (int m = 32; m >= 1; m >>= 1) pick = min(pick, __shfl_xor(pick, m));
-                pick = __builtin_amdgcn_readfirstlane(pick);
-                const int range = __builtin_amdgcn_readfirstlane(__float_as_int(leafbox[((size_t)b * L + pick) * 8 + 7]));
-                v2v_rows(c, pb, bits + (size_t)qb * V, range & 0xfffff, range >> 20);
-            }
-            keys[(size_t)b * Vp + i0] = v2v_key(c.best, c.arg);
-            return;
+            if (g < gbest) { gbest = g; lbest = li; }
         }
-        const float* bb = bounds + (size_t)b * N * 8;
-        auto gap2 = [&](int node) {                 // squared distance between the block's box and the node's box
-            const float* box = bb + (size_t)node * 8;
-            float g = 0.0f;
+        float gmin = gbest;
 #pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const float e = fmaxf(fmaxf(box[k] - hi[k], lo[k] - box[4 + k]), 0.0f);
-                g = fmaf(e, e, g);
-            }
-            return g;
-        };
-        int node = 0;
-        bool ok = mk[0] != 0;
-        while (ok) {
-            const TreeNode nd = nodes[node];
-            if (nd.c0 < 0) break;
-            const bool a0 = mk[nd.c0] != 0, a1 = mk[nd.c1] != 0;
-            if (a0 && a1) {
-                const float g0 = gap2(nd.c0), g1 = gap2(nd.c1);
-                node = __builtin_amdgcn_readfirstlane(g1 < g0 ? nd.c1 : nd.c0);
-            } else if (a0 || a1) {
-                node = a0 ? nd.c0 : nd.c1;
-            } else {
-                ok = false;
-            }
+        for (int m = 32; m >= 1; m >>= 1) gmin = fminf(gmin, __shfl_xor(gmin, m));
+        if (gmin < inf) {
+            int pick = gbest == gmin ? lbest : 0x7fffffff;          // the smallest leaf index among the nearest
+#pragma unroll
+            for (int m = 32; m >= 1; m >>= 1) pick = min(pick, __shfl_xor(pick, m));
+            pick = __builtin_amdgcn_readfirstlane(pick);
+            const int range = __builtin_amdgcn_readfirstlane(__float_as_int(leafbox[((size_t)b * L + pick) * 8 + 7]));
+            v2v_rows(c, pb, bits + (size_t)qb * V, range & 0xfffff, range >> 20);
         }
-        if (ok) v2v_rows(c, pb, bits + (size_t)qb * V, rows[2 * node], rows[2 * node + 1]);
+    }
+    // (the stores go last: behind an unconditional store the compiler no longer takes the mask words of v2v_rows for
+    // unwritten memory and fetches them through vector loads -- select_by_lane_mask needs them in scalar registers)
+    if (lane == 0) {
+        float* o = colbox + ((size_t)b * gridDim.y + qb) * 8;
+        o[0] = lo[0]; o[1] = lo[1]; o[2] = lo[2]; o[3] = 0.0f; o[4] = hi[0]; o[5] = hi[1]; o[6] = hi[2]; o[7] = 0.0f;
     }
     keys[(size_t)b * Vp + i0] = v2v_key(c.best, c.arg);
 }
@@ -885,9 +809,9 @@ __global__ __launch_bounds__(64) void v2v_seed_kernel(
 // (slower, never wrong) -- calls without hints take the two launches.
 __global__ __launch_bounds__(kBoundsBlock) void v2v_rows_seed_kernel(
     const float* __restrict__ verts, int V, int Vp, const int32_t* __restrict__ qperm, const int32_t* __restrict__ rows,
-    const int32_t* __restrict__ height_off, const int32_t* __restrict__ height_nodes, int N, float* __restrict__ prow,
-    float* __restrict__ bounds, float* __restrict__ leafbox, const int32_t* __restrict__ leaf_group, float* __restrict__ prow_g,
-    int G, int row_blocks, const uint64_t* __restrict__ bits, const int32_t* __restrict__ hint, uint64_t* __restrict__ keys,
+    const int32_t* __restrict__ height_off, const int32_t* __restrict__ height_nodes, float* __restrict__ prow,
+    float* __restrict__ leafbox, const int32_t* __restrict__ leaf_group, float* __restrict__ prow_g, int G, int row_blocks,
+    const uint64_t* __restrict__ bits, const int32_t* __restrict__ hint, uint64_t* __restrict__ keys,
     float* __restrict__ colbox, uint4* __restrict__ zero, size_t zero_n16)
 {
     // a buffer the CALLER wants cleared before the kernels it enqueues behind this call run (SMPLify-DC stage 2: the vertex
@@ -899,8 +823,7 @@ __global__ __launch_bounds__(kBoundsBlock) void v2v_rows_seed_kernel(
             zero[i] = make_uint4(0u, 0u, 0u, 0u);
     }
     if ((int)blockIdx.x < row_blocks) {
-        v2v_rows_body(blockIdx.x, verts, V, Vp, qperm, rows, height_off, height_nodes, N, prow, bounds, leafbox, leaf_group,
-                      prow_g, G);
+        v2v_rows_body(blockIdx.x, verts, V, Vp, qperm, rows, height_off, height_nodes, prow, leafbox, leaf_group, prow_g, G);
         return;
     }
     const int b = blockIdx.y, lane = threadIdx.x & 63;
@@ -933,63 +856,11 @@ __global__ __launch_bounds__(kBoundsBlock) void v2v_rows_seed_kernel(
     }
 }
 
-__global__ __launch_bounds__(64) void v2v_tree_kernel(
-    const float* __restrict__ prow, int V, int Vp, const uint64_t* __restrict__ bits,
-    const TreeNode* __restrict__ nodes, const int32_t* __restrict__ rows, const float* __restrict__ bounds,
-    const uint64_t* __restrict__ masked, int N, const int32_t* __restrict__ frontier,
-    const int32_t* __restrict__ order, uint64_t* __restrict__ keys)
-{
-    const int b = blockIdx.x, lane = threadIdx.x;
-    const int pair = __builtin_amdgcn_readfirstlane(order[blockIdx.y >> 1]);      // launch order over 128-blocks
-    const int sub = pair >> 16, qb = (pair & 0xffff) * 2 + (blockIdx.y & 1);
-    const float* pb = prow + (size_t)b * Vp * 3;
-    const int i0 = qb * kTreeCols + lane;
-    uint64_t* kb = keys + (size_t)b * Vp;
-    // any value read here is the key of a real row (seed, or another walk's improvement): a valid bound
-    const uint64_t init = __hip_atomic_load(kb + i0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    Column c;
-    c.px = pb[3 * i0]; c.py = pb[3 * i0 + 1]; c.pz = pb[3 * i0 + 2];
-    c.best = __uint_as_float((uint32_t)(init >> 32));
-    c.arg = (int)(uint32_t)init;
-    const float* bb = bounds + (size_t)b * N * 8;
-    const uint64_t* mk = masked + (size_t)qb * N;     // per node: the lanes with an allowed row below it
-    const uint64_t* m0 = bits + (size_t)qb * V;
-    int node = __builtin_amdgcn_readfirstlane(frontier[sub]);
-    const int end = __builtin_amdgcn_readfirstlane(nodes[node].skip);
-    while (node < end) {
-        // one round of scalar loads per node: its box, with the skip pointer and the leaf's row range in the two padding
-        // words (tree_inner_bounds_kernel), and the lanes that have an allowed row below it
-        const float* box = bb + (size_t)node * 8;
-        const uint64_t lanes = mk[node];
-        const float lx = box[0], ly = box[1], lz = box[2], hx = box[4], hy = box[5], hz = box[6];
-        const int skip = __float_as_int(box[3]), leaf = __float_as_int(box[7]);
-        // only a lane that has an allowed row below the node AND is within reach of its box can improve; the distance
-        // to the box through the nearest point of it (median of three), bit for bit box_dist2()
-        const float dx = c.px - __builtin_amdgcn_fmed3f(c.px, lx, hx);
-        const float dy = c.py - __builtin_amdgcn_fmed3f(c.py, ly, hy);
-        const float dz = c.pz - __builtin_amdgcn_fmed3f(c.pz, lz, hz);
-        const float g = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx)) * kPruneSlack;
-        const uint64_t reach = __builtin_amdgcn_ballot_w64(g <= c.best) & lanes;
-        if (reach == 0) {
-            node = skip;
-        } else if (leaf >= 0) {
-            v2v_rows(c, pb, m0, leaf & 0xfffff, leaf >> 20, reach);
-            node = skip;
-        } else {
-            node = node + 1;
-        }
-        node = __builtin_amdgcn_readfirstlane(node);
-    }
-    const uint64_t k0 = v2v_key(c.best, c.arg);
-    if (k0 < init) atomicMin((unsigned long long*)(kb + i0), (unsigned long long)k0);
-}
-
-// Second form (the default): lanes over LEAVES first.  The walk above spends most of their vector instructions on box tests that fail
-// (~20 node tests of ~12 instructions per wavefront against ~80 instructions of row arithmetic; the kernel is ~70 % VALU
-// issue).  Here a wavefront tests all leaves of its subtree AT ONCE, one leaf per lane, against the box of its 64 columns
-// and the largest bound among them (conservative: box-to-box distance), and only the survivors get the per-column test
-// and their rows.  Same rows as the walks -> the same keys.  colbox: the box of every 64-column block, left by
-// v2v_seed_kernel ([B][column blocks][8]).
+// The scan: lanes over LEAVES first.  (A stackless walk of the subtree's nodes, removed, spent most of its vector
+// instructions on box tests that fail: ~20 node tests of ~12 instructions per wavefront against ~80 instructions of row
+// arithmetic)  A wavefront tests all leaves of its subtree AT ONCE, one leaf per lane, against the box
+// of its 64 columns and the largest bound among them (conservative: box-to-box distance), and only the survivors get the
+// per-column test and their rows.  colbox: the box of every 64-column block, left by the seed ([B][column blocks][8]).
 // Round 5: the (leaf, column) pairs of the SPARSE leaves, one per lane.  Of the ~6 leaves of a subtree whose rows a
 // wavefront evaluates, five are in reach of only ~8 of its 64 columns (tools/diag/scan_counts.py): walking their rows for all
 // 64 lanes costs ~90 instructions per leaf = 11 per useful (leaf, column) pair, where a leaf in reach of 40 columns costs 2.
@@ -1104,7 +975,7 @@ __device__ __forceinline__ void v2v_scan_body(
         SCAN_COUNT(10);
         return;
     }
-    // lower bounds are compared as g <= bound * (1 + 1e-6): the slack of kPruneSlack on the side that changes rarely
+    // lower bounds are compared as g <= bound * (1 + 1e-6): rounding of the two sums, the slack on the side that changes rarely
     constexpr float kBoundSlack = 1.000001f;
     float reach2 = wave_max_uniform(((alive >> lane) & 1) ? c.best : 0.0f) * kBoundSlack;
     float best_s = c.best * kBoundSlack;
@@ -1286,8 +1157,8 @@ __device__ __forceinline__ void v2v_scan_body(
 template <bool kPairs>
 __global__ __launch_bounds__(64) void v2v_scan_kernel(TUCH_SCAN_PARAMS) { v2v_scan_body<0, kPairs>(TUCH_SCAN_ARGS); }
 // The same beside the inside test's chain of small kernels (another stream): at most kSlots of a SIMD's 8 wave slots, by
-// REGISTER count.  (Round 2 capped the walk with an unused LDS allocation -- 25 x 6400 B is ALL of a CU's LDS: the
-// chain's kernels that need LDS themselves, ray_near and ray_tiles_fill, then waited for the search to drain.)
+// REGISTER count, so that the chain's kernels find a slot while the search's one grid of short one-wave workgroups runs
+// (the caps that were measured, and the LDS allocation that did this before).
 template <int kSlots, bool kPairs>
 __global__ __launch_bounds__(64) void v2v_scan_shared_kernel(TUCH_SCAN_PARAMS)
 {
@@ -1312,12 +1183,7 @@ __global__ __launch_bounds__(kBlock) void v2v_tree_finalize_kernel(
     if (out_arg) out_arg[(size_t)b * V + v] = d < __builtin_inff() ? qperm[(uint32_t)k] : 0;
 }
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-struct TreeV2VLayout { size_t prow, bounds, keys, leafbox, colbox, prow_g, total; };
-
-static int flat_mode(const tuch_contact_model* m);
-int choose_v2v_frontier(const tuch_contact_model* m, int B, bool iterative = false);
+struct TreeV2VLayout { size_t prow, keys, leafbox, colbox, prow_g, total; };
 
 TreeV2VLayout tree_v2v_layout(const tuch_contact_model* m, int B)
 {
@@ -1325,7 +1191,6 @@ TreeV2VLayout tree_v2v_layout(const tuch_contact_model* m, int B)
     size_t o = 0;
     const int Vp = m->tree_qblocks * 2 * kTreeCols;
     l.prow = tuch_ws_take(o, (size_t)B * Vp * 3 * sizeof(float) + 64);
-    l.bounds = tuch_ws_take(o, (size_t)B * m->tree_nodes * 8 * sizeof(float));
     l.keys = tuch_ws_take(o, (size_t)B * Vp * sizeof(uint64_t));
     l.leafbox = tuch_ws_take(o, ((size_t)B * m->tree_leaves + 4) * 8 * sizeof(float));     // + padding
     l.colbox = tuch_ws_take(o, (size_t)B * 2 * m->tree_qblocks * 8 * sizeof(float));
@@ -1334,31 +1199,24 @@ TreeV2VLayout tree_v2v_layout(const tuch_contact_model* m, int B)
     return l;
 }
 
+// The tree search needs the tree, the mask in its order, the leaf tables (model.hip: build_tree_mask_tables) and leaf row
+// ranges that pack into a box's padding word; option v2v_tree = 0, or a model without any of these: the all-rows search.
 bool use_v2v_tree(const tuch_contact_model* m)
 {
-    if (m->tree_nodes <= 0 || !m->tree_mask_bits || !m->tree_v2v_info) return false;
+    if (m->tree_nodes <= 0 || !m->tree_mask_bits || !(m->tree_sub_leaf && m->tree_masked_leaf) || !m->tree_rows_pack) return false;
     return m->opt.v2v_tree != 0;
-}
-
-static int flat_mode(const tuch_contact_model* m)
-{
-    // 2: lanes over a subtree's leaves first (v2v_scan_kernel, the default); 0: the stackless walk (v2v_tree_kernel: models
-    // without the leaf tables, and the A/B reference).  (Rounds 2-3 also had "leaf boxes four at a time" and a matrix-core
-    // form: identical keys, both slower -- DESIGN.md section 3; removed in round 4.)
-    if (!(m->tree_sub_leaf && m->tree_masked_leaf)) return 0;
-    return m->opt.v2v_flat >= 2 ? 2 : 0;
 }
 
 int choose_v2v_frontier(const tuch_contact_model* m, int B, bool iterative)
 {
-    // option v2v_waves = 0: the form's own default -- the walks want many short wavefronts (65536: 32 subtrees at batch
-    // 64), the leaf scan tests up to 64 leaves per wavefront at once and is best with a quarter as many (measured at
-    // batch 64, step time: 7000 / 14000 / 30000 / 65536 -> 0.56+ / 0.546 / 0.550 / 0.562 ms, round 3).  Round 5, with the
+    // option v2v_waves = 0: the scan's own default -- it tests up to 64 leaves per wavefront at once and is best with a
+    // quarter of the wavefronts a node-by-node walk wants (measured at batch 64, step time:
+    // 7000 / 14000 / 30000 / 65536 -> 0.56+ / 0.546 / 0.550 / 0.562 ms, round 3).  Round 5, with the
     // sparse pairs one per lane: a caller that says its bounds are near-final (an iterative fit: the hints are the previous
     // iteration's partners) gets a quarter of that again -- fewer prologues, fuller flushes: 0.412 against 0.426 ms per
     // step at batch 64 --; on NEW bodies the search is slower that way (183 against 163 us: two subtrees per block tighten
     // poor bounds later than eight do), so that stays the default
-    const long target = m->opt.v2v_waves > 0 ? m->opt.v2v_waves : (flat_mode(m) >= 2 ? (iterative ? 3500L : 14000L) : 65536L);
+    const long target = m->opt.v2v_waves > 0 ? m->opt.v2v_waves : (iterative ? 3500L : 14000L);
     int f = 0;
     while (f + 1 < m->tree_num_frontiers &&
            (long)B * m->tree_qblocks * (m->tree_frontier_off_host[f + 1] - m->tree_frontier_off_host[f]) < target)
@@ -1422,7 +1280,7 @@ extern "C" int tuch_v2v_min_masked(const float* verts, const uint64_t* geomask_b
 }
 
 // Model-level form of tuch_v2v_min_masked (tuch/smplify/losses.py:76-78,92-93; tuch/train/loss.py:255-257,
-// 269-270): the model's mask, and -- when the model has a cluster tree -- the tree-pruned walk.
+// 269-270): the model's mask, and -- when the model has a cluster tree -- the tree-pruned search.
 extern "C" size_t tuch_v2v_model_workspace_bytes(const tuch_contact_model* m, int B)
 {
     if (!m || B <= 0) return 0;
@@ -1452,8 +1310,10 @@ extern "C" int tuch_v2v_min_model(const tuch_contact_model* m, const float* vert
     TUCH_REQUIRE(B > 0 && B <= 65535, "tuch_v2v_min_model: bad batch %d", B);
     TUCH_REQUIRE((zero_bytes & 15) == 0 && (((uintptr_t)zero) & 15) == 0 && (zero || zero_bytes == 0),
                  "tuch_v2v_min_model: the buffer to clear must be 16-byte aligned and a multiple of 16 bytes");
-    const bool fused_zero = zero && zero_bytes && use_v2v_tree(m) && flat_mode(m) >= 2 && hint_inout;
-    if (zero && zero_bytes && !fused_zero && hipMemsetAsync(zero, 0, zero_bytes, (hipStream_t)stream) != hipSuccess)
+    hipStream_t s = (hipStream_t)stream;
+    // 1. the caller's buffer: cleared by the head's one launch where there is one, else by a fill of its own
+    const bool fused_head = use_v2v_tree(m) && hint_inout;
+    if (zero && zero_bytes && !fused_head && hipMemsetAsync(zero, 0, zero_bytes, s) != hipSuccess)
         return tuch_check_launch("tuch_v2v_min_model: clearing the caller's buffer");
     if (!use_v2v_tree(m))
         return tuch_v2v_min_masked(verts, m->mask_bits, B, m->V, min_d2, argmin, workspace, workspace_bytes, stream);
@@ -1463,77 +1323,53 @@ extern "C" int tuch_v2v_min_model(const tuch_contact_model* m, const float* vert
         tuch_set_error("tuch_v2v_min_model: workspace %zu < %zu bytes", workspace_bytes, l.total);
         return TUCH_ERR_WORKSPACE;
     }
-    scope.arm(workspace, m->canary_hits, (hipStream_t)stream);
+    scope.arm(workspace, m->canary_hits, s);
     char* ws = (char*)workspace;
     float* prow = (float*)(ws + l.prow);
-    float* bounds = (float*)(ws + l.bounds);
     uint64_t* keys = (uint64_t*)(ws + l.keys);
     float* leafbox = (float*)(ws + l.leafbox);
     float* colbox = (float*)(ws + l.colbox);
-    const int scan = flat_mode(m);          // 2: lanes over leaves first, 0: the walk
-    hipStream_t s = (hipStream_t)stream;
+    float* prow_g = (float*)(ws + l.prow_g);
     const int V = m->V, Vp = m->tree_qblocks * 2 * kTreeCols, N = m->tree_nodes;
-    const TreeNode* nodes = (const TreeNode*)m->tree_node;
+    const uint64_t* bits = (const uint64_t*)m->tree_mask_bits;
+    const int32_t* qperm = (const int32_t*)m->tree_qperm;
+    // 2. head: the rows in tree order with the leaf boxes, and a first bound for every column
     const int row_blocks = ceil_div(m->tree_leaves, kBoundsBlock / 16);
-    if (scan >= 2 && hint_inout) {
-        // rows + the seed from the previous call's partners in one launch (see v2v_rows_seed_kernel)
+    if (fused_head) {
+        // from the previous call's partners, in one launch (see v2v_rows_seed_kernel)
         hipLaunchKernelGGL(v2v_rows_seed_kernel, dim3(row_blocks + ceil_div(2 * m->tree_qblocks, kBoundsBlock / 64), B),
-                           dim3(kBoundsBlock), 0, s, verts, V, Vp, (const int32_t*)m->tree_qperm, (const int32_t*)m->tree_rows,
-                           (const int32_t*)m->tree_height_off, (const int32_t*)m->tree_height_nodes, N, prow, bounds, leafbox,
-                           (const int32_t*)m->tree_leaf_group, scan >= 2 ? (float*)(ws + l.prow_g) : (float*)nullptr,
-                           m->tree_groups, row_blocks, (const uint64_t*)m->tree_mask_bits, (const int32_t*)hint_inout, keys,
-                           colbox, (uint4*)(fused_zero ? zero : nullptr),
-                           fused_zero ? zero_bytes / 16 : (size_t)0);
+                           dim3(kBoundsBlock), 0, s, verts, V, Vp, qperm, (const int32_t*)m->tree_rows,
+                           (const int32_t*)m->tree_height_off, (const int32_t*)m->tree_height_nodes, prow, leafbox,
+                           (const int32_t*)m->tree_leaf_group, prow_g, m->tree_groups, row_blocks, bits,
+                           (const int32_t*)hint_inout, keys, colbox, (uint4*)zero, zero_bytes / 16);
     } else {
-    hipLaunchKernelGGL(v2v_rows_kernel, dim3(row_blocks, B), dim3(kBoundsBlock), 0, s,
-                       verts, V, Vp, (const int32_t*)m->tree_qperm, (const int32_t*)m->tree_rows,
-                       (const int32_t*)m->tree_height_off, (const int32_t*)m->tree_height_nodes, N, prow, bounds,
-                       scan >= 2 ? leafbox : (float*)nullptr, (const int32_t*)m->tree_leaf_group,
-                       scan >= 2 ? (float*)(ws + l.prow_g) : (float*)nullptr, m->tree_groups);
-    if (scan < 2)      // (the leaf scans seed from the leaf boxes and never look at an inner node)
-        hipLaunchKernelGGL(tree_inner_bounds_kernel<4>, dim3(B), dim3(kBoundsBlock), tree_inner_bounds_lds<4>(N), s, nodes, N,
-                           (const int32_t*)m->tree_height_off, (const int32_t*)m->tree_height_nodes, m->tree_heights, bounds,
-                           (const int32_t*)m->tree_v2v_info);
-    hipLaunchKernelGGL(v2v_seed_kernel, dim3(B, 2 * m->tree_qblocks), dim3(64), 0, s, (const float*)prow, V, Vp,
-                       (const uint64_t*)m->tree_mask_bits, nodes, (const int32_t*)m->tree_rows, (const float*)bounds,
-                       (const uint64_t*)m->tree_masked, N, (const int32_t*)hint_inout, keys, scan >= 2 ? colbox : (float*)nullptr,
-                       scan >= 2 ? (const float*)leafbox : (const float*)nullptr,
-                       (const uint64_t*)m->tree_masked_leaf, m->tree_leaves);
+        // from the nearest admissible leaf, which needs the leaf boxes first: two launches
+        hipLaunchKernelGGL(v2v_rows_kernel, dim3(row_blocks, B), dim3(kBoundsBlock), 0, s, verts, V, Vp, qperm,
+                           (const int32_t*)m->tree_rows, (const int32_t*)m->tree_height_off,
+                           (const int32_t*)m->tree_height_nodes, prow, leafbox, (const int32_t*)m->tree_leaf_group, prow_g,
+                           m->tree_groups);
+        hipLaunchKernelGGL(v2v_seed_kernel, dim3(B, 2 * m->tree_qblocks), dim3(64), 0, s, (const float*)prow, V, Vp, bits,
+                           (const uint64_t*)m->tree_masked, N, keys, colbox, (const float*)leafbox,
+                           (const uint64_t*)m->tree_masked_leaf, m->tree_leaves);
     }
+    // 3. scan.  pairs: the sparse leaves' (leaf, column) pairs one per lane (needs a symmetric mask and leaves of at most
+    // 64 rows: a column's admissible rows of a leaf are one window of ITS row of the bit matrix).  leave_room: the
+    // inside test's chain runs beside the search on another stream, the scan keeps to seven wavefronts per SIMD.
+    const bool pairs = m->opt.v2v_pairs > 0 && m->mask_symmetric && m->tree_leaf_rows_max <= 64 && m->tree_groups < (1 << 24);
+    const auto scan = leave_room ? (pairs ? v2v_scan_shared_kernel<7, true> : v2v_scan_shared_kernel<7, false>)
+                                 : (pairs ? v2v_scan_kernel<true> : v2v_scan_kernel<false>);
     const int f = choose_v2v_frontier(m, B, iterative);
     const int f0 = m->tree_frontier_off_host[f], nsub = m->tree_frontier_off_host[f + 1] - f0;
-    // leave_room: an unused LDS allocation caps the walk at 25 of a CU's 32 wave slots.  The walk is one grid of 220 k
-    // short one-wave workgroups; when the inside test runs beside it on another stream -- a chain of mostly small
-    // kernels -- every slot is taken and those (and a 16 MB memset) queue behind the walk's workgroups: the chain only
-    // got going when the walk was done (tools/graph_timeline.py: the memset took 236 us).  -2.5 % step time; alone the
-    // walk is 10 % slower with the cap (0.28 -> 0.31 ms), hence a flag (TUCH_V2V_LDS: bytes, to compare).
-    const int lds_pad = leave_room && m->opt.v2v_lds > 0 ? m->opt.v2v_lds : 0;
-    if (scan == 2) {
-        // pairs: the sparse leaves' (leaf, column) pairs one per lane (needs a symmetric mask and leaves of at most 64 rows:
-        // a column's admissible rows of a leaf are one window of ITS row of the bit matrix)
-        const bool pairs = m->opt.v2v_pairs > 0 && m->mask_symmetric && m->tree_leaf_rows_max <= 64 && m->tree_groups < (1 << 24);
-        const int capped = leave_room && m->opt.v2v_lds < 0 ? -m->opt.v2v_lds : 0;       // wave slots by register count
-        void (*kernel)(const float*, int, int, const uint64_t*, const float*, const float*, const uint64_t*, const uint64_t*, int, int,
-                       const int32_t*, const int32_t*, const int32_t*, uint64_t*, const float*, const uint64_t*, int, int);
-        if (pairs) kernel = capped == 4 ? v2v_scan_shared_kernel<4, true> : capped == 5 ? v2v_scan_shared_kernel<5, true> : capped == 6 ? v2v_scan_shared_kernel<6, true>
-                            : capped ? v2v_scan_shared_kernel<7, true> : v2v_scan_kernel<true>;
-        else kernel = capped == 4 ? v2v_scan_shared_kernel<4, false> : capped == 5 ? v2v_scan_shared_kernel<5, false> : capped == 6 ? v2v_scan_shared_kernel<6, false>
-                      : capped ? v2v_scan_shared_kernel<7, false> : v2v_scan_kernel<false>;
-        hipLaunchKernelGGL(kernel, dim3(B, 2 * nsub * m->tree_qblocks), dim3(64), capped ? (size_t)0 : (size_t)lds_pad, s, (const float*)prow,
-                           V, Vp, (const uint64_t*)m->tree_mask_bits, (const float*)leafbox, (const float*)colbox,
-                           (const uint64_t*)m->tree_masked_leaf, (const uint64_t*)m->tree_masked, N, m->tree_leaves,
-                           (const int32_t*)m->tree_frontier_nodes + f0, (const int32_t*)m->tree_sub_leaf + 2 * (size_t)f0,
-                           (const int32_t*)m->tree_launch_order + (size_t)f0 * m->tree_qblocks, keys,
-                           (const float*)(ws + l.prow_g), (const uint64_t*)m->tree_mask_bits_g, m->tree_groups,
-                           std::min(m->opt.v2v_pairs, 33));       // (the queue holds 63 + 32 pairs)
-    }
-    else
-    hipLaunchKernelGGL(v2v_tree_kernel, dim3(B, 2 * nsub * m->tree_qblocks), dim3(64), (size_t)lds_pad, s, (const float*)prow, V, Vp,
-                       (const uint64_t*)m->tree_mask_bits, nodes, (const int32_t*)m->tree_rows, (const float*)bounds,
-                       (const uint64_t*)m->tree_masked, N, (const int32_t*)m->tree_frontier_nodes + f0,
-                       (const int32_t*)m->tree_launch_order + (size_t)f0 * m->tree_qblocks, keys);
+    hipLaunchKernelGGL(scan, dim3(B, 2 * nsub * m->tree_qblocks), dim3(64), 0, s, (const float*)prow, V, Vp, bits,
+                       (const float*)leafbox, (const float*)colbox, (const uint64_t*)m->tree_masked_leaf,
+                       (const uint64_t*)m->tree_masked, N, m->tree_leaves, (const int32_t*)m->tree_frontier_nodes + f0,
+                       (const int32_t*)m->tree_sub_leaf + 2 * (size_t)f0,
+                       (const int32_t*)m->tree_launch_order + (size_t)f0 * m->tree_qblocks, keys, (const float*)prow_g,
+                       (const uint64_t*)m->tree_mask_bits_g, m->tree_groups,
+                       std::min(m->opt.v2v_pairs, 33));       // (the queue holds 63 + 32 pairs)
+    // 4. finalize
     hipLaunchKernelGGL(v2v_tree_finalize_kernel, dim3(ceil_div(V, kBlock), B), dim3(kBlock), 0, s,
-                       (const uint64_t*)keys, (const int32_t*)m->tree_qperm, V, Vp, min_d2, argmin, (int32_t*)hint_inout);
+                       (const uint64_t*)keys, qperm, V, Vp, min_d2, argmin, (int32_t*)hint_inout);
     return tuch_check_launch("tuch_v2v_min_model");
 }
 

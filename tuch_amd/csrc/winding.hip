@@ -774,9 +774,6 @@ __global__ __launch_bounds__(kBlock) void segment_finalize_kernel(
 
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-// option winding_strips = 0 selects the plain per-triangle kernel (A/B measurements)
-bool use_strips(const tuch_contact_model* m) { return m->opt.winding_strips != 0; }
-
 // Number of stream chunks for the strip kernel: fill the 256 CUs x 4 SIMDs x 8 resident waves an
 // integral number of times (tail effect), keep chunks long enough to amortise the priming triple.
 int choose_strip_splits(int B, int Q, int L)
@@ -795,7 +792,7 @@ int choose_strip_splits(int B, int Q, int L)
 }
 
 struct ExteriorLayout {
-    size_t tris, partial, bounds, stats, caps, seg_tris, seg_partial, seg_count, seg_list, body_flags, ray, ray_bytes, total;
+    size_t stream, partial, bounds, stats, caps, seg_tris, seg_partial, seg_count, seg_list, body_flags, ray, ray_bytes, total;
     int lpad;
     int tree_frontier;         // frontier used by the hierarchical path (-1: flat path)
     int tree_subs;
@@ -829,18 +826,36 @@ int choose_frontier(const tuch_contact_model* m, int B)
 
 inline int strip_lpad(int L) { return ceil_div(L, 3) * 3 + 6; }
 
-int choose_splits(int B, int Q, int F);
+// The form of the body test and of the segment filter behind it: chosen once per entry point.
+enum class BodyForm { Rays, Tree, Strips };                     // ray crossings, tree walk, flat strip walk
+enum class SegmentForm { None, Fused, Rays, SolidAngles };      // no filter, one launch behind the body's rays, crossings, angles
+
+BodyForm body_form(const tuch_contact_model* m, bool want_w)
+{
+    const int ray = ray_mode(m);
+    if (ray == 2 || (ray == 1 && !want_w)) return BodyForm::Rays;
+    return use_tree(m) ? BodyForm::Tree : BodyForm::Strips;
+}
+
+SegmentForm segment_form(const tuch_contact_model* m, bool apply_segments, BodyForm body, bool want_seg_w, bool want_seg_exterior)
+{
+    if (!apply_segments || m->num_segments <= 0) return SegmentForm::None;
+    // by ray crossings under the same rule as the body test (ray_mode: when only flags are wanted, or always with
+    // TUCH_WINDING_RAY=2)
+    const int ray = ray_mode(m);
+    if (!(m->seg_link_off && (ray == 2 || (ray == 1 && !want_seg_w)))) return SegmentForm::SolidAngles;
+    // flags only, by rays, leaf-assisted: the whole segment filter is one launch behind the body test (ray_winding.hip)
+    if (body == BodyForm::Rays && !want_seg_w && !want_seg_exterior && tuch_ray_segment_fused_available(m)) return SegmentForm::Fused;
+    return SegmentForm::Rays;
+}
 
 ExteriorLayout exterior_layout(const tuch_contact_model* m, int B)
 {
     ExteriorLayout l;
     size_t o = 0;
     l.lpad = strip_lpad(m->strip_len);
-    // triangle buffer or strip stream, whichever is larger (both forms are supported)
-    const size_t tri_bytes = (size_t)B * m->F * 9 * sizeof(float);
     size_t strip_bytes = (size_t)B * l.lpad * sizeof(StreamElem);
-    int max_splits = choose_splits(B, m->V, m->F) > choose_strip_splits(B, m->V, strip_lpad(m->strip_len))
-                         ? choose_splits(B, m->V, m->F) : choose_strip_splits(B, m->V, strip_lpad(m->strip_len));
+    int max_splits = choose_strip_splits(B, m->V, l.lpad);
     l.tree_frontier = -1;
     l.tree_subs = 0;
     if (m->tree_nodes > 0) {       // sized for both paths: the switch is read per call
@@ -850,7 +865,7 @@ ExteriorLayout exterior_layout(const tuch_contact_model* m, int B)
         if (tree_bytes > strip_bytes) strip_bytes = tree_bytes;
         if (l.tree_subs > max_splits) max_splits = l.tree_subs;
     }
-    l.tris = tuch_ws_take(o, tri_bytes > strip_bytes ? tri_bytes : strip_bytes);
+    l.stream = tuch_ws_take(o, strip_bytes);          // the posed strip stream, the flat one or the tree's
     l.partial = tuch_ws_take(o, (size_t)B * max_splits * (m->V + 128) * sizeof(float));
     l.bounds = tuch_ws_take(o, (size_t)B * (m->tree_nodes > 0 ? m->tree_nodes : 1) * 2 * kSlabStride * sizeof(float));
     l.stats = tuch_ws_take(o, 256);
@@ -878,43 +893,69 @@ int choose_splits(int B, int Q, int F)
     return s;
 }
 
-// the posed strip stream of the tree (leaf strips + caps) and the slabs of every node
-void launch_tree_boxes(const tuch_contact_model* m, const float* verts, int B, StreamElem* st, float* bounds, hipStream_t s)
+// What the two walks below run over: the model's own vertices in the tree's order (tree_qperm, heavy (subtree, query
+// block) pairs first), or a caller's points [B,Q,3] with counts [B] (or nullptr) of them meaningful.
+struct WalkQueries { const float* points; int Q; const int32_t* counts; bool model_order; };
+struct WalkBuffers { StreamElem* stream; float* bounds; float* partial; };      // regions of the caller's layout
+
+// Tree walk: gather the posed stream of the tree (leaf strips + caps), the slabs of every node, walk the subtrees of
+// frontier f, reduce the partial sums (w == exterior == nullptr: the sums stay in buf.partial, tuch_winding_tree_work).
+int launch_tree_winding(const tuch_contact_model* m, const float* verts, int B, const WalkQueries& q, int f,
+                        const WalkBuffers& buf, float thresh, float* w, uint8_t* exterior, unsigned long long* stats,
+                        hipStream_t s)
 {
-    const int T = m->tree_stream_len + 3;
+    const int T = m->tree_stream_len + 3, N = m->tree_nodes;
+    const int f0 = m->tree_frontier_off_host[f], nsub = m->tree_frontier_off_host[f + 1] - f0;
+    // wavefronts of 64 queries; the model's query blocks hold 128 vertices (m->tree_qblocks of them): two wavefronts each
+    const int qblocks = q.model_order ? 2 * m->tree_qblocks : ceil_div(q.Q, kTreeQueries), stride = qblocks * kTreeQueries;
+    if (q.counts && hipMemsetAsync(buf.partial, 0, (size_t)B * nsub * stride * sizeof(float), s) != hipSuccess) {
+        tuch_set_error("winding tree walk: hipMemsetAsync failed");
+        return TUCH_ERR_HIP;
+    }
+    const TreeNode* nodes = (const TreeNode*)m->tree_node;
+    const int32_t* height_off = (const int32_t*)m->tree_height_off;
+    const int32_t* height_nodes = (const int32_t*)m->tree_height_nodes;
     hipLaunchKernelGGL(gather_stream_kernel, dim3(ceil_div(T, kBlock), B), dim3(kBlock), 0, s, verts,
-                       (const int32_t*)m->tree_vidx, (const float*)m->tree_sign, m->V, m->tree_stream_len, T, st);
-    hipLaunchKernelGGL(tree_leaf_bounds_kernel, dim3(ceil_div(m->tree_leaves, kBoundsBlock / 64), B),
-                       dim3(kBoundsBlock), 0, s, (const StreamElem*)st, T, (const TreeNode*)m->tree_node,
-                       m->tree_nodes, (const int32_t*)m->tree_height_off, (const int32_t*)m->tree_height_nodes, bounds);
-    hipLaunchKernelGGL(tree_inner_bounds_kernel<kSlabStride>, dim3(B), dim3(kBoundsBlock),
-                       tree_inner_bounds_lds<kSlabStride>(m->tree_nodes), s, (const TreeNode*)m->tree_node, m->tree_nodes,
-                       (const int32_t*)m->tree_height_off, (const int32_t*)m->tree_height_nodes, m->tree_heights,
-                       bounds);
+                       (const int32_t*)m->tree_vidx, (const float*)m->tree_sign, m->V, m->tree_stream_len, T, buf.stream);
+    hipLaunchKernelGGL(tree_leaf_bounds_kernel, dim3(ceil_div(m->tree_leaves, kBoundsBlock / 64), B), dim3(kBoundsBlock), 0, s,
+                       (const StreamElem*)buf.stream, T, nodes, N, height_off, height_nodes, buf.bounds);
+    hipLaunchKernelGGL(tree_inner_bounds_kernel<kSlabStride>, dim3(B), dim3(kBoundsBlock), tree_inner_bounds_lds<kSlabStride>(N),
+                       s, nodes, N, height_off, height_nodes, m->tree_heights, buf.bounds);
+    const int32_t* qperm = q.model_order ? (const int32_t*)m->tree_qperm : nullptr;
+    const int32_t* order = q.model_order ? (const int32_t*)m->tree_launch_order + (size_t)f0 * m->tree_qblocks : nullptr;
+    hipLaunchKernelGGL(stats ? winding_tree_kernel<true> : winding_tree_kernel<false>,
+                       dim3(B < 8 ? B : 8, nsub * qblocks, ceil_div(B, 8)), dim3(64), 0, s, q.points,
+                       (const StreamElem*)buf.stream, nodes, (const float*)buf.bounds, N,
+                       (const int32_t*)m->tree_frontier_nodes + f0,
+                       (const int32_t*)m->tree_ancestors + (size_t)f0 * kMaxAncestors, order, qperm, q.counts, q.Q, T, nsub, B,
+                       buf.partial, stats);
+    if (!w && !exterior) return TUCH_OK;
+    if (q.model_order)          // (the sums are in the tree's order)
+        hipLaunchKernelGGL(winding_finalize_tree_kernel, dim3(ceil_div(q.Q, kBlock), B), dim3(kBlock), 0, s,
+                           (const float*)buf.partial, qperm, q.Q, stride, nsub, thresh, w, exterior);
+    else
+        hipLaunchKernelGGL(winding_finalize_kernel, dim3(ceil_div(q.Q, kBlock), B), dim3(kBlock), 0, s,
+                           (const float*)buf.partial, q.Q, stride, nsub, thresh, w, exterior);
+    return TUCH_OK;
 }
 
-// gather the posed stream, box every node, walk the tree: partial sums into ws + l.partial
-void launch_tree_walk(const tuch_contact_model* m, const ExteriorLayout& l, const float* verts, int B, char* ws,
-                      unsigned long long* stats, hipStream_t s)
+// Flat strip walk: gather the posed strip stream (lpad elements), every query block against every chunk of it, reduce
+int launch_strip_winding(const tuch_contact_model* m, const float* verts, int B, const WalkQueries& q, int lpad,
+                         const WalkBuffers& buf, float thresh, float* w, uint8_t* exterior, hipStream_t s)
 {
-    StreamElem* st = (StreamElem*)(ws + l.tris);
-    const int T = m->tree_stream_len + 3;
-    float* bounds = (float*)(ws + l.bounds);
-    launch_tree_boxes(m, verts, B, st, bounds, s);
-    const int f0 = m->tree_frontier_off_host[l.tree_frontier];
-    // the model's query blocks hold 128 vertices (m->tree_qblocks of them): two wavefronts each
-    const dim3 grid(B < 8 ? B : 8, 2 * l.tree_subs * m->tree_qblocks, ceil_div(B, 8));
-    const int32_t* frontier = (const int32_t*)m->tree_frontier_nodes + f0;
-    const int32_t* ancestors = (const int32_t*)m->tree_ancestors + (size_t)f0 * kMaxAncestors;
-    const int32_t* order = (const int32_t*)m->tree_launch_order + (size_t)f0 * m->tree_qblocks;
-    if (stats)
-        hipLaunchKernelGGL(winding_tree_kernel<true>, grid, dim3(64), 0, s, verts, (const StreamElem*)st,
-                           (const TreeNode*)m->tree_node, (const float*)bounds, m->tree_nodes, frontier, ancestors, order,
-                           (const int32_t*)m->tree_qperm, (const int32_t*)nullptr, m->V, T, l.tree_subs, B, (float*)(ws + l.partial), stats);
-    else
-        hipLaunchKernelGGL(winding_tree_kernel<false>, grid, dim3(64), 0, s, verts, (const StreamElem*)st,
-                           (const TreeNode*)m->tree_node, (const float*)bounds, m->tree_nodes, frontier, ancestors, order,
-                           (const int32_t*)m->tree_qperm, (const int32_t*)nullptr, m->V, T, l.tree_subs, B, (float*)(ws + l.partial), stats);
+    const int nsplit = choose_strip_splits(B, q.Q, lpad);
+    if (q.counts && hipMemsetAsync(buf.partial, 0, (size_t)B * nsplit * q.Q * sizeof(float), s) != hipSuccess) {
+        tuch_set_error("winding strip walk: hipMemsetAsync failed");
+        return TUCH_ERR_HIP;
+    }
+    hipLaunchKernelGGL(gather_stream_kernel, dim3(ceil_div(lpad, kBlock), B), dim3(kBlock), 0, s, verts,
+                       (const int32_t*)m->strip_vidx, (const float*)m->strip_sign, m->V, m->strip_len, lpad, buf.stream);
+    const int per_split = ceil_div(ceil_div(lpad - 6, nsplit), 3) * 3;
+    hipLaunchKernelGGL(winding_strip_kernel, dim3(B, nsplit, ceil_div(q.Q, kStripQueries)), dim3(kStripBlock), 0, s,
+                       q.points, (const StreamElem*)buf.stream, q.Q, lpad, per_split, q.counts, buf.partial);
+    hipLaunchKernelGGL(winding_finalize_kernel, dim3(ceil_div(q.Q, kBlock), B), dim3(kBlock), 0, s,
+                       (const float*)buf.partial, q.Q, q.Q, nsplit, thresh, w, exterior);
+    return TUCH_OK;
 }
 
 }  // namespace
@@ -994,83 +1035,72 @@ extern "C" int tuch_exterior_flags(const tuch_contact_model* m, const float* ver
     if (tuch_ray_available(m)) scope.record(l.ray, [&] { tuch_ray_layout_touch(m, B, 0); return 0; });
     scope.arm(workspace, m->canary_hits, (hipStream_t)stream);
     char* ws = (char*)workspace;
-    float* tris = (float*)(ws + l.tris);
     hipStream_t s = (hipStream_t)stream;
+    const BodyForm body = body_form(m, w != nullptr);
+    const SegmentForm seg = segment_form(m, apply_segments != 0, body, seg_w != nullptr, seg_exterior != nullptr);
+    const WalkQueries own = {verts, m->V, nullptr, true};
+    const WalkBuffers buf = {(StreamElem*)(ws + l.stream), (float*)(ws + l.bounds), (float*)(ws + l.partial)};
+    float* caps = (float*)(ws + l.caps);
+    float* seg_tris = (float*)(ws + l.seg_tris);
+    float* seg_partial = (float*)(ws + l.seg_partial);
+    int32_t* seg_count = (int32_t*)(ws + l.seg_count);
+    int32_t* seg_list = (int32_t*)(ws + l.seg_list);
+    uint8_t* body_flags = (uint8_t*)(ws + l.body_flags);
     int rc = TUCH_OK;
-    const int ray = ray_mode(m);
-    const bool segments = apply_segments && m->num_segments > 0;
-    const bool body_by_rays = ray == 2 || (ray == 1 && !w);
-    const bool segments_by_rays = segments && m->seg_link_off && (ray == 2 || (ray == 1 && !seg_w));
-    // flags only, by rays, leaf-assisted: the whole segment filter is one launch behind the body test (ray_winding.hip)
-    const bool segments_fused = segments && segments_by_rays && body_by_rays && !seg_w && !seg_exterior &&
-                                tuch_ray_segment_fused_available(m);
-    if (segments && !segments_fused) {
-        // what the segment pass needs of the vertices alone goes first, off the critical chain behind the body test
+    // 1. what the segment pass needs of the vertices alone goes first, off the critical chain behind the body test
+    switch (seg) {
+    case SegmentForm::None:
+    case SegmentForm::Fused:
+        break;
+    case SegmentForm::Rays:
+    case SegmentForm::SolidAngles:
         if (m->num_caps > 0) {
             hipLaunchKernelGGL(cap_centroid_kernel, dim3(m->num_caps, B), dim3(64), 0, s,
                                verts, (const int32_t*)m->cap_off, (const int32_t*)m->cap_vidx, m->V,
-                               m->num_caps, (float*)(ws + l.caps), (int32_t*)(ws + l.seg_count), m->num_segments);
-        } else if (hipMemsetAsync(ws + l.seg_count, 0, (size_t)B * m->num_segments * sizeof(int32_t), s) != hipSuccess) {
+                               m->num_caps, caps, seg_count, m->num_segments);
+        } else if (hipMemsetAsync(seg_count, 0, (size_t)B * m->num_segments * sizeof(int32_t), s) != hipSuccess) {
             tuch_set_error("tuch_exterior_flags: hipMemsetAsync failed");
             return TUCH_ERR_HIP;
         }
-        if (segments_by_rays)
-            tuch_ray_segment_prepare(m, verts, (const float*)(ws + l.caps), body_by_rays && m->seg_elem_mask, B,
-                                     (float*)(ws + l.seg_tris), s);
+        if (seg == SegmentForm::Rays)
+            tuch_ray_segment_prepare(m, verts, (const float*)caps, body == BodyForm::Rays && m->seg_elem_mask, B, seg_tris, s);
+        break;
     }
-    if (body_by_rays) {
+    // 2. the body test
+    switch (body) {
+    case BodyForm::Rays:
         rc = tuch_ray_exterior_verts(m, verts, B, thresh, exterior, w, ws + l.ray, s, nullptr,
-                                     segments_fused ? (uint8_t*)(ws + l.body_flags) : (uint8_t*)nullptr);
-        if (rc != TUCH_OK) return rc;
-    } else if (use_strips(m) && use_tree(m)) {
-        launch_tree_walk(m, l, verts, B, ws, nullptr, s);
-        hipLaunchKernelGGL(winding_finalize_tree_kernel, dim3(ceil_div(m->V, kBlock), B), dim3(kBlock), 0, s,
-                           (const float*)(ws + l.partial), (const int32_t*)m->tree_qperm, m->V,
-                           2 * m->tree_qblocks * kTreeQueries, l.tree_subs, thresh, w, exterior);
-    } else if (use_strips(m) && m->strip_len > 0) {
-        StreamElem* st = (StreamElem*)tris;
-        hipLaunchKernelGGL(gather_stream_kernel, dim3(ceil_div(l.lpad, kBlock), B), dim3(kBlock), 0, s, verts,
-                           (const int32_t*)m->strip_vidx, (const float*)m->strip_sign, m->V, m->strip_len,
-                           l.lpad, st);
-        const int nsplit = choose_strip_splits(B, m->V, l.lpad);
-        const int per_split = ceil_div(ceil_div(l.lpad - 6, nsplit), 3) * 3;
-        hipLaunchKernelGGL(winding_strip_kernel, dim3(B, nsplit, ceil_div(m->V, kStripQueries)), dim3(kStripBlock),
-                           0, s, verts, (const StreamElem*)st, m->V, l.lpad, per_split, (const int32_t*)nullptr,
-                           (float*)(ws + l.partial));
-        hipLaunchKernelGGL(winding_finalize_kernel, dim3(ceil_div(m->V, kBlock), B), dim3(kBlock), 0, s,
-                           (const float*)(ws + l.partial), m->V, m->V, nsplit, thresh, w, exterior);
-    } else {
-        hipLaunchKernelGGL(gather_triangles_kernel, dim3(ceil_div(m->F * 3, kBlock), B), dim3(kBlock), 0, s,
-                           verts, (const int32_t*)m->faces, m->V, m->F, tris);
-        rc = tuch_winding_numbers(verts, tris, B, m->V, m->F, w, exterior, thresh, ws + l.partial,
-                                  l.bounds - l.partial, stream);
-        if (rc != TUCH_OK) return rc;
+                                     seg == SegmentForm::Fused ? body_flags : (uint8_t*)nullptr);
+        break;
+    case BodyForm::Tree:
+        rc = launch_tree_winding(m, verts, B, own, l.tree_frontier, buf, thresh, w, exterior, nullptr, s);
+        break;
+    case BodyForm::Strips:
+        rc = launch_strip_winding(m, verts, B, own, l.lpad, buf, thresh, w, exterior, s);
+        break;
     }
-    if (segments_fused) {
-        rc = tuch_ray_segment_flags_one(m, verts, (const uint8_t*)(ws + l.body_flags), tuch_ray_segment_counts(m, B, ws + l.ray), B, thresh,
-                                        exterior, s);
-        if (rc != TUCH_OK) return rc;
-    } else if (segments) {
-        float* caps = (float*)(ws + l.caps);
-        float* seg_tris = (float*)(ws + l.seg_tris);
-        float* seg_partial = (float*)(ws + l.seg_partial);
-        int32_t* seg_count = (int32_t*)(ws + l.seg_count);
-        int32_t* seg_list = (int32_t*)(ws + l.seg_list);
+    if (rc != TUCH_OK) return rc;
+    // 3. the segment filter: vertices interior to their own closed segment become exterior
+    // (the body's inside test, when it ran by ray crossings, has left the crossings of every vertex with the body faces
+    // of its segments: tuch_ray_segment_counts)
+    auto leaf_counts = [&] { return body == BodyForm::Rays ? tuch_ray_segment_counts(m, B, ws + l.ray) : nullptr; };
+    switch (seg) {
+    case SegmentForm::None:
+        break;
+    case SegmentForm::Fused:
+        rc = tuch_ray_segment_flags_one(m, verts, (const uint8_t*)body_flags, leaf_counts(), B, thresh, exterior, s);
+        break;
+    case SegmentForm::Rays:
+    case SegmentForm::SolidAngles: {
         const bool all = seg_w || seg_exterior;     // the detailed outputs want every segment vertex
         hipLaunchKernelGGL(segment_compact_kernel, dim3(ceil_div(m->seg_q_total, kBlock), B), dim3(kBlock), 0, s,
                            all ? (const uint8_t*)nullptr : (const uint8_t*)exterior, (const int32_t*)m->seg_of_q,
                            (const int32_t*)m->seg_q_off, (const int32_t*)m->seg_q_vidx, m->V, m->seg_q_total,
                            m->num_segments, seg_count, seg_list);
-        // by ray crossings under the same rule as the body test (ray_mode: when only flags are wanted, or always with
-        // TUCH_WINDING_RAY=2)
-        if (segments_by_rays) {
-            // the body's inside test, when it ran by ray crossings just above, has left the crossings of every vertex
-            // with the body faces of its segments
-            rc = tuch_ray_segment_flags(m, verts, caps, seg_count, seg_list,
-                                        body_by_rays ? tuch_ray_segment_counts(m, B, ws + l.ray) : nullptr, B, seg_splits(m),
-                                        thresh, seg_tris, (int32_t*)seg_partial, seg_w, seg_exterior, exterior, s);
-            if (rc != TUCH_OK) return rc;
-            return tuch_check_launch("tuch_exterior_flags");
+        if (seg == SegmentForm::Rays) {
+            rc = tuch_ray_segment_flags(m, verts, caps, seg_count, seg_list, leaf_counts(), B, seg_splits(m), thresh, seg_tris,
+                                        (int32_t*)seg_partial, seg_w, seg_exterior, exterior, s);
+            break;
         }
         hipLaunchKernelGGL(gather_segment_triangles_kernel, dim3(ceil_div(m->seg_f_total * 3, kBlock), B),
                            dim3(kBlock), 0, s, verts, (const float*)caps, (const int32_t*)m->seg_faces,
@@ -1084,7 +1114,10 @@ extern "C" int tuch_exterior_flags(const tuch_contact_model* m, const float* ver
                            (const float*)seg_partial, (const int32_t*)m->seg_of_q, (const int32_t*)m->seg_q_off,
                            (const int32_t*)m->seg_q_vidx, (const int32_t*)seg_count, (const int32_t*)seg_list,
                            m->V, m->seg_q_total, m->num_segments, seg_splits(m), thresh, seg_w, seg_exterior, exterior);
+        break;
     }
+    }
+    if (rc != TUCH_OK) return rc;
     return tuch_check_launch("tuch_exterior_flags");
 }
 
@@ -1107,7 +1140,10 @@ extern "C" int tuch_winding_tree_work(const tuch_contact_model* m, const float* 
     hipStream_t s = (hipStream_t)stream;
     unsigned long long* stats = (unsigned long long*)(ws + l.stats);
     if (hipMemsetAsync(stats, 0, 2 * sizeof(unsigned long long), s) != hipSuccess) return TUCH_ERR_HIP;
-    launch_tree_walk(m, l, verts, B, ws, stats, s);
+    const WalkQueries own = {verts, m->V, nullptr, true};
+    const WalkBuffers buf = {(StreamElem*)(ws + l.stream), (float*)(ws + l.bounds), (float*)(ws + l.partial)};
+    const int rc = launch_tree_winding(m, verts, B, own, l.tree_frontier, buf, 0.0f, nullptr, nullptr, stats, s);
+    if (rc != TUCH_OK) return rc;
     if (hipMemcpyAsync(out_host, stats, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess) {
         tuch_set_error("tuch_winding_tree_work: copy back failed");
@@ -1138,22 +1174,36 @@ extern "C" int tuch_ray_work(const tuch_contact_model* m, const float* verts, in
 // (tuch/train/loss.py:297: HD points offset along the face normals).  points [B,Q,3]; counts [B]
 // (device, optional) = number of meaningful points per body when the set is ragged and padded
 // to Q; w / exterior of padded entries are 0 / 1.
-struct PointsLayout { size_t stream, bounds, partial, total; int frontier, nsub, qblocks; };
+struct PointsLayout { size_t stream, bounds, partial, total; int frontier; };
 
 static PointsLayout points_layout(const tuch_contact_model* m, int B, int Q)
 {
     PointsLayout l;
-    l.qblocks = ceil_div(Q, kTreeQueries);
+    const int qblocks = ceil_div(Q, kTreeQueries);
     // enough wavefronts to balance the uneven subtree walks (as choose_frontier, for Q points per body)
     int f = 0;
     while (f + 1 < m->tree_num_frontiers &&
-           (long)B * l.qblocks * (m->tree_frontier_off_host[f + 1] - m->tree_frontier_off_host[f]) < 65536L) ++f;   // wavefronts
+           (long)B * qblocks * (m->tree_frontier_off_host[f + 1] - m->tree_frontier_off_host[f]) < 65536L) ++f;   // wavefronts
     l.frontier = f;
-    l.nsub = m->tree_frontier_off_host[f + 1] - m->tree_frontier_off_host[f];
+    const int nsub = m->tree_frontier_off_host[f + 1] - m->tree_frontier_off_host[f];
     size_t o = 0;
     l.stream = tuch_ws_take(o, (size_t)B * (m->tree_stream_len + 3) * sizeof(StreamElem));
     l.bounds = tuch_ws_take(o, (size_t)B * m->tree_nodes * 2 * kSlabStride * sizeof(float));
-    l.partial = tuch_ws_take(o, (size_t)B * l.nsub * l.qblocks * kTreeQueries * sizeof(float));
+    l.partial = tuch_ws_take(o, (size_t)B * nsub * qblocks * kTreeQueries * sizeof(float));
+    l.total = o;
+    return l;
+}
+
+// the flat strip walk of tuch_winding_points
+struct StripPointsLayout { size_t stream, partial, total; int lpad; };
+
+static StripPointsLayout strip_points_layout(const tuch_contact_model* m, int B, int Q)
+{
+    StripPointsLayout l;
+    l.lpad = strip_lpad(m->strip_len);
+    size_t o = 0;
+    l.stream = tuch_ws_take(o, (size_t)B * l.lpad * sizeof(StreamElem));
+    l.partial = tuch_ws_take(o, (size_t)B * choose_strip_splits(B, Q, l.lpad) * Q * sizeof(float));
     l.total = o;
     return l;
 }
@@ -1162,9 +1212,7 @@ extern "C" size_t tuch_winding_points_workspace_bytes(const tuch_contact_model* 
 {
     if (!m || B <= 0 || Q <= 0) return 0;
     tuch_ws_scope scope(m->opt.canary != 0);
-    const int lpad = strip_lpad(m->strip_len);
-    const size_t flat = align256((size_t)B * lpad * sizeof(StreamElem)) +
-                        align256((size_t)B * choose_strip_splits(B, Q, lpad) * Q * sizeof(float));
+    const size_t flat = strip_points_layout(m, B, Q).total;
     if (m->tree_nodes <= 0) return flat;
     size_t tree = points_layout(m, B, Q).total;
     const size_t ray = tuch_ray_workspace_bytes(m, B, Q);
@@ -1184,51 +1232,30 @@ extern "C" int tuch_winding_points(const tuch_contact_model* m, const float* ver
         return TUCH_ERR_WORKSPACE;
     }
     hipStream_t s = (hipStream_t)stream;
-    const int ray = ray_mode(m);
+    char* ws = (char*)workspace;
+    const WalkQueries q = {points, Q, counts, false};
     tuch_ws_scope scope(m->opt.canary != 0);
-    if (ray == 2 || (ray == 1 && !w)) {   // off-surface points: the winding number is the integer crossing count
+    int rc = TUCH_OK;
+    switch (body_form(m, w != nullptr)) {
+    case BodyForm::Rays:        // off-surface points: the winding number is the integer crossing count
         scope.record(0, [&] { tuch_ray_layout_touch(m, B, Q); return 0; });
         scope.arm(workspace, m->canary_hits, s);
         return tuch_ray_exterior_points(m, verts, points, counts, B, Q, thresh, exterior, w, workspace, s);
-    }
-    if (use_strips(m) && use_tree(m)) {
-        // hierarchical walk (cluster tree + boundary caps) with the caller's points as queries
+    case BodyForm::Tree: {      // hierarchical walk (cluster tree + boundary caps) with the caller's points as queries
         const PointsLayout l = scope.record(0, [&] { return points_layout(m, B, Q); });
         scope.arm(workspace, m->canary_hits, s);
-        char* ws = (char*)workspace;
-        StreamElem* st = (StreamElem*)(ws + l.stream);
-        float* bounds = (float*)(ws + l.bounds);
-        float* partial = (float*)(ws + l.partial);
-        const int T = m->tree_stream_len + 3, stride = l.qblocks * kTreeQueries;
-        if (counts && hipMemsetAsync(partial, 0, (size_t)B * l.nsub * stride * sizeof(float), s) != hipSuccess) {
-            tuch_set_error("tuch_winding_points: hipMemsetAsync failed");
-            return TUCH_ERR_HIP;
-        }
-        launch_tree_boxes(m, verts, B, st, bounds, s);
-        const int f0 = m->tree_frontier_off_host[l.frontier];
-        hipLaunchKernelGGL(winding_tree_kernel<false>, dim3(B < 8 ? B : 8, l.nsub * l.qblocks, ceil_div(B, 8)), dim3(64), 0, s, points,
-                           (const StreamElem*)st, (const TreeNode*)m->tree_node, (const float*)bounds, m->tree_nodes,
-                           (const int32_t*)m->tree_frontier_nodes + f0,
-                           (const int32_t*)m->tree_ancestors + (size_t)f0 * kMaxAncestors, (const int32_t*)nullptr,
-                           (const int32_t*)nullptr, counts, Q, T, l.nsub, B, partial, (unsigned long long*)nullptr);
-        hipLaunchKernelGGL(winding_finalize_kernel, dim3(ceil_div(Q, kBlock), B), dim3(kBlock), 0, s,
-                           (const float*)partial, Q, stride, l.nsub, thresh, w, exterior);
-        return tuch_check_launch("tuch_winding_points");
+        const WalkBuffers buf = {(StreamElem*)(ws + l.stream), (float*)(ws + l.bounds), (float*)(ws + l.partial)};
+        rc = launch_tree_winding(m, verts, B, q, l.frontier, buf, thresh, w, exterior, nullptr, s);
+        break;
     }
-    const int lpad = strip_lpad(m->strip_len);
-    StreamElem* st = (StreamElem*)workspace;
-    float* partial = (float*)((char*)workspace + align256((size_t)B * lpad * sizeof(StreamElem)));
-    const int nsplit = choose_strip_splits(B, Q, lpad);
-    if (counts && hipMemsetAsync(partial, 0, (size_t)B * nsplit * Q * sizeof(float), s) != hipSuccess) {
-        tuch_set_error("tuch_winding_points: hipMemsetAsync failed");
-        return TUCH_ERR_HIP;
+    case BodyForm::Strips: {
+        const StripPointsLayout l = scope.record(0, [&] { return strip_points_layout(m, B, Q); });
+        scope.arm(workspace, m->canary_hits, s);
+        const WalkBuffers buf = {(StreamElem*)(ws + l.stream), nullptr, (float*)(ws + l.partial)};
+        rc = launch_strip_winding(m, verts, B, q, l.lpad, buf, thresh, w, exterior, s);
+        break;
     }
-    hipLaunchKernelGGL(gather_stream_kernel, dim3(ceil_div(lpad, kBlock), B), dim3(kBlock), 0, s, verts,
-                       (const int32_t*)m->strip_vidx, (const float*)m->strip_sign, m->V, m->strip_len, lpad, st);
-    const int per_split = ceil_div(ceil_div(lpad - 6, nsplit), 3) * 3;
-    hipLaunchKernelGGL(winding_strip_kernel, dim3(B, nsplit, ceil_div(Q, kStripQueries)), dim3(kStripBlock), 0, s,
-                       points, (const StreamElem*)st, Q, lpad, per_split, counts, partial);
-    hipLaunchKernelGGL(winding_finalize_kernel, dim3(ceil_div(Q, kBlock), B), dim3(kBlock), 0, s,
-                       (const float*)partial, Q, Q, nsplit, thresh, w, exterior);
+    }
+    if (rc != TUCH_OK) return rc;
     return tuch_check_launch("tuch_winding_points");
 }

@@ -1124,11 +1124,9 @@ class ContactModel:
         self._h = None
         self._faces_i32 = None
         # host-side switches, read from the environment once (like the library's own, tuch_contact_model_set_option):
-        # overlap = search on a second stream beside the inside test, v2v_hint = partner hints kept between calls,
-        # inside_first = the inside test's chain is enqueued before the search
+        # overlap = search on a second stream beside the inside test, v2v_hint = partner hints kept between calls
         self._py_options = {'overlap': int(os.environ.get('TUCH_OVERLAP', '1') != '0'),
-                            'v2v_hint': int(os.environ.get('TUCH_V2V_HINT', '1') != '0'),
-                            'inside_first': int(os.environ.get('TUCH_INSIDE_FIRST', '1') != '0')}
+                            'v2v_hint': int(os.environ.get('TUCH_V2V_HINT', '1') != '0')}
         self._pending_options = {}
 
     @property
@@ -1231,8 +1229,7 @@ class ContactModel:
         # the search's 55 k one-wave workgroups and only get going when it is done (eager: ray_leaf_bounds 119 us
         # instead of 14; replayed graph at batch 8: 0.240 against 0.213 ms once tree_inner_bounds_kernel no longer
         # delays the search's start).
-        first = not overlap or self._py_options.get('inside_first', 0)
-        exterior = self.exterior_flags(verts, apply_segments=apply_segments) if first else None
+        exterior = self.exterior_flags(verts, apply_segments=apply_segments)
         with (torch.cuda.stream(side) if overlap else contextlib.nullcontext()):
             if overlap and zero is not None:
                 zero.record_stream(side)
@@ -1240,8 +1237,6 @@ class ContactModel:
             # (the caller's extra work -- region pairs, reprojection + prior -- FIRST, beside the short head of the inside
             # test's chain, was measured: 0.587 against 0.552 ms per step; it delays the search, which the chain waits for)
             extra = call_also()
-        if not first:
-            exterior = self.exterior_flags(verts, apply_segments=apply_segments)
         if overlap:
             cur.wait_stream(side)
             for t in (mn, partner, *(extra if isinstance(extra, (tuple, list)) else (extra,))):
