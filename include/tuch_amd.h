@@ -385,6 +385,24 @@ int tuch_closest_point(const tuch_contact_model* model, const float* verts /* [B
                        const float* points /* [B,Q,3] */, const int32_t* counts /* [B] or NULL */, int B, int Q,
                        float* d2 /* [B,Q] */, int32_t* face /* [B,Q] */, float* bary /* [B,Q,3] */,
                        void* workspace, size_t workspace_bytes, void* stream);
+/* The same search with a hint: tuch_closest_point's arguments plus hint [B,Q] device ints or NULL (NULL: exactly
+ * tuch_closest_point).  hint[b,q] names a face that is probably the answer -- in a fitting loop the face the previous
+ * iteration returned.  It is only a bound: d2, face and bary equal tuch_closest_point's bit for bit for EVERY content
+ * of hint (the right face, a wrong one, -1, F, INT32_MAX, INT32_MIN, any mix within a wavefront).  A hint in [0, F) --
+ * checked before it is used as an address -- makes the query start from that face's exact distance and group instead
+ * of from the walk over every box of the body; any other value, or a hinted face whose distance is not finite (NaN
+ * vertices), takes tuch_closest_point's path.  hint may alias the face output: a lane reads its own hint before it
+ * writes its face, so a loop can keep one [B,Q] tensor that is both.  Workspace as for tuch_closest_point. */
+int tuch_closest_point_hinted(const tuch_contact_model* model, const float* verts /* [B,V,3] */,
+                              const float* points /* [B,Q,3] */, const int32_t* counts /* [B] or NULL */,
+                              const int32_t* hint /* [B,Q] or NULL */, int B, int Q, float* d2 /* [B,Q] */,
+                              int32_t* face /* [B,Q] */, float* bary /* [B,Q,3] */, void* workspace,
+                              size_t workspace_bytes, void* stream);
+/* The face groups the search walks, as host copies (any may be NULL): *num_groups = G, group_off_host [G+1],
+ * face_list_host [F] (the faces of group g are face_list[group_off[g] .. group_off[g+1])), face_group_host [F] (the
+ * group of every face: the inverse of face_list, where a hinted query starts). */
+int tuch_contact_model_face_groups(const tuch_contact_model* model, int* num_groups, int32_t* group_off_host,
+                                   int32_t* face_list_host, int32_t* face_group_host);
 /* Its adjoint in the envelope form (the weights held fixed: exact wherever the closest feature is locally constant):
  * grad_points [B,Q,3] = 2 g (p - c) is WRITTEN (0 for padded entries and face = -1, which contribute nothing), and
  * -2 g bary[k] (p - c) is added to the rows of the winning face's three corners -- with grad_verts_fixed_zeroed
@@ -396,6 +414,30 @@ int tuch_closest_point_bwd(const tuch_contact_model* model, const float* verts, 
                            float* grad_points /* [B,Q,3] written, or NULL */,
                            void* grad_verts_fixed_zeroed /* B*V*3 zeroed 64-bit words, or NULL */,
                            float* grad_verts /* [B,V,3], or NULL */, void* stream);
+
+/* Point-to-surface data term of a fit to unregistered points (csrc/scan_fit.hip).  The queries are points[b,q] -
+ * transl[b] (one float32 subtraction per component) against the model's mesh posed by verts[b]: d2, face, bary are
+ * those of tuch_closest_point_hinted on these queries, bit for bit (counts, hint and its aliasing with face as there).
+ *   per_body[b] = sum_{q < counts[b]} w_q rho(d2_q) / sum_{q < counts[b]} w_q,   total[0] = sum_b per_body[b],
+ * with weights [B,Q] or NULL (all ones) and rho = 0: d2;  1: sqrt(d2), derivative 0 at d2 = 0;  2: sigma^2 d2 /
+ * (sigma^2 + d2) (sigma > 0; ignored otherwise).  A point of weight 0 is not computed from and may be non-finite; a
+ * body whose weights sum to 0 or with counts[b] = 0 has per_body = 0 and zero gradient rows.
+ *   The gradients of total for a unit upstream gradient, the weights of the nearest point held fixed, with g_q = w_q
+ * rho'(d2_q) / sum w and r = (p - t) - c: grad_points [B,Q,3] = 2 g r (or NULL), the rows of the winning face's corners
+ * in grad_verts [B,V,3] get -2 g bary_k r, grad_transl [B,3] = -sum_q 2 g r.  grad_verts is zeroed by the call and
+ * summed with float atomics, or, under tuch_set_deterministic(1), as 64-bit fixed-point integers in the workspace
+ * (the same bits on every call); per_body, its normaliser, total and grad_transl are fixed-order sums in both modes.
+ * ticket: one int, zero before the first call and left zero by every call.  No allocation, no synchronisation,
+ * capturable; the workspace is guarded under option canary. */
+size_t tuch_scan_fit_workspace_bytes(const tuch_contact_model* model, int B, int Q);
+int tuch_scan_fit_terms(const tuch_contact_model* model, const float* verts /* [B,V,3] */,
+                        const float* transl /* [B,3] */, const float* points /* [B,Q,3] */,
+                        const int32_t* counts /* [B] or NULL */, const float* weights /* [B,Q] or NULL */,
+                        const int32_t* hint /* [B,Q] or NULL */, int B, int Q, int rho, float sigma,
+                        float* d2 /* [B,Q] */, int32_t* face /* [B,Q] */, float* bary /* [B,Q,3] */, int* ticket,
+                        float* per_body /* [B] */, float* total /* [1] */, float* grad_verts /* [B,V,3] */,
+                        float* grad_transl /* [B,3] */, float* grad_points /* [B,Q,3] or NULL */, void* workspace,
+                        size_t workspace_bytes, void* stream);
 
 /* region-pair minima: TUCH.contact_from_verts, train_module.py:69-91 (select NULL, unmasked)
  * and the region-to-region term, losses.py:107-117 (select = gt_contact & has_discrete_contact,

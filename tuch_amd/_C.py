@@ -116,6 +116,11 @@ _SIGNATURES = {
     'tuch_closest_point': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_size_t, c_void_p]),
     'tuch_closest_point_bwd': (c_int, [c_void_p] * 6 + [c_int, c_int] + [c_void_p] * 4),
+    'tuch_closest_point_hinted': (c_int, [c_void_p] * 5 + [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                          c_void_p]),
+    'tuch_contact_model_face_groups': (c_int, [c_void_p, POINTER(c_int), c_void_p, c_void_p, c_void_p]),
+    'tuch_scan_fit_workspace_bytes': (c_size_t, [c_void_p, c_int, c_int]),
+    'tuch_scan_fit_terms': (c_int, [c_void_p] * 7 + [c_int, c_int, c_int, c_float] + [c_void_p] * 10 + [c_size_t, c_void_p]),
     'tuch_contact_terms_ragged_fwd': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p,
                                               c_void_p]),
     'tuch_contact_terms_ragged_bwd': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float,

@@ -1,5 +1,5 @@
-// Closest point on the posed surface for arbitrary query points (tuch_closest_point, include/tuch_amd.h), its adjoint
-// and the face groups it walks.
+// Closest point on the posed surface for arbitrary query points (tuch_closest_point and tuch_closest_point_hinted,
+// include/tuch_amd.h; tuch_cp_search for scan_fit.hip), its adjoint and the face groups it walks.
 //
 // Two launches:
 //   cp_group_bounds_kernel  per (body, group): the posed corners of the group's faces, gathered in group order
@@ -27,6 +27,19 @@
 //     lb(g) - 64 u far(g)  <=  computed d2(f)  <=  far(g) (1 + 64 u),
 // and a group is skipped for a lane only when lb(g) - 64 u far(g) is GREATER than the lane's bound (the best computed
 // d2 so far, at the start min_g far(g) (1 + 64 u)): no face of it can produce a key that is smaller or equal.
+//
+// The hinted start (tuch_closest_point_hinted).  hint [B,Q] names, per query, a face that is probably the answer -- in
+// a fitting loop the previous iteration's.  The hint is only a bound: a lane whose hint is a face index in [0, F)
+// (checked before it addresses anything) runs cp_eval on that face's posed corners and enters the result as an
+// ordinary key; its bound starts at that exact d2, its seed is the face's group (cp_face_group, the inverse of
+// cp_face_list), and it takes no part in sweep 1, which is skipped when no lane of the wavefront needs it.  The key is
+// a computed key of a face, one the full sweep computes too, so it cannot undercut the full sweep's minimum, and
+// lb(g) - 64 u far(g) <= bound still admits every group that can hold a smaller or equal key: a face with a smaller
+// d2, or with equal bits and a smaller index, has computed d2 <= bound and by the inequality above makes its group's
+// lb - 64 u far <= bound.  A lane whose hint is out of range, or whose hinted d2 is not finite (a NaN bound would
+// compare false with everything and admit nothing), takes the unhinted path.  So the outputs equal the unhinted
+// call's bit for bit for every content of hint.  hint may alias the face output: a lane reads only its own entry, and
+// before it writes its face (a wholly padded block writes without reading).
 #include "model.h"
 #include "workspace.h"
 
@@ -237,12 +250,29 @@ static __device__ __forceinline__ unsigned long long cp_test_group(float px, flo
     return key;
 }
 
-__global__ __launch_bounds__(64) void cp_search_kernel(const float* __restrict__ points, const int32_t* __restrict__ counts,
+// the posed corners of face f (in [0, F)) of one body, as cp_eval takes them
+static __device__ __forceinline__ void cp_face_corners(const int32_t* __restrict__ faces, const float* __restrict__ body_verts, int V,
+                                                       int f, float* t)
+{
+    for (int k = 0; k < 3; ++k) {
+        const int vi = cp_clamp_index(faces[(size_t)f * 3 + k], V);
+        const float* x = body_verts + (size_t)vi * 3;
+        t[3 * k] = x[0]; t[3 * k + 1] = x[1]; t[3 * k + 2] = x[2];
+    }
+}
+
+// kHinted: hint [B,Q] is read (file header: the hinted start); hint and out_face may be the same memory, so neither is
+// __restrict__.  Without it the kernel is the unhinted search, instruction for instruction.
+// shift [B,3] or nullptr: the query is points - shift[b], one float32 subtraction per component (scan_fit.hip: the
+// scan in the frame of the untranslated mesh); p - 0 has p's bits.
+template <bool kHinted>
+__global__ __launch_bounds__(64) void cp_search_kernel(const float* __restrict__ points, const float* __restrict__ shift,
+                                                      const int32_t* __restrict__ counts, const int32_t* hint, const int32_t* __restrict__ face_group,
                                                       const float* __restrict__ boxes, const float* __restrict__ tris,
                                                       const int32_t* __restrict__ group_off, const int32_t* __restrict__ face_list,
                                                       const int32_t* __restrict__ faces, const float* __restrict__ verts,
                                                       int V, int F, int G, int Q, float* __restrict__ out_d2,
-                                                      int32_t* __restrict__ out_face, float* __restrict__ out_bary)
+                                                      int32_t* out_face, float* __restrict__ out_bary)
 {
     __shared__ float s_tri[2][kCpGroupFaces * kCpTri];
     __shared__ int32_t s_fid[2][kCpGroupFaces];
@@ -267,20 +297,40 @@ __global__ __launch_bounds__(64) void cp_search_kernel(const float* __restrict__
     if (active) {
         const float* p = points + ((size_t)b * Q + q) * 3;
         px = p[0]; py = p[1]; pz = p[2];
+        if (shift) { px -= shift[3 * b]; py -= shift[3 * b + 1]; pz -= shift[3 * b + 2]; }
     }
     const float* box = boxes + (size_t)b * G * kCpBox;
     const float* body_tris = tris + (size_t)b * F * kCpTri;
-    // sweep 1: an upper bound of the answer, and the group that gives it (this lane's seed)
-    float ub = __builtin_huge_valf();
+    // the hinted start: the hinted face's own key, its exact d2 as the bound, its group as the seed
+    unsigned long long key = kCpNoKey;
+    bool hinted = false;
     int seed = -1;
-    for (int g = 0; g < G; ++g) {
-        float lb, far;
-        cp_box(px, py, pz, box + (size_t)g * kCpBox, lb, far);
-        if (far < ub) { ub = far; seed = g; }
+    if (kHinted && active) {
+        const int h = hint[(size_t)b * Q + q];
+        if (h >= 0 && h < F) {
+            const int hg = face_group[h];
+            float t[kCpTri], v, w;
+            cp_face_corners(faces, verts + (size_t)b * V * 3, V, h, t);
+            const float d = cp_eval(px, py, pz, t, v, w);
+            if (hg >= 0 && hg < G && d < __builtin_huge_valf()) {       // (false for a NaN d: that lane falls back)
+                hinted = true;
+                seed = hg;
+                key = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)h;
+            }
+        }
     }
+    // sweep 1: an upper bound of the answer, and the group that gives it (this lane's seed); not for a hinted lane, and
+    // not at all where every query of the wavefront is hinted
+    float ub = __builtin_huge_valf();
+    if (!kHinted || __ballot(active && !hinted) != 0ull)
+        for (int g = 0; g < G; ++g) {
+            float lb, far;
+            cp_box(px, py, pz, box + (size_t)g * kCpBox, lb, far);
+            if (far < ub && !(kHinted && hinted)) { ub = far; seed = g; }
+        }
     // a lane without a query admits nothing (its bound is below every lb - margin, NaN included)
     float bound = active ? __builtin_fmaf(ub, kCpMargin, ub) : -__builtin_huge_valf();
-    unsigned long long key = kCpNoKey;
+    if (kHinted && hinted) bound = __uint_as_float((unsigned)(key >> 32));
     int buf = 0, first = 0, n = 0;
     CpStage r;
     // The seeds first: the box bound alone is the size of a group, and a lane that met its near groups late in the
@@ -338,11 +388,7 @@ __global__ __launch_bounds__(64) void cp_search_kernel(const float* __restrict__
     } else {
         // the winner's weights: the same sequence on the same corners
         float t[kCpTri], v, w;
-        for (int k = 0; k < 3; ++k) {
-            const int vi = cp_clamp_index(faces[(size_t)face * 3 + k], V);
-            const float* x = verts + ((size_t)b * V + vi) * 3;
-            t[3 * k] = x[0]; t[3 * k + 1] = x[1]; t[3 * k + 2] = x[2];
-        }
+        cp_face_corners(faces, verts + (size_t)b * V * 3, V, face, t);
         cp_eval(px, py, pz, t, v, w);
         b1 = v;
         b2 = w;
@@ -418,17 +464,20 @@ extern "C" size_t tuch_closest_point_workspace_bytes(const tuch_contact_model* m
     return cp_layout(m, B).total;
 }
 
-extern "C" int tuch_closest_point(const tuch_contact_model* m, const float* verts, const float* points, const int32_t* counts,
-                                  int B, int Q, float* d2, int32_t* face, float* bary, void* workspace, size_t workspace_bytes,
-                                  void* stream)
+// every entry point that searches (scan_fit.hip's too): `name` is the one the errors speak of; hint == nullptr launches
+// the unhinted instantiation, shift == nullptr leaves the points as they are
+int tuch_cp_search(const char* name, const tuch_contact_model* m, const float* verts, const float* points, const float* shift,
+                   const int32_t* counts, const int32_t* hint, int B, int Q, float* d2, int32_t* face, float* bary,
+                   void* workspace, size_t workspace_bytes, void* stream)
 {
-    TUCH_REQUIRE(m && verts && points && d2 && face && bary, "tuch_closest_point: null pointer");
-    TUCH_REQUIRE(B >= 0 && B <= 65535 && Q >= 0, "tuch_closest_point: bad sizes B=%d Q=%d", B, Q);
+    TUCH_REQUIRE(m && verts && points && d2 && face && bary, "%s: null pointer", name);
+    TUCH_REQUIRE(B >= 0 && B <= 65535 && Q >= 0, "%s: bad sizes B=%d Q=%d", name, B, Q);
     if (B == 0 || Q == 0) return TUCH_OK;
-    TUCH_REQUIRE(m->cp_groups > 0 && m->cp_group_off && m->cp_face_list, "tuch_closest_point: the model has no face groups");
+    TUCH_REQUIRE(m->cp_groups > 0 && m->cp_group_off && m->cp_face_list && m->cp_face_group, "%s: the model has no face groups",
+                 name);
     const size_t need = tuch_closest_point_workspace_bytes(m, B, Q);
     if (!workspace || workspace_bytes < need) {
-        tuch_set_error("tuch_closest_point: workspace %zu < %zu bytes", workspace_bytes, need);
+        tuch_set_error("%s: workspace %zu < %zu bytes", name, workspace_bytes, need);
         return TUCH_ERR_WORKSPACE;
     }
     hipStream_t s = (hipStream_t)stream;
@@ -440,10 +489,27 @@ extern "C" int tuch_closest_point(const tuch_contact_model* m, const float* vert
     const int G = m->cp_groups;
     hipLaunchKernelGGL(cp_group_bounds_kernel, dim3(G, B), dim3(64), 0, s, verts, (const int32_t*)m->faces,
                        (const int32_t*)m->cp_face_list, (const int32_t*)m->cp_group_off, m->V, m->F, G, boxes, tris);
-    hipLaunchKernelGGL(cp_search_kernel, dim3(ceil_div(Q, 64), B), dim3(64), 0, s, points, counts, (const float*)boxes,
-                       (const float*)tris, (const int32_t*)m->cp_group_off, (const int32_t*)m->cp_face_list,
-                       (const int32_t*)m->faces, verts, m->V, m->F, G, Q, d2, face, bary);
-    return tuch_check_launch("tuch_closest_point");
+    hipLaunchKernelGGL(hint ? cp_search_kernel<true> : cp_search_kernel<false>, dim3(ceil_div(Q, 64), B), dim3(64), 0, s, points,
+                       shift, counts, hint, (const int32_t*)m->cp_face_group, (const float*)boxes, (const float*)tris,
+                       (const int32_t*)m->cp_group_off, (const int32_t*)m->cp_face_list, (const int32_t*)m->faces, verts, m->V,
+                       m->F, G, Q, d2, face, bary);
+    return tuch_check_launch(name);
+}
+
+extern "C" int tuch_closest_point(const tuch_contact_model* m, const float* verts, const float* points, const int32_t* counts,
+                                  int B, int Q, float* d2, int32_t* face, float* bary, void* workspace, size_t workspace_bytes,
+                                  void* stream)
+{
+    return tuch_cp_search("tuch_closest_point", m, verts, points, nullptr, counts, nullptr, B, Q, d2, face, bary, workspace, workspace_bytes,
+                     stream);
+}
+
+extern "C" int tuch_closest_point_hinted(const tuch_contact_model* m, const float* verts, const float* points,
+                                         const int32_t* counts, const int32_t* hint, int B, int Q, float* d2, int32_t* face,
+                                         float* bary, void* workspace, size_t workspace_bytes, void* stream)
+{
+    return tuch_cp_search("tuch_closest_point_hinted", m, verts, points, nullptr, counts, hint, B, Q, d2, face, bary, workspace,
+                     workspace_bytes, stream);
 }
 
 extern "C" int tuch_closest_point_bwd(const tuch_contact_model* m, const float* verts, const float* points, const int32_t* face,

@@ -110,6 +110,15 @@ extern "C" int tuch_winding_points(const tuch_contact_model* m, const float* ver
                                    const int32_t* counts, int B, int Q, float thresh, float* w,
                                    uint8_t* exterior, void* workspace, size_t workspace_bytes, void* stream);
 
+// The closest-point search behind every entry point that needs it (closest_point.hip): queries points [B,Q,3] - shift[b]
+// (shift [B,3] or nullptr), hint [B,Q] or nullptr (may alias face); `name` is the entry point the errors speak of.
+extern "C" size_t tuch_closest_point_workspace_bytes(const tuch_contact_model* m, int B, int Q);
+int tuch_cp_search(const char* name, const tuch_contact_model* m, const float* verts, const float* points, const float* shift,
+                   const int32_t* counts, const int32_t* hint, int B, int Q, float* d2, int32_t* face, float* bary,
+                   void* workspace, size_t workspace_bytes, void* stream);
+// rho of tuch_scan_fit_terms (scan_fit.hip), as include/tuch_amd.h numbers them
+enum { TUCH_SCAN_RHO_SQUARED = 0, TUCH_SCAN_RHO_DISTANCE = 1, TUCH_SCAN_RHO_GMOF = 2 };
+
 struct tuch_contact_model {
     tuch_tables tables;        // owns every device table below
     tuch_options opt;
@@ -166,6 +175,7 @@ struct tuch_contact_model {
     int cp_groups;
     int32_t* cp_group_off;     // [cp_groups + 1]
     int32_t* cp_face_list;     // [F]
+    int32_t* cp_face_group;    // [F] the group of every face (the inverse of cp_face_list): the seed of a hinted query
     // ordered one-ring of every vertex (closed manifold meshes only, else nullptr): ring_vidx[ring_off[v] + j] = r_j
     // with the faces around v being (v, r_j, r_{j+1}) in their own orientation, j cyclic (ray_winding.hip)
     int32_t* ring_off;         // [V+1]

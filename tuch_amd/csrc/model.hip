@@ -80,7 +80,7 @@ int build_strip_tables(tuch_contact_model* m, const int32_t* faces)
 }
 
 // Face groups of the closest-point query: the faces ordered by their leaf (index order within a leaf; without a tree
-// every face counts as leaf 0), cut wherever the leaf changes or a group has 64 faces.
+// every face counts as leaf 0), cut wherever the leaf changes or a group has 64 faces; and the group of every face.
 void build_closest_point_tables(tuch_contact_model* m)
 {
     const int F = m->F, kGroup = 64;
@@ -92,8 +92,12 @@ void build_closest_point_tables(tuch_contact_model* m)
         if (i == 0 || i - off.back() == kGroup || (!leaf.empty() && leaf[list[i]] != leaf[list[i - 1]])) off.push_back(i);
     m->cp_groups = (int)off.size();
     off.push_back(F);
+    std::vector<int32_t> group(F);
+    for (int g = 0; g + 1 < (int)off.size(); ++g)
+        for (int i = off[g]; i < off[g + 1]; ++i) group[list[i]] = g;
     m->tables.put(&m->cp_face_list, list.data(), list.size());
     m->tables.put(&m->cp_group_off, off.data(), off.size());
+    m->tables.put(&m->cp_face_group, group.data(), group.size());
 }
 
 // do the leaves' strip runs tile the exact part of the stream?  (ray_winding.hip poses the strip leaf by leaf)
@@ -590,6 +594,22 @@ extern "C" int tuch_contact_model_tree_order(const tuch_contact_model* m, int32_
     TUCH_REQUIRE(m->tree_nodes > 0, "tuch_contact_model_tree_order: the model has no cluster tree");
     if (qperm_host) memcpy(qperm_host, m->tree_qperm_host.data(), sizeof(int32_t) * m->V);
     if (face_leaf_host) memcpy(face_leaf_host, m->tree_face_leaf_host.data(), sizeof(int32_t) * m->F);
+    return TUCH_OK;
+}
+
+extern "C" int tuch_contact_model_face_groups(const tuch_contact_model* m, int* num_groups, int32_t* group_off_host,
+                                              int32_t* face_list_host, int32_t* face_group_host)
+{
+    TUCH_REQUIRE(m, "tuch_contact_model_face_groups: null model");
+    TUCH_REQUIRE(m->cp_groups > 0 && m->cp_group_off && m->cp_face_list && m->cp_face_group,
+                 "tuch_contact_model_face_groups: the model has no face groups");
+    if (num_groups) *num_groups = m->cp_groups;
+    if (group_off_host && tuch_table_download(group_off_host, m->cp_group_off, sizeof(int32_t) * (m->cp_groups + 1)) != TUCH_OK)
+        return TUCH_ERR_HIP;
+    if (face_list_host && tuch_table_download(face_list_host, m->cp_face_list, sizeof(int32_t) * m->F) != TUCH_OK)
+        return TUCH_ERR_HIP;
+    if (face_group_host && tuch_table_download(face_group_host, m->cp_face_group, sizeof(int32_t) * m->F) != TUCH_OK)
+        return TUCH_ERR_HIP;
     return TUCH_OK;
 }
 

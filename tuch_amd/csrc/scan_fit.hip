@@ -1,0 +1,269 @@
+// The data term of a fit to unregistered points (tuch_scan_fit_terms, include/tuch_amd.h): for every real point of a scan
+// the nearest point of the posed, translated mesh, a robust function of its squared distance, the bodies' weighted means,
+// their total, and the unit gradients w.r.t. vertices, translation and points.
+//
+// Launches: the two of the closest-point search (closest_point.hip; the queries are points - transl, subtracted by the
+// search itself), scan_zero_kernel on the gradient accumulator (a kernel, not a memset: a captured loop then holds kernel
+// nodes only), scan_term_kernel, and in deterministic mode the conversion of the fixed-point sums: 4 or 5.
+//
+//   scan_term_kernel   one point per thread, 256 per workgroup.  Every workgroup first adds up its body's weights in one
+//                      fixed order (the normaliser: the same bits in every workgroup of the body, alone or in a batch),
+//                      then g_q = w_q rho'(d2_q) / sum w and r = (p - t) - c with c = sum_k bary_k x_k:
+//                        grad_points = 2 g r,  rows of the winning face's corners += -2 g bary_k r  (64-bit fixed-point
+//                        integer atomics in deterministic mode, float atomics otherwise),  grad_transl = -sum_q 2 g r.
+//                      The per-body sums (loss, normaliser, grad_transl) cross to the workgroup that arrives last by
+//                      mesh_fit.hip's ticket scheme and are added in chunk order there, the total in a fixed tree: no
+//                      float atomics for them in either mode.
+//
+// A point of weight 0 is not computed from (it may be non-finite); neither is one the search found no face for (a body
+// with non-finite vertices).  A body without weight (counts[b] = 0, or all weights 0) has loss 0 and zero gradient rows.
+#include "model.h"
+#include "workspace.h"
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kWaves = kBlock / 64;
+constexpr int kPart = 8;                 // floats per partial: sum w rho, -sum e.xyz, sum w, 3 unused
+
+typedef __attribute__((address_space(1))) float gfloat;
+
+struct ScanLayout { size_t search, fixed, partial, total; };
+
+ScanLayout scan_layout(const tuch_contact_model* m, int B, int Q)
+{
+    ScanLayout l;
+    size_t o = 0;
+    // (the search guards its own regions: its layout is recorded by its own scope at this offset)
+    l.search = tuch_ws_take(o, tuch_closest_point_workspace_bytes(m, B, Q), false);
+    l.fixed = tuch_ws_take(o, (size_t)B * m->V * 3 * sizeof(long long));
+    l.partial = tuch_ws_take(o, (size_t)B * ceil_div(Q, kBlock) * kPart * sizeof(float));
+    l.total = o;
+    return l;
+}
+
+static __device__ __forceinline__ int clamp_index(int i, int n) { return i < 0 ? 0 : (i >= n ? n - 1 : i); }
+
+// Sum over the 64 lanes, valid in lane 0, in a fixed order.
+static __device__ __forceinline__ float wave_sum(float v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;
+}
+
+// rho(d2) and its derivative.  'distance' has derivative 0 at d2 = 0 (vertex_fit's convention: torch.norm's subgradient).
+static __device__ __forceinline__ void scan_rho(int rho, float sigma2, float d2, float& value, float& slope)
+{
+    if (rho == TUCH_SCAN_RHO_SQUARED) {
+        value = d2;
+        slope = 1.0f;
+    } else if (rho == TUCH_SCAN_RHO_DISTANCE) {
+        value = __builtin_sqrtf(d2);
+        slope = value > 0.0f ? 0.5f / value : 0.0f;
+    } else {
+        const float q = sigma2 / (sigma2 + d2);
+        value = q * d2;
+        slope = q * q;
+    }
+}
+
+template <bool kFixed>
+__global__ __launch_bounds__(kBlock) void scan_term_kernel(
+    const float* __restrict__ verts, const float* __restrict__ transl, const float* __restrict__ points,
+    const int32_t* __restrict__ counts, const float* __restrict__ weights, const float* __restrict__ d2,
+    const int32_t* __restrict__ face, const float* __restrict__ bary, const int32_t* __restrict__ faces, int B, int V, int F,
+    int Q, int rho, float sigma2, float* partial, int* ticket, float* __restrict__ per_body, float* __restrict__ total,
+    float* __restrict__ grad_points, float* __restrict__ grad_verts, long long* __restrict__ grad_fixed,
+    float* __restrict__ grad_transl)
+{
+    __shared__ float red[kWaves][4];
+    __shared__ float s_wsum;
+    __shared__ float tree[kBlock];
+    __shared__ bool last;
+    const int c = blockIdx.x, b = blockIdx.y, t = threadIdx.x, chunks = gridDim.x;
+    int count = Q;
+    if (counts) {
+        count = counts[b];
+        count = count < 0 ? 0 : (count > Q ? Q : count);
+    }
+    // the normaliser: this body's weights in one fixed order
+    float wsum = (float)count;
+    if (weights) {
+        float acc = 0.0f;
+        for (int i = t; i < count; i += kBlock) acc += weights[(size_t)b * Q + i];
+        acc = wave_sum(acc);
+        if ((t & 63) == 0) red[t >> 6][0] = acc;
+        __syncthreads();
+        if (t == 0) {
+            float a = red[0][0];
+#pragma unroll
+            for (int j = 1; j < kWaves; ++j) a += red[j][0];
+            s_wsum = a;
+        }
+        __syncthreads();
+        wsum = s_wsum;
+        __syncthreads();                                      // (red is written again below)
+    }
+    const int q = c * kBlock + t;
+    float s = 0.0f, ex = 0.0f, ey = 0.0f, ez = 0.0f;
+    if (q < count) {
+        const size_t o = (size_t)b * Q + q;
+        const float w = weights ? weights[o] : 1.0f;
+        const int f = face[o];
+        if (w != 0.0f && wsum != 0.0f && f >= 0 && f < F) {
+            float value, slope;
+            scan_rho(rho, sigma2, d2[o], value, slope);
+            s = w * value;
+            const float g2 = 2.0f * (w * slope / wsum);
+            const float bw[3] = {bary[o * 3], bary[o * 3 + 1], bary[o * 3 + 2]};
+            int vi[3];
+            float cx = 0.0f, cy = 0.0f, cz = 0.0f;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                vi[k] = clamp_index(faces[(size_t)f * 3 + k], V);
+                const float* x = verts + ((size_t)b * V + vi[k]) * 3;
+                cx = __builtin_fmaf(bw[k], x[0], cx); cy = __builtin_fmaf(bw[k], x[1], cy); cz = __builtin_fmaf(bw[k], x[2], cz);
+            }
+            // (the query as the search formed it: one subtraction per component)
+            ex = g2 * ((points[o * 3] - transl[3 * b]) - cx);
+            ey = g2 * ((points[o * 3 + 1] - transl[3 * b + 1]) - cy);
+            ez = g2 * ((points[o * 3 + 2] - transl[3 * b + 2]) - cz);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const size_t row = ((size_t)b * V + vi[k]) * 3;
+                if (kFixed) {
+                    fixed_add(grad_fixed + row, -bw[k] * ex);
+                    fixed_add(grad_fixed + row + 1, -bw[k] * ey);
+                    fixed_add(grad_fixed + row + 2, -bw[k] * ez);
+                } else {
+                    atomicAdd(grad_verts + row, -bw[k] * ex);
+                    atomicAdd(grad_verts + row + 1, -bw[k] * ey);
+                    atomicAdd(grad_verts + row + 2, -bw[k] * ez);
+                }
+            }
+        }
+    }
+    if (grad_points && q < Q) {
+        float* g = grad_points + ((size_t)b * Q + q) * 3;
+        g[0] = ex; g[1] = ey; g[2] = ez;
+    }
+    float sx = wave_sum(-ex), sy = wave_sum(-ey), sz = wave_sum(-ez);
+    s = wave_sum(s);
+    if ((t & 63) == 0) {
+        float* r = red[t >> 6];
+        r[0] = s; r[1] = sx; r[2] = sy; r[3] = sz;
+    }
+    __syncthreads();
+    if (t < 5) {
+        float acc = wsum;
+        if (t < 4) {
+            acc = red[0][t];
+#pragma unroll
+            for (int j = 1; j < kWaves; ++j) acc += red[j][t];
+        }
+        __hip_atomic_store((gfloat*)partial + ((size_t)b * chunks + c) * kPart + t, acc, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+    }
+    // as vertex_fit_kernel (mesh_fit.hip): wave 0 holds the storing lanes and the lane that takes the ticket; its
+    // write-through stores have left before the ticket is taken, and the partials are read by loads that bypass this
+    // CU's cache
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (t == 0) last = atomicAdd(ticket, 1) == chunks * B - 1;
+    __syncthreads();
+    if (!last) return;
+    float mine = 0.0f;
+    for (int idx = t; idx < 4 * B; idx += kBlock) {           // (body, component); the stride keeps a thread on one component
+        const int body = idx >> 2, k = idx & 3;
+        const gfloat* p = (const gfloat*)partial + (size_t)body * chunks * kPart + k;
+        float acc = 0.0f;
+        for (int j = 0; j < chunks; ++j) acc += __hip_atomic_load(p + kPart * j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (k == 0) {
+            const float n = __hip_atomic_load((const gfloat*)partial + (size_t)body * chunks * kPart + 4, __ATOMIC_RELAXED,
+                                              __HIP_MEMORY_SCOPE_AGENT);
+            const float v = n != 0.0f ? acc / n : 0.0f;
+            per_body[body] = v;
+            mine += v;
+        } else {
+            grad_transl[3 * body + k - 1] = acc;
+        }
+    }
+    tree[t] = mine;
+    __syncthreads();
+    for (int h = kBlock / 2; h > 0; h >>= 1) {
+        if (t < h) tree[t] += tree[t + h];
+        __syncthreads();
+    }
+    if (t == 0) { total[0] = tree[0]; *ticket = 0; }
+}
+
+// n 32-bit words of zeros (the float gradient, or the 64-bit fixed-point sums as pairs of words)
+__global__ __launch_bounds__(kBlock) void scan_zero_kernel(uint32_t* __restrict__ out, size_t n)
+{
+    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i < n) out[i] = 0u;
+}
+
+__global__ __launch_bounds__(kBlock) void scan_fixed_to_float_kernel(const long long* __restrict__ fixed, float* __restrict__ out,
+                                                                    size_t n)
+{
+    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i < n) out[i] = fixed_value(fixed[i]);
+}
+
+}  // namespace
+
+extern "C" size_t tuch_scan_fit_workspace_bytes(const tuch_contact_model* m, int B, int Q)
+{
+    if (!m || B <= 0 || Q <= 0) return 0;
+    tuch_ws_scope scope(m->opt.canary != 0);
+    return scan_layout(m, B, Q).total;
+}
+
+extern "C" int tuch_scan_fit_terms(const tuch_contact_model* m, const float* verts, const float* transl, const float* points,
+                                   const int32_t* counts, const float* weights, const int32_t* hint, int B, int Q, int rho,
+                                   float sigma, float* d2, int32_t* face, float* bary, int* ticket, float* per_body,
+                                   float* total, float* grad_verts, float* grad_transl, float* grad_points, void* workspace,
+                                   size_t workspace_bytes, void* stream)
+{
+    TUCH_REQUIRE(m && verts && transl && points && d2 && face && bary && ticket && per_body && total && grad_verts && grad_transl,
+                 "tuch_scan_fit_terms: null pointer");
+    TUCH_REQUIRE(B > 0 && B <= 65535 && Q > 0 && (long long)B * ceil_div(Q, kBlock) < (1ll << 30),
+                 "tuch_scan_fit_terms: bad sizes B=%d Q=%d", B, Q);
+    TUCH_REQUIRE(rho == TUCH_SCAN_RHO_SQUARED || rho == TUCH_SCAN_RHO_DISTANCE || (rho == TUCH_SCAN_RHO_GMOF && sigma > 0.0f),
+                 "tuch_scan_fit_terms: rho %d (0 squared, 1 distance, 2 gmof with sigma > 0; sigma = %g)", rho, (double)sigma);
+    const size_t need = tuch_scan_fit_workspace_bytes(m, B, Q);
+    if (!workspace || workspace_bytes < need) {
+        tuch_set_error("tuch_scan_fit_terms: workspace %zu < %zu bytes", workspace_bytes, need);
+        return TUCH_ERR_WORKSPACE;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    tuch_ws_scope scope(m->opt.canary != 0);
+    const ScanLayout l = scope.record(0, [&] { return scan_layout(m, B, Q); });
+    scope.arm(workspace, m->canary_hits, s);
+    const int rc = tuch_cp_search("tuch_scan_fit_terms", m, verts, points, transl, counts, hint, B, Q, d2, face, bary,
+                                  (char*)workspace + l.search, tuch_closest_point_workspace_bytes(m, B, Q), stream);
+    if (rc != TUCH_OK) return rc;
+    long long* fixed = (long long*)((char*)workspace + l.fixed);
+    float* partial = (float*)((char*)workspace + l.partial);
+    const bool det = tuch_deterministic() != 0;
+    const size_t n = (size_t)B * m->V * 3;
+    const size_t words = det ? 2 * n : n;
+    hipLaunchKernelGGL(scan_zero_kernel, dim3((unsigned)((words + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
+                       det ? (uint32_t*)fixed : (uint32_t*)grad_verts, words);
+    const dim3 grid(ceil_div(Q, kBlock), B);
+    const float sigma2 = sigma * sigma;
+    if (det) {
+        hipLaunchKernelGGL(scan_term_kernel<true>, grid, dim3(kBlock), 0, s, verts, transl, points, counts, weights,
+                           (const float*)d2, (const int32_t*)face, (const float*)bary, (const int32_t*)m->faces, B, m->V, m->F,
+                           Q, rho, sigma2, partial, ticket, per_body, total, grad_points, (float*)nullptr, fixed, grad_transl);
+        hipLaunchKernelGGL(scan_fixed_to_float_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
+                           (const long long*)fixed, grad_verts, n);
+    } else {
+        hipLaunchKernelGGL(scan_term_kernel<false>, grid, dim3(kBlock), 0, s, verts, transl, points, counts, weights,
+                           (const float*)d2, (const int32_t*)face, (const float*)bary, (const int32_t*)m->faces, B, m->V, m->F,
+                           Q, rho, sigma2, partial, ticket, per_body, total, grad_points, grad_verts, (long long*)nullptr,
+                           grad_transl);
+    }
+    return tuch_check_launch("tuch_scan_fit_terms");
+}

@@ -1,5 +1,5 @@
-"""Fit SMPL to target meshes in correspondence: the optimisation loop of the reference's ``tuch/utils/smplxtosmpl_mtp.py``
-(:63-105), batched and on the device.
+"""Fit SMPL to target meshes in correspondence (MeshFitter) and to unregistered points (ScanFitter, at the end of the file).
+MeshFitter is the optimisation loop of the reference's ``tuch/utils/smplxtosmpl_mtp.py`` (:63-105), batched and on the device.
 
 The reference fits ``body_pose``, ``betas`` and ``transl`` of ONE body with Adam (lr 1e-2, 5000 iterations) against
 ``torch.norm(target - verts, dim=2).mean()`` and starts over for every file.  Here a batch of bodies is fitted at once: the
@@ -122,3 +122,141 @@ class MeshFitter:
                 vertices = verts + t['transl'][:, None]
             own = lambda x: x.detach().clone()
             return MeshFit(own(t['global_orient']), own(t['body_pose']), own(t['betas']), own(t['transl']), vertices, loss)
+
+
+ScanFit = namedtuple('ScanFit', ['global_orient', 'body_pose', 'betas', 'transl', 'vertices', 'loss', 'face', 'bary'])
+
+
+class ScanFitter:
+    """Fit SMPL to unregistered points -- a scan, a depth point cloud, a mesh of another topology: ``ScanFitter(smpl,
+    model)(points [B,Q,3], global_orient)`` -> ScanFit.  ``model`` is a ``ContactModel`` over the body model's faces (no
+    geodesic mask is needed).  The data term is ops.scan_fit: every real point's distance to the nearest point of the posed,
+    translated mesh under ``rho`` ('distance', 'squared' or 'gmof' with ``sigma``), averaged per body with ``weights``
+    [B,Q]; ``counts`` [B] marks how many points per body are real.  The loop is MeshFitter's: body model forward, the term
+    with its gradients as one call, backward from the cached unit seed, Adam as one launch, run by SMPLifyDC._Stage and kept
+    as a session (at most four; ``TUCH_GRAPH_STRICT`` and ``TUCH_SMPLIFY_SESSIONS`` as there).
+
+    ``use_hint``: the session holds a [B,Q] int32 tensor that is both the search's hint and where it writes its faces, so
+    every iteration starts each point from the face it found last time; the tensor is reset to -1 at the start of every
+    call.  The hint changes no bit of any result (tuch_closest_point_hinted).
+
+    ``vertices`` [B,V,3] include the translation; ``loss`` [B], ``face`` [B,Q] and ``bary`` [B,Q,3] are those of the
+    evaluation after the last update.  ``global_orient`` is held fixed unless ``fit_global_orient`` is set.  Inputs are
+    never modified; there is no host fallback."""
+
+    def __init__(self, smpl, model, step_size=1e-2, num_iters=300, fit_global_orient=True, rho='distance', sigma=None,
+                 use_hint=True, use_graph=True, record_history=False):
+        if rho not in ops.SCAN_RHO:
+            raise ValueError('ScanFitter: rho must be one of %s, got %r' % (sorted(ops.SCAN_RHO), rho))
+        if rho == 'gmof' and not (sigma is not None and float(sigma) > 0.0):
+            raise ValueError("ScanFitter: rho='gmof' needs sigma > 0, got %r" % (sigma,))
+        self.smpl = smpl
+        self.model = model
+        self.step_size = step_size
+        self.num_iters = num_iters
+        self.fit_global_orient = fit_global_orient
+        self.rho, self.sigma = rho, sigma
+        self.use_hint = use_hint
+        self.use_graph = use_graph
+        # as MeshFitter: the objective and the parameters *before* every update in self.history['fit'], the parameters in
+        # the optimiser's order: body_pose, betas, transl (, global_orient)
+        self.record_history = record_history
+        self.graph_strict = os.environ.get('TUCH_GRAPH_STRICT', '0') == '1'
+        self.keep_sessions = os.environ.get('TUCH_SMPLIFY_SESSIONS', '1') != '0'
+        self.history = None
+        self.graph_replayed = {}
+        self._sessions = {}
+
+    def _session(self, batch, num_points, with_counts, with_weights, device):
+        """(key, session): the static tensors, the iteration closure and the loop of a fit with these constants."""
+        key = (batch, num_points, bool(with_counts), bool(with_weights), device.index, float(self.step_size),
+               bool(self.fit_global_orient), self.rho, None if self.sigma is None else float(self.sigma), bool(self.use_hint),
+               bool(self.record_history))
+        sess = self._sessions.get(key)
+        if sess is not None:
+            return key, sess
+        z = lambda *shape, dtype=torch.float32: torch.zeros(*shape, dtype=dtype, device=device)
+        t = dict(body_pose=z(batch, 69), betas=z(batch, 10), transl=z(batch, 3), global_orient=z(batch, 3),
+                 points=z(batch, num_points, 3), hint=z(batch, num_points, dtype=torch.int32),
+                 counts=z(batch, dtype=torch.int32) if with_counts else None,
+                 weights=z(batch, num_points) if with_weights else None)
+        smpl, model = self.smpl, self.model
+        hint = t['hint'] if self.use_hint else None
+
+        def iteration():
+            out = smpl(global_orient=t['global_orient'], body_pose=t['body_pose'], betas=t['betas'])
+            # (the hint tensor receives the new faces: the aliasing tuch_closest_point_hinted allows)
+            total, _, _ = ops.scan_fit(model, out.vertices, t['transl'], t['points'], t['counts'], t['weights'], hint,
+                                       self.rho, self.sigma, face_out=hint)
+            return total, out.vertices
+        params = [t['body_pose'], t['betas'], t['transl']] + ([t['global_orient']] if self.fit_global_orient else [])
+        for p in params:
+            p.requires_grad = True
+        sess = dict(t=t, stage=SMPLifyDC._Stage(self, 'fit', params, iteration, {}))
+        return key, sess
+
+    def __call__(self, points, global_orient, counts=None, weights=None, body_pose=None, betas=None, transl=None):
+        if points.dim() != 3 or points.shape[2] != 3 or points.shape[0] == 0 or points.shape[1] == 0:
+            raise ValueError('ScanFitter: points must be [B,Q,3], got %s' % (tuple(points.shape),))
+        batch, num_points = points.shape[0], points.shape[1]
+        for name, value, shape in (('global_orient', global_orient, (batch, 3)), ('body_pose', body_pose, (batch, 69)),
+                                   ('betas', betas, (batch, 10)), ('transl', transl, (batch, 3)), ('counts', counts, (batch,)),
+                                   ('weights', weights, (batch, num_points))):
+            if value is not None and tuple(value.shape) != shape:
+                raise ValueError('ScanFitter: %s has shape %s, expected %s' % (name, tuple(value.shape), shape))
+        device = points.device
+        if device.type != 'cuda':
+            raise RuntimeError('ScanFitter runs on a HIP device (there is no host fallback); got tensors on %s' % device)
+        if int(self.model.num_verts) != int(self.smpl.v_template.shape[0]):
+            raise ValueError('ScanFitter: the ContactModel has %d vertices, the body model %d'
+                             % (self.model.num_verts, self.smpl.v_template.shape[0]))
+        if self.smpl.v_template.device != device:
+            self.smpl = self.smpl.to(device)
+        on_gpu = bool(self.use_graph)
+        capture = on_gpu and self.num_iters > 4
+        if self.record_history:
+            self.history = {'fit': []}
+        # graph replays never run on the NULL stream (ops.py)
+        with ops.off_default_stream(device) if on_gpu else contextlib.nullcontext():
+            key, sess = self._session(batch, num_points, counts is not None, weights is not None, device)
+            t = sess['t']
+            with torch.no_grad():
+                t['points'].copy_(points)
+                t['global_orient'].copy_(global_orient)
+                t['hint'].fill_(-1)                       # no memory of another call's answers
+                if counts is not None:
+                    t['counts'].copy_(counts.clamp(0, num_points))
+                if weights is not None:
+                    t['weights'].copy_(weights)
+                for name, value in (('body_pose', body_pose), ('betas', betas)):
+                    t[name].zero_() if value is None else t[name].copy_(value)
+                if transl is not None:
+                    t['transl'].copy_(transl)
+                else:               # the centroid of each body's real, weighted points minus that of its initial vertices
+                    verts = self.smpl(global_orient=t['global_orient'], body_pose=t['body_pose'], betas=t['betas']).vertices
+                    w = torch.ones(batch, num_points, device=device) if weights is None else t['weights'].clone()
+                    if counts is not None:
+                        w = w * (torch.arange(num_points, device=device)[None] < t['counts'][:, None])
+                    used = (w != 0)[:, :, None]
+                    centre = torch.where(used, w[:, :, None] * t['points'], torch.zeros_like(t['points'])).sum(1)
+                    wsum = w.sum(1, keepdim=True)
+                    centre = torch.where(wsum != 0, centre / torch.where(wsum != 0, wsum, torch.ones_like(wsum)),
+                                         verts.mean(1))       # (a body without points stays where it is)
+                    t['transl'].copy_(centre - verts.mean(1))
+            captured = sess['stage'].run(self.num_iters, None, capture)
+            # a captured loop is kept for the next call; a session that ran eagerly (or lost its capture) is dropped
+            if not (captured and self.keep_sessions):
+                self._sessions.pop(key, None)
+            elif key not in self._sessions:
+                while len(self._sessions) >= 4:
+                    self._sessions.pop(next(iter(self._sessions)))
+                self._sessions[key] = sess
+            with torch.no_grad():
+                verts = self.smpl(global_orient=t['global_orient'], body_pose=t['body_pose'], betas=t['betas']).vertices
+                hint = t['hint'] if self.use_hint else None
+                _, loss, near = ops.scan_fit(self.model, verts, t['transl'], t['points'], t['counts'], t['weights'], hint,
+                                             self.rho, self.sigma)
+                vertices = verts + t['transl'][:, None]
+            own = lambda x: x.detach().clone()
+            return ScanFit(own(t['global_orient']), own(t['body_pose']), own(t['betas']), own(t['transl']), vertices, loss,
+                           near.face, near.bary)

@@ -1344,7 +1344,8 @@ class ContactModel:
                                        _C.ptr(w), _C.ptr(ext), _C.ptr(ws), nbytes, _C.stream()))
         return w, ext
 
-    def closest_point(self, verts: torch.Tensor, points: torch.Tensor, counts: Optional[torch.Tensor] = None) -> 'ClosestPoint':
+    def closest_point(self, verts: torch.Tensor, points: torch.Tensor, counts: Optional[torch.Tensor] = None,
+                      hint: Optional[torch.Tensor] = None) -> 'ClosestPoint':
         """The nearest point of this mesh posed by verts [B,V,3] for arbitrary points [B,Q,3] (csrc/closest_point.hip):
         ``ClosestPoint(d2 [B,Q], face [B,Q] int32, bary [B,Q,3])`` with the nearest point = sum_k bary[k] *
         verts[faces[face][k]].  counts [B] int32 marks how many points per body are real; the others get d2 = inf,
@@ -1352,13 +1353,28 @@ class ContactModel:
         is exact, blocks of 64 consecutive points that are close in space are fast (a wavefront visits the face groups
         any of its 64 queries needs).  d2 is differentiable with respect to verts and points with the weights held fixed
         (exact wherever the closest feature does not change), bit-reproducibly under ``deterministic()``; face and bary
-        are not differentiable."""
+        are not differentiable.
+        hint [B,Q] int32: per query a face that is probably the answer (a fitting loop passes the previous iteration's
+        ``face``).  It changes no bit of the result, whatever it holds (wrong faces and indices out of range included);
+        a valid one lets the query start from that face's exact distance instead of from a walk over every box of the
+        body (tuch_closest_point_hinted)."""
         if verts.dim() != 3 or points.dim() != 3 or verts.shape[0] != points.shape[0] or verts.shape[1] != self.num_verts:
             raise _C.TuchError('closest_point: verts [B,%d,3] and points [B,Q,3] expected, got %s and %s'
                                % (self.num_verts, tuple(verts.shape), tuple(points.shape)))
         if counts is not None:
             counts = counts.to(torch.int32).contiguous()
-        return ClosestPoint(*_ClosestPoint.apply(verts, points, self, counts))
+        hint = _hint_of(hint, points, 'closest_point')
+        return ClosestPoint(*_ClosestPoint.apply(verts, points, self, counts, hint))
+
+    def face_groups(self):
+        """The face groups the closest-point search walks, as host arrays: (group_off [G+1], face_list [F], face_group
+        [F]); face_group is the inverse of face_list -- the group a hinted query starts from."""
+        n = ctypes.c_int(0)
+        L = _C.lib()
+        _C.check(L.tuch_contact_model_face_groups(self._handle, ctypes.byref(n), None, None, None))
+        off, lst, grp = np.zeros(n.value + 1, np.int32), np.zeros(self.num_faces, np.int32), np.zeros(self.num_faces, np.int32)
+        _C.check(L.tuch_contact_model_face_groups(self._handle, None, *(a.ctypes.data_as(ctypes.c_void_p) for a in (off, lst, grp))))
+        return off, lst, grp
 
     def signed_distance(self, verts: torch.Tensor, points: torch.Tensor, counts: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Distance [B,Q] from points [B,Q,3] to this mesh posed by verts, negative where the point is interior
@@ -1424,11 +1440,23 @@ class ClosestPoint(NamedTuple):
     bary: torch.Tensor
 
 
+def _hint_of(hint, points, what):
+    """hint as the kernels read it: int32 [B,Q] on the points' device, contiguous (the tensor itself where it already is:
+    a loop's hint tensor may be the one the faces are written to)."""
+    if hint is None:
+        return None
+    if tuple(hint.shape) != tuple(points.shape[:2]) or hint.device != points.device:
+        raise _C.TuchError('%s: hint must be [B,Q] = %s on %s, got %s on %s'
+                           % (what, tuple(points.shape[:2]), points.device, tuple(hint.shape), hint.device))
+    return hint.to(torch.int32).contiguous()
+
+
 class _ClosestPoint(torch.autograd.Function):
-    """ContactModel.closest_point: tuch_closest_point forward, tuch_closest_point_bwd (the envelope form) backward."""
+    """ContactModel.closest_point: tuch_closest_point_hinted forward (hint None: tuch_closest_point's search),
+    tuch_closest_point_bwd (the envelope form) backward."""
 
     @staticmethod
-    def forward(ctx, verts, points, model: ContactModel, counts):
+    def forward(ctx, verts, points, model: ContactModel, counts, hint):
         v, pts = _f32(verts), _f32(points)
         b, q, _ = pts.shape
         L = _C.lib()
@@ -1438,8 +1466,8 @@ class _ClosestPoint(torch.autograd.Function):
         nbytes = L.tuch_closest_point_workspace_bytes(model._handle, b, q)
         ws = _workspace(nbytes, pts.device)
         if b and q:
-            _C.check(L.tuch_closest_point(model._handle, _C.ptr(v), _C.ptr(pts), _C.ptr(counts), b, q, _C.ptr(d2), _C.ptr(face),
-                                          _C.ptr(bary), _C.ptr(ws), nbytes, _C.stream()))
+            _C.check(L.tuch_closest_point_hinted(model._handle, _C.ptr(v), _C.ptr(pts), _C.ptr(counts), _C.ptr(hint), b, q,
+                                                 _C.ptr(d2), _C.ptr(face), _C.ptr(bary), _C.ptr(ws), nbytes, _C.stream()))
         ctx.save_for_backward(v, pts, face, bary)
         ctx.model = model
         ctx.mark_non_differentiable(face, bary)
@@ -1451,7 +1479,7 @@ class _ClosestPoint(torch.autograd.Function):
         b, q, _ = pts.shape
         want_v, want_p = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         if b == 0 or q == 0 or not (want_v or want_p):
-            return (torch.zeros_like(v) if want_v else None), (torch.zeros_like(pts) if want_p else None), None, None
+            return (torch.zeros_like(v) if want_v else None), (torch.zeros_like(pts) if want_p else None), None, None, None
         g = grad_d2.to(torch.float32).contiguous()
         gp = torch.empty_like(pts) if want_p else None
         gv = fixed = None
@@ -1462,7 +1490,96 @@ class _ClosestPoint(torch.autograd.Function):
             gv = torch.zeros_like(v)
         _C.check(_C.lib().tuch_closest_point_bwd(ctx.model._handle, _C.ptr(v), _C.ptr(pts), _C.ptr(face), _C.ptr(bary),
                                                  _C.ptr(g), b, q, _C.ptr(gp), _C.ptr(fixed), _C.ptr(gv), _C.stream()))
-        return gv, gp, None, None
+        return gv, gp, None, None, None
+
+
+SCAN_RHO = {'squared': 0, 'distance': 1, 'gmof': 2}
+
+
+class _ScanFit(torch.autograd.Function):
+    """ops.scan_fit: the search, the term and the unit gradients in one C call (csrc/scan_fit.hip: tuch_scan_fit_terms).
+    `face` [B,Q] int32 is written in place (it may be the hint tensor).  backward() only hands the gradients over (scaled
+    unless the upstream gradient is the cached unit seed of ops.backward_scalar)."""
+
+    @staticmethod
+    def forward(ctx, verts, transl, points, model: ContactModel, counts, weights, hint, rho, sigma, face):
+        v, tr, pts = _f32(verts), _f32(transl), _f32(points)
+        b, q, _ = pts.shape
+        dev = pts.device
+        L = _C.lib()
+        d2 = torch.empty(b, q, dtype=torch.float32, device=dev)
+        bary = torch.empty(b, q, 3, dtype=torch.float32, device=dev)
+        per_body = torch.empty(b, dtype=torch.float32, device=dev)
+        out = torch.empty(1, dtype=torch.float32, device=dev)
+        gv = torch.empty_like(v)
+        gt = torch.empty(b, 3, dtype=torch.float32, device=dev)
+        gp = torch.empty_like(pts) if ctx.needs_input_grad[2] else None
+        nbytes = L.tuch_scan_fit_workspace_bytes(model._handle, b, q)
+        ws = _workspace(nbytes, dev)
+        _C.check(L.tuch_scan_fit_terms(model._handle, _C.ptr(v), _C.ptr(tr), _C.ptr(pts), _C.ptr(counts), _C.ptr(weights),
+                                       _C.ptr(hint), b, q, rho, sigma, _C.ptr(d2), _C.ptr(face), _C.ptr(bary),
+                                       _C.ptr(_ticket(dev)), _C.ptr(per_body), _C.ptr(out), _C.ptr(gv), _C.ptr(gt), _C.ptr(gp),
+                                       _C.ptr(ws), nbytes, _C.stream()))
+        ctx.save_for_backward(gv, gt, gp)
+        ctx.in_dtypes = (verts.dtype, transl.dtype, points.dtype)
+        ctx.mark_non_differentiable(per_body, d2, bary)
+        ctx.set_materialize_grads(False)        # the other outputs' absent gradients arrive as None, not as zero fills
+        return out[0], per_body, d2, bary
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, *_others):
+        if g is None:
+            return (None,) * 10
+        gv, gt, gp = ctx.saved_tensors
+        if not backward_pass.is_unit_seed(g):
+            g = g.reshape(()).to(torch.float32)
+            gv, gt, gp = gv * g, gt * g, (gp * g if gp is not None else None)
+        dv, dt, dp = ctx.in_dtypes
+        return (gv.to(dv), gt.to(dt), gp.to(dp) if gp is not None else None) + (None,) * 7
+
+
+def scan_fit(model: ContactModel, verts, transl, points, counts=None, weights=None, hint=None, rho='distance', sigma=None,
+             face_out=None):
+    """Point-to-surface data term of a fit to unregistered points: ``(total, per_body, ClosestPoint)``.  The queries are
+    ``points[b,q] - transl[b]`` against ``model``'s mesh posed by ``verts[b]``; the ClosestPoint has the bits of
+    ``model.closest_point(verts, points - transl[:, None], counts, hint)``.  per_body[b] = sum_q w_q rho(d2_q) / sum_q w_q
+    over the body's real points (counts [B]) and total = their sum over the bodies -- the bodies are independent, as in
+    vertex_fit.  rho: 'squared' (d2), 'distance' (sqrt d2, gradient 0 at d2 = 0) or 'gmof' (sigma^2 d2 / (sigma^2 + d2),
+    needs sigma).  weights [B,Q] or None; a point of weight 0 is never computed from (it may be non-finite); a body whose
+    weights sum to 0 or with counts[b] = 0 has loss 0 and zero gradient rows.  total is differentiable w.r.t. verts,
+    transl and points with the weights of the nearest point held fixed; the sums into the vertex rows are 64-bit
+    fixed-point under ``deterministic()`` and float atomics otherwise, every per-body sum is fixed-order in both modes.
+    hint [B,Q] int32 as in ``closest_point``; face_out: a contiguous int32 [B,Q] tensor to receive the faces -- it may be
+    the hint tensor itself (a loop's memory of its last answer).  There is no host fallback."""
+    if rho not in SCAN_RHO:
+        raise ValueError('scan_fit: rho must be one of %s, got %r' % (sorted(SCAN_RHO), rho))
+    if rho == 'gmof' and not (sigma is not None and float(sigma) > 0.0):
+        raise ValueError("scan_fit: rho='gmof' needs sigma > 0, got %r" % (sigma,))
+    if verts.dim() != 3 or tuple(verts.shape[1:]) != (model.num_verts, 3):
+        raise ValueError('scan_fit: verts must be [B,%d,3], got %s' % (model.num_verts, tuple(verts.shape)))
+    b = verts.shape[0]
+    if points.dim() != 3 or points.shape[0] != b or points.shape[2] != 3:
+        raise ValueError('scan_fit: points must be [%d,Q,3], got %s' % (b, tuple(points.shape)))
+    q = points.shape[1]
+    if tuple(transl.shape) != (b, 3):
+        raise ValueError('scan_fit: transl has shape %s, expected %s' % (tuple(transl.shape), (b, 3)))
+    if b == 0 or q == 0:
+        raise ValueError('scan_fit: empty input %s' % (tuple(points.shape),))
+    if weights is not None and tuple(weights.shape) != (b, q):
+        raise ValueError('scan_fit: weights must be [%d,%d], got %s' % (b, q, tuple(weights.shape)))
+    if counts is not None and tuple(counts.shape) != (b,):
+        raise ValueError('scan_fit: counts must be [%d], got %s' % (b, tuple(counts.shape)))
+    _need_hip('scan_fit', verts, transl, points, weights, counts, hint, face_out)
+    if face_out is not None and (tuple(face_out.shape) != (b, q) or face_out.dtype != torch.int32 or not face_out.is_contiguous()):
+        raise ValueError('scan_fit: face_out must be a contiguous int32 [%d,%d] tensor' % (b, q))
+    counts = None if counts is None else counts.to(torch.int32).contiguous()
+    weights = None if weights is None else _f32(weights.detach())
+    hint = _hint_of(hint, points, 'scan_fit')
+    face = face_out if face_out is not None else torch.empty(b, q, dtype=torch.int32, device=points.device)
+    total, per_body, d2, bary = _ScanFit.apply(verts, transl, points, model, counts, weights, hint, SCAN_RHO[rho],
+                                               float(sigma) if sigma is not None else 0.0, face)
+    return total, per_body, ClosestPoint(d2, face, bary)
 
 
 class HDModel:
