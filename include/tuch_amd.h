@@ -439,6 +439,70 @@ int tuch_scan_fit_terms(const tuch_contact_model* model, const float* verts /* [
                         float* grad_transl /* [B,3] */, float* grad_points /* [B,Q,3] or NULL */, void* workspace,
                         size_t workspace_bytes, void* stream);
 
+/* Nearest point of a static point cloud; the model -> scan term of a two-sided fit (csrc/point_cloud.hip).  No model
+ * is involved: a cloud has no mesh.
+ *   The rule.  The cloud of body b is the set of VALID points of points [B,Q,3]: index < counts[b] (counts [B] or NULL,
+ * clamped to [0, Q]), weight != 0 where weights [B,Q] are given, all three coordinates finite; any other point is never
+ * a neighbour and never computed from (it may be NaN).  The query is q = x + shift[b], one float32 add per component
+ * (shift NULL: the bits of x).  THE squared distance of a (query, point) pair is d = q - s per component and
+ * d2 = (dx dx + dy dy) + dz dz, every product and sum rounded to float32 on its own (no fused multiply-add).  The
+ * winner is the smallest packed key d2 bits << 32 | index, index being the point's position in the caller's [Q] order:
+ * the smallest d2, among equal bits the smallest index; only a finite d2 can win, and with max_distance tau > 0 only
+ * d2 <= (float)tau * (float)tau, compared in float32 (max_distance <= 0: no limit).  A query without winner -- empty
+ * cloud, non-finite query, every valid point beyond tau, an entry at or beyond query_counts[b] -- gets index = -1,
+ * d2 = +inf.  A query's outputs have the same bits alone or in any batch, for any order of the queries, for any order
+ * in which the build filed the points, for any resolution, eager or replayed, and for EVERY content of hint.  A body
+ * with NaN / Inf queries or points changes no other body's bits; every index read from a table is clamped before it
+ * addresses anything.  There is no gradient with respect to the points of the cloud: they are data.
+ *   tuch_point_cloud_build files the valid points into a uniform grid per body -- isotropic cells, the longest extent of
+ * the valid points' box cut into `resolution` (1 .. 256) cells, the header (origin, cell edge, dims) written on the
+ * device -- in the workspace (tuch_point_cloud_workspace_bytes: 0 for B, Q or resolution <= 0).  Five kernel launches,
+ * no host round trip, no allocation, no synchronisation, capturable.  The query reads points / counts / weights again
+ * only to check a hint: pass the arrays the cloud was built from.
+ *   hint [B,N] device ints or NULL: hint[b,n] in [0, Q) that names a valid point -- checked before anything is
+ * addressed -- whose d2 is finite and within tau gives the lane's starting bound and enters as an ordinary key; any other
+ * value takes the unhinted path.  hint may alias index: a lane reads its own entry before it writes it.
+ *   Cells and 4^3-cell blocks are skipped only when no point filed in them can produce a key smaller than or equal to
+ * the lane's bound; the bound's margin (2^-20, relative, in units of cells) is derived in the source file.
+ *   Option canary (tuch_point_cloud_set_canary, process-wide, returns the old value; set it before sizing and building):
+ * guard words behind every region of the workspace and of the term's scratch; words found changed are counted in the
+ * workspace's first word (zero it once), read -- and reset -- with tuch_point_cloud_canary_hits, which synchronises. */
+size_t tuch_point_cloud_workspace_bytes(int B, int Q, int resolution);
+int tuch_point_cloud_build(const float* points /* [B,Q,3] */, const int32_t* counts /* [B] or NULL */,
+                           const float* weights /* [B,Q] or NULL */, int B, int Q, int resolution, void* workspace,
+                           size_t workspace_bytes, void* stream);
+int tuch_point_cloud_nearest(const void* workspace, size_t workspace_bytes, const float* points /* [B,Q,3] */,
+                             const int32_t* counts /* [B] or NULL */, const float* weights /* [B,Q] or NULL */,
+                             const float* queries /* [B,N,3] */, const float* shift /* [B,3] or NULL */,
+                             const int32_t* query_counts /* [B] or NULL */, const int32_t* hint /* [B,N] or NULL */,
+                             float max_distance, int B, int Q, int N, float* d2 /* [B,N] */, int32_t* index /* [B,N] */,
+                             void* stream);
+/* The term: the query for q = verts[b,v] + transl[b] (d2, index [B,V] as tuch_point_cloud_nearest gives them; a vertex
+ * of weight 0 is not computed from and gets -1 / +inf), vertex weights w NULL (ones; layout 0), [V] (layout 1) or [B,V]
+ * (layout 2), rho / sigma as tuch_scan_fit_terms, and
+ *   per_body[b] = scale sum_v w_v rho(d2_v) / sum_v w_v,   total[0] = sum_b per_body[b].
+ * A vertex without winner contributes rho(tau^2) when max_distance is given and the body's cloud is not empty, 0
+ * otherwise, and has a zero gradient row.  A body whose cloud is empty or whose weights sum to 0 has per_body = 0 and
+ * zero gradients.  For a unit upstream gradient, the nearest point held fixed: grad_verts[b,v] = 2 g_v (q - s) with
+ * g_v = scale w_v rho'(d2_v) / sum w (every row written, by the lane that owns it: no atomics), grad_transl[b] = sum_v
+ * grad_verts[b,v].  per_body, its normaliser, total and grad_transl are fixed-order sums: the same bits in either mode
+ * of tuch_set_deterministic, on every call, and for a body alone or in a batch.  ticket as for tuch_scan_fit_terms;
+ * scratch: tuch_point_cloud_fit_scratch_bytes(B, V) bytes.  One launch; capturable. */
+size_t tuch_point_cloud_fit_scratch_bytes(int B, int V);
+int tuch_point_cloud_fit_terms(const void* workspace, size_t workspace_bytes, const float* points, const int32_t* counts,
+                               const float* weights, const float* verts /* [B,V,3] */, const float* transl /* [B,3] */,
+                               const int32_t* hint /* [B,V] or NULL */, float max_distance, int B, int Q, int V,
+                               const float* vertex_weights, int vertex_weight_layout, int rho, float sigma, float scale,
+                               float* d2 /* [B,V] */, int32_t* index /* [B,V] */, int* ticket, float* per_body /* [B] */,
+                               float* total /* [1] */, float* grad_verts /* [B,V,3] */, float* grad_transl /* [B,3] */,
+                               void* scratch, size_t scratch_bytes, void* stream);
+/* Host copies of the per-body headers the build wrote: origin_host [B,3], cell_host [B], dims_host [B,3].  Synchronises;
+ * for tests and tools (a test can put points exactly on cell walls). */
+int tuch_point_cloud_grid(const void* workspace, int B, int resolution, float* origin_host, float* cell_host,
+                          int32_t* dims_host);
+int tuch_point_cloud_set_canary(int on);
+int tuch_point_cloud_canary_hits(void* workspace, int* hits_host, int reset);
+
 /* region-pair minima: TUCH.contact_from_verts, train_module.py:69-91 (select NULL, unmasked)
  * and the region-to-region term, losses.py:107-117 (select = gt_contact & has_discrete_contact,
  * geodesically masked).  out_min [B,P] (0 where not selected), out_ij [B,P,2] arg-min vertices. */

@@ -121,6 +121,15 @@ _SIGNATURES = {
     'tuch_contact_model_face_groups': (c_int, [c_void_p, POINTER(c_int), c_void_p, c_void_p, c_void_p]),
     'tuch_scan_fit_workspace_bytes': (c_size_t, [c_void_p, c_int, c_int]),
     'tuch_scan_fit_terms': (c_int, [c_void_p] * 7 + [c_int, c_int, c_int, c_float] + [c_void_p] * 10 + [c_size_t, c_void_p]),
+    'tuch_point_cloud_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'tuch_point_cloud_build': (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_void_p, c_size_t, c_void_p]),
+    'tuch_point_cloud_nearest': (c_int, [c_void_p, c_size_t] + [c_void_p] * 7 + [c_float, c_int, c_int, c_int] + [c_void_p] * 3),
+    'tuch_point_cloud_fit_scratch_bytes': (c_size_t, [c_int, c_int]),
+    'tuch_point_cloud_fit_terms': (c_int, [c_void_p, c_size_t] + [c_void_p] * 6 + [c_float, c_int, c_int, c_int, c_void_p, c_int,
+                                           c_int, c_float, c_float] + [c_void_p] * 8 + [c_size_t, c_void_p]),
+    'tuch_point_cloud_grid': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'tuch_point_cloud_set_canary': (c_int, [c_int]),
+    'tuch_point_cloud_canary_hits': (c_int, [c_void_p, POINTER(c_int), c_int]),
     'tuch_contact_terms_ragged_fwd': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p,
                                               c_void_p]),
     'tuch_contact_terms_ragged_bwd': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float,

@@ -125,6 +125,7 @@ class MeshFitter:
 
 
 ScanFit = namedtuple('ScanFit', ['global_orient', 'body_pose', 'betas', 'transl', 'vertices', 'loss', 'face', 'bary'])
+CloudFit = namedtuple('CloudFit', ['loss', 'd2', 'index'])
 
 
 class ScanFitter:
@@ -140,16 +141,36 @@ class ScanFitter:
     every iteration starts each point from the face it found last time; the tensor is reset to -1 at the start of every
     call.  The hint changes no bit of any result (tuch_closest_point_hinted).
 
-    ``vertices`` [B,V,3] include the translation; ``loss`` [B], ``face`` [B,Q] and ``bary`` [B,Q,3] are those of the
-    evaluation after the last update.  ``global_orient`` is held fixed unless ``fit_global_orient`` is set.  Inputs are
+    ``model_to_scan`` lambda > 0 makes the fit two-sided: the iteration's objective is the scan -> model term plus
+    lambda times the model -> scan term (ops.cloud_fit: every vertex's distance to the nearest real point of the scan
+    under the same ``rho`` / ``sigma``, averaged per body with ``vertex_weights`` [V] or [B,V], truncated at
+    ``max_distance`` for partial scans).  The session then holds an ops.PointCloud over its static points / counts /
+    weights buffers (``resolution`` cells along the longest extent) and a [B,V] int32 tensor that is the query's hint and
+    where it writes its indices; the cloud is rebuilt and the tensor reset to -1 at the start of every call, outside the
+    replayed loop.  With the default 0.0 nothing of this exists: the bits and the launches are those of the one-sided fit.
+
+    ``vertices`` [B,V,3] include the translation; ``loss`` [B] (the scan -> model term), ``face`` [B,Q] and ``bary``
+    [B,Q,3] are those of the evaluation after the last update; the other direction's is ``self.model_to_scan_result`` =
+    CloudFit(loss [B], d2 [B,V], index [B,V]) (None when the option is off).  ``global_orient`` is held fixed unless ``fit_global_orient`` is set.  Inputs are
     never modified; there is no host fallback."""
 
     def __init__(self, smpl, model, step_size=1e-2, num_iters=300, fit_global_orient=True, rho='distance', sigma=None,
-                 use_hint=True, use_graph=True, record_history=False):
+                 use_hint=True, use_graph=True, record_history=False, model_to_scan=0.0, vertex_weights=None,
+                 max_distance=None, resolution=64):
         if rho not in ops.SCAN_RHO:
             raise ValueError('ScanFitter: rho must be one of %s, got %r' % (sorted(ops.SCAN_RHO), rho))
         if rho == 'gmof' and not (sigma is not None and float(sigma) > 0.0):
             raise ValueError("ScanFitter: rho='gmof' needs sigma > 0, got %r" % (sigma,))
+        if not float(model_to_scan) >= 0.0:
+            raise ValueError('ScanFitter: model_to_scan must be >= 0, got %r' % (model_to_scan,))
+        if max_distance is not None and not float(max_distance) > 0.0:
+            raise ValueError('ScanFitter: max_distance must be > 0 (or None), got %r' % (max_distance,))
+        if not (isinstance(resolution, int) and 1 <= resolution <= 256):
+            raise ValueError('ScanFitter: resolution must be an int in 1 .. 256, got %r' % (resolution,))
+        num_verts = int(smpl.v_template.shape[0])
+        if vertex_weights is not None and (not torch.is_tensor(vertex_weights) or vertex_weights.dim() not in (1, 2)
+                                           or vertex_weights.shape[-1] != num_verts):
+            raise ValueError('ScanFitter: vertex_weights must be a [%d] or [B,%d] tensor' % (num_verts, num_verts))
         self.smpl = smpl
         self.model = model
         self.step_size = step_size
@@ -157,6 +178,11 @@ class ScanFitter:
         self.fit_global_orient = fit_global_orient
         self.rho, self.sigma = rho, sigma
         self.use_hint = use_hint
+        self.model_to_scan = float(model_to_scan)
+        self.vertex_weights = vertex_weights
+        self.max_distance = None if max_distance is None else float(max_distance)
+        self.resolution = resolution
+        self.model_to_scan_result = None
         self.use_graph = use_graph
         # as MeshFitter: the objective and the parameters *before* every update in self.history['fit'], the parameters in
         # the optimiser's order: body_pose, betas, transl (, global_orient)
@@ -171,7 +197,8 @@ class ScanFitter:
         """(key, session): the static tensors, the iteration closure and the loop of a fit with these constants."""
         key = (batch, num_points, bool(with_counts), bool(with_weights), device.index, float(self.step_size),
                bool(self.fit_global_orient), self.rho, None if self.sigma is None else float(self.sigma), bool(self.use_hint),
-               bool(self.record_history))
+               bool(self.record_history), self.model_to_scan,
+               id(self.vertex_weights) if self.vertex_weights is not None else None, self.max_distance, self.resolution)
         sess = self._sessions.get(key)
         if sess is not None:
             return key, sess
@@ -182,17 +209,35 @@ class ScanFitter:
                  weights=z(batch, num_points) if with_weights else None)
         smpl, model = self.smpl, self.model
         hint = t['hint'] if self.use_hint else None
+        cloud = vw = near = None
+        if self.model_to_scan > 0.0:
+            num_verts = int(smpl.v_template.shape[0])
+            if self.vertex_weights is not None:
+                if self.vertex_weights.dim() == 2 and self.vertex_weights.shape[0] != batch:
+                    raise ValueError('ScanFitter: vertex_weights are %s, the batch is %d'
+                                     % (tuple(self.vertex_weights.shape), batch))
+                vw = self.vertex_weights.detach().to(device=device, dtype=torch.float32).contiguous()
+            # (over the session's own buffers: rebuilt in place at the start of every call)
+            cloud = ops.PointCloud(t['points'], t['counts'], t['weights'], self.resolution)
+            t['near'] = z(batch, num_verts, dtype=torch.int32)
+            near = t['near'] if self.use_hint else None
 
         def iteration():
             out = smpl(global_orient=t['global_orient'], body_pose=t['body_pose'], betas=t['betas'])
             # (the hint tensor receives the new faces: the aliasing tuch_closest_point_hinted allows)
             total, _, _ = ops.scan_fit(model, out.vertices, t['transl'], t['points'], t['counts'], t['weights'], hint,
                                        self.rho, self.sigma, face_out=hint)
+            if cloud is not None:
+                # the two vertex gradients meet in autograd's accumulation (one add of [B,V,3])
+                other, _, _ = ops.cloud_fit(cloud, out.vertices, t['transl'], vw, near, self.rho, self.sigma,
+                                            self.max_distance, self.model_to_scan, index_out=near)
+                total = total + other
             return total, out.vertices
         params = [t['body_pose'], t['betas'], t['transl']] + ([t['global_orient']] if self.fit_global_orient else [])
         for p in params:
             p.requires_grad = True
-        sess = dict(t=t, stage=SMPLifyDC._Stage(self, 'fit', params, iteration, {}))
+        sess = dict(t=t, cloud=cloud, vertex_weights=vw, keys_alive=(self.vertex_weights,),
+                    stage=SMPLifyDC._Stage(self, 'fit', params, iteration, {}))
         return key, sess
 
     def __call__(self, points, global_orient, counts=None, weights=None, body_pose=None, betas=None, transl=None):
@@ -243,6 +288,9 @@ class ScanFitter:
                     centre = torch.where(wsum != 0, centre / torch.where(wsum != 0, wsum, torch.ones_like(wsum)),
                                          verts.mean(1))       # (a body without points stays where it is)
                     t['transl'].copy_(centre - verts.mean(1))
+                if sess['cloud'] is not None:
+                    sess['cloud'].rebuild(t['points'], t['counts'], t['weights'])
+                    t['near'].fill_(-1)                   # no memory of another call's answers
             captured = sess['stage'].run(self.num_iters, None, capture)
             # a captured loop is kept for the next call; a session that ran eagerly (or lost its capture) is dropped
             if not (captured and self.keep_sessions):
@@ -257,6 +305,12 @@ class ScanFitter:
                 _, loss, near = ops.scan_fit(self.model, verts, t['transl'], t['points'], t['counts'], t['weights'], hint,
                                              self.rho, self.sigma)
                 vertices = verts + t['transl'][:, None]
+                self.model_to_scan_result = None
+                if sess['cloud'] is not None:
+                    _, other, found = ops.cloud_fit(sess['cloud'], verts, t['transl'], sess['vertex_weights'],
+                                                    t['near'] if self.use_hint else None, self.rho, self.sigma,
+                                                    self.max_distance, self.model_to_scan)
+                    self.model_to_scan_result = CloudFit(other, found.d2, found.index)
             own = lambda x: x.detach().clone()
             return ScanFit(own(t['global_orient']), own(t['body_pose']), own(t['betas']), own(t['transl']), vertices, loss,
                            near.face, near.bary)

@@ -1582,6 +1582,244 @@ def scan_fit(model: ContactModel, verts, transl, points, counts=None, weights=No
     return total, per_body, ClosestPoint(d2, face, bary)
 
 
+class NearestPoint(NamedTuple):
+    d2: torch.Tensor
+    index: torch.Tensor
+
+
+class CloudGrid(NamedTuple):
+    """Host copies of a PointCloud's per-body headers: origin [B,3] float32, cell [B] float32, dims [B,3] int32."""
+    origin: np.ndarray
+    cell: np.ndarray
+    dims: np.ndarray
+
+
+def set_cloud_canary(on: bool) -> bool:
+    """Guard words behind the regions of every PointCloud workspace sized from now on (tuch_point_cloud_set_canary:
+    process-wide; set it before constructing the cloud).  Returns the previous setting."""
+    return bool(_C.lib().tuch_point_cloud_set_canary(int(bool(on))))
+
+
+class _CloudNearest(torch.autograd.Function):
+    """PointCloud.nearest: tuch_point_cloud_nearest forward; backward is 2 g (q - s) for queries and its sum over a body's
+    queries for shift, the index held fixed (a handful of element-wise torch ops: not on any loop's path -- the loops
+    use cloud_fit, whose gradients come out of the kernel)."""
+
+    @staticmethod
+    def forward(ctx, queries, shift, cloud, counts, hint, tau, index):
+        qs = _f32(queries)
+        sh = None if shift is None else _f32(shift)
+        b, n, _ = qs.shape
+        d2 = torch.empty(b, n, dtype=torch.float32, device=qs.device)
+        _C.check(_C.lib().tuch_point_cloud_nearest(
+            _C.ptr(cloud._ws), cloud._nbytes, _C.ptr(cloud.points), _C.ptr(cloud.counts), _C.ptr(cloud.weights), _C.ptr(qs),
+            _C.ptr(sh), _C.ptr(counts), _C.ptr(hint), tau, b, cloud.num_points, n, _C.ptr(d2), _C.ptr(index), _C.stream()))
+        ctx.save_for_backward(qs, sh, index)
+        ctx.cloud_points = cloud.points
+        ctx.in_dtypes = (queries.dtype, None if shift is None else shift.dtype)
+        return d2
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        qs, sh, index = ctx.saved_tensors
+        won = index >= 0
+        s = torch.gather(ctx.cloud_points, 1, index.clamp(min=0).long()[:, :, None].expand(-1, -1, 3))
+        q = qs if sh is None else qs + sh[:, None]
+        zero = torch.zeros((), dtype=torch.float32, device=qs.device)
+        gq = torch.where(won[:, :, None], 2.0 * g.to(torch.float32)[:, :, None] * (q - s), zero)
+        dq, ds = ctx.in_dtypes
+        return (gq.to(dq) if ctx.needs_input_grad[0] else None,
+                gq.sum(1).to(ds) if sh is not None and ctx.needs_input_grad[1] else None, None, None, None, None, None)
+
+
+class PointCloud:
+    """A batch of static point clouds with a uniform grid per body for exact nearest-point queries
+    (csrc/point_cloud.hip; the rule is in include/tuch_amd.h).  ``PointCloud(points [B,Q,3], counts=None, weights=None,
+    resolution=64)`` owns the workspace and builds on construction, on the current stream.  The cloud of body b is its
+    VALID points: index < counts[b], weight != 0, finite.  The tensors are kept by reference (float32 contiguous inputs
+    are not copied): change them in place and call ``rebuild()``.  There is no host fallback."""
+
+    def __init__(self, points, counts=None, weights=None, resolution=64):
+        if not (isinstance(resolution, int) and 1 <= resolution <= 256):
+            raise ValueError('PointCloud: resolution must be an int in 1 .. 256, got %r' % (resolution,))
+        self.resolution = resolution
+        self._ws = None
+        self.rebuild(points, counts, weights)
+
+    def rebuild(self, points, counts=None, weights=None):
+        """Build again, in place where the batch and point counts are unchanged (the workspace is kept): for a session
+        that keeps its buffers.  Capturable."""
+        if points.dim() != 3 or points.shape[2] != 3 or points.shape[0] == 0 or points.shape[1] == 0:
+            raise ValueError('PointCloud: points must be [B,Q,3] with B, Q > 0, got %s' % (tuple(points.shape),))
+        b, q = points.shape[0], points.shape[1]
+        if counts is not None and tuple(counts.shape) != (b,):
+            raise ValueError('PointCloud: counts must be [%d], got %s' % (b, tuple(counts.shape)))
+        if weights is not None and tuple(weights.shape) != (b, q):
+            raise ValueError('PointCloud: weights must be [%d,%d], got %s' % (b, q, tuple(weights.shape)))
+        _need_hip('PointCloud', points, counts, weights)
+        self.points = _f32(points)
+        self.counts = None if counts is None else counts.detach().to(torch.int32).contiguous()
+        self.weights = None if weights is None else _f32(weights)
+        L = _C.lib()
+        nbytes = L.tuch_point_cloud_workspace_bytes(b, q, self.resolution)
+        if self._ws is None or self._nbytes != nbytes or self._ws.device != points.device:
+            # (zeroed once: the first word counts changed guard words under the canary option)
+            self._ws = torch.zeros(max(int(nbytes), 1), dtype=torch.uint8, device=points.device)
+            self._nbytes = nbytes
+        self.batch, self.num_points = b, q
+        with torch.cuda.device(points.device):
+            _C.check(L.tuch_point_cloud_build(_C.ptr(self.points), _C.ptr(self.counts), _C.ptr(self.weights), b, q,
+                                              self.resolution, _C.ptr(self._ws), nbytes, _C.stream()))
+        return self
+
+    def _check_queries(self, what, queries, shift, hint, name='queries'):
+        if queries.dim() != 3 or queries.shape[0] != self.batch or queries.shape[2] != 3 or queries.shape[1] == 0:
+            raise ValueError('%s: %s must be [%d,N,3] with N > 0, got %s' % (what, name, self.batch, tuple(queries.shape)))
+        if shift is not None and tuple(shift.shape) != (self.batch, 3):
+            raise ValueError('%s: shift / transl has shape %s, expected %s' % (what, tuple(shift.shape), (self.batch, 3)))
+        _need_hip(what, queries, shift, hint)
+        if queries.device != self.points.device:
+            raise RuntimeError('%s: %s on %s, the cloud on %s' % (what, name, queries.device, self.points.device))
+        if hint is not None and (tuple(hint.shape) != tuple(queries.shape[:2]) or hint.dtype != torch.int32
+                                 or not hint.is_contiguous()):
+            raise ValueError('%s: hint must be a contiguous int32 %s tensor' % (what, tuple(queries.shape[:2])))
+
+    def nearest(self, queries, shift=None, counts=None, hint=None, max_distance=None, index_out=None) -> NearestPoint:
+        """For every real query ``queries[b,n] + shift[b]`` the nearest valid point of body b's cloud:
+        ``NearestPoint(d2 [B,N], index [B,N] int32)``; no winner: index -1, d2 +inf.  counts [B]: real queries per body;
+        hint [B,N] int32: a guess per query that changes no bit of any result (it may be ``index_out``, the tensor the
+        indices are written to); max_distance tau > 0: only points with d2 <= f32(tau)^2 can win.  d2 is differentiable
+        w.r.t. queries and shift with the index held fixed."""
+        self._check_queries('PointCloud.nearest', queries, shift, hint)
+        b, n = queries.shape[0], queries.shape[1]
+        if counts is not None and tuple(counts.shape) != (b,):
+            raise ValueError('PointCloud.nearest: counts must be [%d], got %s' % (b, tuple(counts.shape)))
+        tau = _tau_of('PointCloud.nearest', max_distance)
+        _need_hip('PointCloud.nearest', counts, index_out)
+        index = _index_out('PointCloud.nearest', index_out, b, n, queries.device)
+        counts = None if counts is None else counts.to(torch.int32).contiguous()
+        d2 = _CloudNearest.apply(queries, shift, self, counts, hint, tau, index)
+        return NearestPoint(d2, index)
+
+    def grid(self) -> CloudGrid:
+        """The headers the build wrote, as host arrays (synchronises; for tests and tools)."""
+        origin = np.empty((self.batch, 3), np.float32)
+        cell = np.empty(self.batch, np.float32)
+        dims = np.empty((self.batch, 3), np.int32)
+        as_p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        with torch.cuda.device(self.points.device):
+            _C.check(_C.lib().tuch_point_cloud_grid(_C.ptr(self._ws), self.batch, self.resolution, as_p(origin), as_p(cell),
+                                                    as_p(dims)))
+        return CloudGrid(origin, cell, dims)
+
+    def canary_hits(self, reset: bool = True) -> int:
+        """Guard words of this cloud's workspace (and of the term's scratch) found changed (set_cloud_canary)."""
+        out = ctypes.c_int(0)
+        with torch.cuda.device(self.points.device):
+            _C.check(_C.lib().tuch_point_cloud_canary_hits(_C.ptr(self._ws), ctypes.byref(out), int(reset)))
+        return out.value
+
+
+def _tau_of(what, max_distance) -> float:
+    if max_distance is None:
+        return 0.0
+    tau = float(max_distance)
+    if not tau > 0.0:
+        raise ValueError('%s: max_distance must be > 0 (or None), got %r' % (what, max_distance))
+    return tau
+
+
+def _index_out(what, index_out, b, n, device):
+    if index_out is None:
+        return torch.empty(b, n, dtype=torch.int32, device=device)
+    if tuple(index_out.shape) != (b, n) or index_out.dtype != torch.int32 or not index_out.is_contiguous():
+        raise ValueError('%s: index_out must be a contiguous int32 [%d,%d] tensor' % (what, b, n))
+    return index_out
+
+
+class _CloudFit(torch.autograd.Function):
+    """ops.cloud_fit: the query, the term and the unit gradients in one launch (tuch_point_cloud_fit_terms).  `index`
+    [B,V] int32 is written in place (it may be the hint tensor).  backward() only hands the gradients over, as
+    _ScanFit's."""
+
+    @staticmethod
+    def forward(ctx, verts, transl, cloud, vw, layout, hint, rho, sigma, tau, scale, index):
+        v, tr = _f32(verts), _f32(transl)
+        b, n, _ = v.shape
+        dev = v.device
+        L = _C.lib()
+        d2 = torch.empty(b, n, dtype=torch.float32, device=dev)
+        per_body = torch.empty(b, dtype=torch.float32, device=dev)
+        out = torch.empty(1, dtype=torch.float32, device=dev)
+        gv = torch.empty_like(v)
+        gt = torch.empty(b, 3, dtype=torch.float32, device=dev)
+        nbytes = L.tuch_point_cloud_fit_scratch_bytes(b, n)
+        scratch = _workspace(nbytes, dev)
+        _C.check(L.tuch_point_cloud_fit_terms(
+            _C.ptr(cloud._ws), cloud._nbytes, _C.ptr(cloud.points), _C.ptr(cloud.counts), _C.ptr(cloud.weights), _C.ptr(v),
+            _C.ptr(tr), _C.ptr(hint), tau, b, cloud.num_points, n, _C.ptr(vw), layout, rho, sigma, scale, _C.ptr(d2),
+            _C.ptr(index), _C.ptr(_ticket(dev)), _C.ptr(per_body), _C.ptr(out), _C.ptr(gv), _C.ptr(gt), _C.ptr(scratch),
+            nbytes, _C.stream()))
+        ctx.save_for_backward(gv, gt)
+        ctx.in_dtypes = (verts.dtype, transl.dtype)
+        ctx.mark_non_differentiable(per_body, d2)
+        ctx.set_materialize_grads(False)
+        return out[0], per_body, d2
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, *_others):
+        if g is None:
+            return (None,) * 11
+        gv, gt = ctx.saved_tensors
+        if not backward_pass.is_unit_seed(g):
+            g = g.reshape(()).to(torch.float32)
+            gv, gt = gv * g, gt * g
+        dv, dt = ctx.in_dtypes
+        return (gv.to(dv), gt.to(dt)) + (None,) * 9
+
+
+def cloud_fit(cloud: PointCloud, verts, transl, vertex_weights=None, hint=None, rho='distance', sigma=None,
+              max_distance=None, scale=1.0, index_out=None):
+    """Model -> scan data term of a two-sided fit: ``(total, per_body, NearestPoint)``.  The queries are ``verts[b,v] +
+    transl[b]`` against ``cloud``; the NearestPoint has the bits of ``cloud.nearest(verts, transl, hint=hint,
+    max_distance=max_distance)`` (a vertex of weight 0 is not computed from: -1 / +inf).  per_body[b] = scale sum_v w_v
+    rho(d2_v) / sum_v w_v with vertex_weights [V], [B,V] or None (ones) and rho / sigma as in ``scan_fit``; a vertex
+    without winner contributes rho(tau^2) under max_distance tau when the body's cloud is not empty, else 0; total is
+    their sum over the bodies, differentiable w.r.t. verts and transl with the nearest point held fixed (there is no
+    gradient w.r.t. the cloud's points: they are data).  Every sum is fixed-order: the same bits on every call, in
+    either mode of ``deterministic()``, for a body alone or in a batch.  hint / index_out as in ``PointCloud.nearest``.
+    There is no host fallback."""
+    if not isinstance(cloud, PointCloud):
+        raise ValueError('cloud_fit: cloud must be a PointCloud, got %r' % type(cloud).__name__)
+    if rho not in SCAN_RHO:
+        raise ValueError('cloud_fit: rho must be one of %s, got %r' % (sorted(SCAN_RHO), rho))
+    if rho == 'gmof' and not (sigma is not None and float(sigma) > 0.0):
+        raise ValueError("cloud_fit: rho='gmof' needs sigma > 0, got %r" % (sigma,))
+    if transl is None or tuple(transl.shape) != (cloud.batch, 3):
+        raise ValueError('cloud_fit: transl must be [%d,3], got %s'
+                         % (cloud.batch, None if transl is None else tuple(transl.shape)))
+    cloud._check_queries('cloud_fit', verts, transl, hint, name='verts')
+    b, n = verts.shape[0], verts.shape[1]
+    layout, vw = 0, None
+    if vertex_weights is not None:
+        if tuple(vertex_weights.shape) == (n,):
+            layout = 1
+        elif tuple(vertex_weights.shape) == (b, n):
+            layout = 2
+        else:
+            raise ValueError('cloud_fit: vertex_weights must be [%d] or [%d,%d], got %s' % (n, b, n, tuple(vertex_weights.shape)))
+        _need_hip('cloud_fit', vertex_weights)
+        vw = _f32(vertex_weights)
+    tau = _tau_of('cloud_fit', max_distance)
+    _need_hip('cloud_fit', index_out)
+    index = _index_out('cloud_fit', index_out, b, n, verts.device)
+    total, per_body, d2 = _CloudFit.apply(verts, transl, cloud, vw, layout, hint, SCAN_RHO[rho],
+                                          float(sigma) if sigma is not None else 0.0, tau, float(scale), index)
+    return total, per_body, NearestPoint(d2, index)
+
+
 class HDModel:
     """Device tables of the HD vertex regressor for the fused HD branch (wraps tuch_hd_model; csrc/hd_contact.hip).
     hd_idx / hd_w [N,K]: the K <= 8 non-zeros of every regressor row (K = 3: barycentric samples); hd_face [N]:
