@@ -296,6 +296,30 @@ int tuch_winding_tree_work(const tuch_contact_model* model, const float* verts, 
  * listed, wavefronts}: [1] / [2] is the share of lanes that can have a crossing at all.  Workspace as for tuch_exterior_flags.  Synchronises the stream. */
 int tuch_ray_work(const tuch_contact_model* model, const float* verts, int B, void* workspace,
                   size_t workspace_bytes, unsigned long long* out_host, void* stream);
+/* FOR THE TESTS ONLY (tests/test_near_encode.py, tests/test_gpu_near_lists.py): the numbers and the lists of the inside
+ * test's near stage (csrc/ray_winding.hip: ray_leaf_bounds_kernel, ray_near_kernel).
+ * tuch_near_encode_host runs the kernels' own conversion of a single-precision value to the near test's signed 16-bit
+ * fixed point on the HOST (no GPU needed): round_up != 0 the smallest level >= value, otherwise the largest level <= value,
+ * saturating (NaN: +32767 rounding up, -32768 rounding down).  *out = the level, value * 8192 rounded. */
+int tuch_near_encode_host(float value, int round_up, int* out);
+/* tuch_ray_near_debug runs the two kernels as a call of tuch_exterior_flags (points == NULL: the model's vertices) or of
+ * tuch_winding_points (points [B,Q,3], counts [B] or NULL) does and copies out (device pointers, each may be NULL), with
+ * L = dims_host[0] leaves and N = dims_host[1] query blocks of 64 slots:
+ *   out_bounds  [B][13][L] float : the padded single-precision bounds as formed before encoding, in the order of the
+ *                                  record's halves: lower bounds of the slabs x y x+y x-y x-z y-z, upper bounds of x y z
+ *                                  x+y x-y x+z y+z (sheared frame, relative to the body's reference point);
+ *   out_records [B][L][8] uint32 : the encoded records (13 halves, the leaf number, the node);
+ *   out_rays    [B][N*64][9] float : x y z x+y x-y x+z x-z y+z y-z of every query slot (slots of blocks behind a body's
+ *                                  last point are left as they were);
+ *   out_bitmap  [B][L][N*8] uint8 : bit (slot & 7) of byte (slot >> 3) set where (leaf, slot) is listed;
+ *   out_leaves  [B][N][L] int32  : the leaves of every block's list in list order, -1 behind its end;
+ *   out_len     [B][N] int32     : the lists' lengths.
+ * waves: 0 the form the step would take for these sizes, 1 / 4 wavefronts per query block.  dims_host[2] = the workspace
+ * bytes needed; verts == NULL: only dims_host is filled.  Not on any timed path. */
+int tuch_ray_near_debug(const tuch_contact_model* model, const float* verts, const float* points, const int32_t* counts,
+                        int B, int Q, int waves, void* workspace, size_t workspace_bytes, long long* dims_host,
+                        float* out_bounds, uint32_t* out_records, float* out_rays, uint8_t* out_bitmap,
+                        int32_t* out_leaves, int32_t* out_len, void* stream);
 /* The cluster tree the model built for itself: qperm_host [V] = vertices in tree order, face_leaf_host [F] = leaf
  * (preorder sequence number) of every face; either may be NULL.  Fails when the model has no tree. */
 int tuch_contact_model_tree_order(const tuch_contact_model* model, int32_t* qperm_host, int32_t* face_leaf_host);

@@ -102,6 +102,8 @@ _SIGNATURES = {
     'tuch_hd_contact_details': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     'tuch_ray_work': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
     'tuch_contact_model_tree_order': (c_int, [c_void_p, c_void_p, c_void_p]),
+    'tuch_near_encode_host': (c_int, [c_float, c_int, POINTER(c_int)]),
+    'tuch_ray_near_debug': (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_void_p, c_size_t] + [c_void_p] * 8),
     'tuch_v2v_model_workspace_bytes': (c_size_t, [c_void_p, c_int]),
     'tuch_v2v_hint_bytes': (c_size_t, [c_void_p, c_int]),
     'tuch_v2v_min_model': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int,

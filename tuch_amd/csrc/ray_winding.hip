@@ -102,20 +102,30 @@ __device__ __forceinline__ float row_min(float v)
 // kPose: the kernel also WRITES the sheared strip (each 16-lane group poses the run of its own leaf; the leaves' runs
 // tile the stream, checked at model creation) and clears the counters of the kernels that follow -- ray_stream_kernel's
 // work, without a launch of its own ahead of this one on the step's serial chain.
-// bits of the largest half-precision number <= x / the smallest >= x (|x| beyond the half range saturates outwards)
-__device__ __forceinline__ uint32_t half_below(float x)
+// ---- the near test's numbers: signed 16-bit fixed point ------------------------------------------------------------------
+// Both sides of the near test (ray_near_kernel) -- a leaf's 13 bounds and a ray's nine values, all relative to the body's
+// reference point -- are levels k / kNearScale, k in [-32768, 32767]: steps of 2^-13 m over [-4 m, 4 m).  (Half precision
+// on the bounds alone steps by 2^-10 m beyond 1 m from the reference point; tools/diag/near_encode_sim.py counts the pairs
+// listed with either)  up: the smallest level >= v, otherwise the largest level <= v; where no such level
+// exists, and for NaN, the end of the range on that side: +32767 rounding up, -32768 rounding down.  A number that is
+// rounded UP is only ever the right-hand side of a `bound > value` rejection (an upper bound, or a ray's value set against a
+// lower bound), one rounded DOWN only the left-hand side -- so those two codes can never reject.  The conversion is
+// monotone: v <= w implies near_encode(v) <= near_encode(w) in either direction (NaN aside).
+constexpr float kNearScale = 8192.0f;
+constexpr int kNearMin = -32768, kNearMax = 32767;
+__host__ __device__ __forceinline__ int near_encode(float v, bool up)
 {
-    const _Float16 h = (_Float16)x;
-    uint32_t u = __builtin_bit_cast(uint16_t, h);
-    if ((float)h > x) u = (u & 0x8000u) ? u + 1 : (u == 0 ? 0x8001u : u - 1);
-    return u;
+    const float t = v * kNearScale;                 // exact (a power of two), +-inf beyond the float range
+    if (up) {
+        const float c = __builtin_ceilf(t);
+        return !(c <= (float)kNearMax) ? kNearMax : c < (float)kNearMin ? kNearMin : (int)c;       // NaN: kNearMax
+    }
+    const float c = __builtin_floorf(t);
+    return !(c >= (float)kNearMin) ? kNearMin : c > (float)kNearMax ? kNearMax : (int)c;           // NaN: kNearMin
 }
-__device__ __forceinline__ uint32_t half_above(float x)
+__host__ __device__ __forceinline__ uint32_t near_pack(int lo_half, int hi_half)
 {
-    const _Float16 h = (_Float16)x;
-    uint32_t u = __builtin_bit_cast(uint16_t, h);
-    if ((float)h < x) u = (u & 0x8000u) ? (u == 0x8000u ? 0x0001u : u - 1) : u + 1;
-    return u;
+    return ((uint32_t)lo_half & 0xffffu) | (uint32_t)hi_half << 16;
 }
 // where the tables of one call's `bounds` region start (floats): [B][13][L] | records [B][L][8 dwords] | centres [B][4]
 __device__ __host__ __forceinline__ size_t near_records_at(int B, int L) { return (size_t)B * kNearSlabs * L; }
@@ -153,7 +163,7 @@ __global__ __launch_bounds__(kBoundsBlock) void ray_leaf_bounds_kernel(
     const RayElem* __restrict__ stream, int T, const TreeNode* __restrict__ nodes, int N,
     const int32_t* __restrict__ height_off, const int32_t* __restrict__ height_nodes, float* __restrict__ bounds,
     const float* __restrict__ verts, const int32_t* __restrict__ vidx, const float* __restrict__ sign, int V, int Lexact,
-    RayElem* __restrict__ stream_out, uint4* __restrict__ zeroed, size_t zeroed_n, float4* __restrict__ boxes)
+    RayElem* __restrict__ stream_out, uint4* __restrict__ zeroed, size_t zeroed_n, float4* __restrict__ boxes, int keep_bounds)
 {
     const int b = blockIdx.y;
     const RayElem* st = stream + (size_t)b * T;
@@ -210,7 +220,7 @@ __global__ __launch_bounds__(kBoundsBlock) void ray_leaf_bounds_kernel(
             lo_p[k] = lo[k] - pad;
             hi_p[k] = hi + pad;
         }
-        // ... as the 32-byte RECORD both stages of the near test read: half precision, relative to a
+        // ... as the 32-byte RECORD both stages of the near test read: 16-bit fixed point (near_encode), relative to a
         // reference point of the body (the first element of its strip, so that the numbers stay small wherever the body
         // stands), lower bounds rounded down and upper bounds up after a pad for the roundings of the subtraction.
         float c[3];
@@ -223,16 +233,25 @@ __global__ __launch_bounds__(kBoundsBlock) void ray_leaf_bounds_kernel(
         }
         float pc[kSlabs];
         slab_project(c[0], c[1], c[2], pc);
-        uint32_t lo_h[kSlabs], hi_h[kSlabs];
+        float lo_r[kSlabs], hi_r[kSlabs];
+        int lo_h[kSlabs], hi_h[kSlabs];
 #pragma unroll
         for (int k = 0; k < kSlabs; ++k) {
             const float pad = 4e-6f * (fabsf(lo_p[k]) + fabsf(hi_p[k]) + fabsf(pc[k])) + 1e-7f;
-            lo_h[k] = half_below(lo_p[k] - pc[k] - pad);
-            hi_h[k] = half_above(hi_p[k] - pc[k] + pad);
+            lo_r[k] = lo_p[k] - pc[k] - pad;
+            hi_r[k] = hi_p[k] - pc[k] + pad;
+            lo_h[k] = near_encode(lo_r[k], false);
+            hi_h[k] = near_encode(hi_r[k], true);
         }
         uint4* r = reinterpret_cast<uint4*>(bounds + near_records_at(gridDim.y, L)) + ((size_t)b * L + leaf) * 2;
-        r[0] = make_uint4(lo_h[0] | lo_h[1] << 16, lo_h[3] | lo_h[4] << 16, lo_h[6] | lo_h[8] << 16, hi_h[0] | hi_h[1] << 16);
-        r[1] = make_uint4(hi_h[2] | hi_h[3] << 16, hi_h[4] | hi_h[5] << 16, hi_h[7] | (uint32_t)leaf << 16, (uint32_t)node);  // + who it is
+        r[0] = make_uint4(near_pack(lo_h[0], lo_h[1]), near_pack(lo_h[3], lo_h[4]), near_pack(lo_h[6], lo_h[8]), near_pack(hi_h[0], hi_h[1]));
+        r[1] = make_uint4(near_pack(hi_h[2], hi_h[3]), near_pack(hi_h[4], hi_h[5]), near_pack(hi_h[7], leaf), (uint32_t)node);  // + who it is
+        if (keep_bounds) {      // tuch_ray_near_debug: the 13 single-precision bounds behind the record, in the order of its halves
+            float* o = bounds + ((size_t)b * kNearSlabs) * L + leaf;
+            const float v[kNearSlabs] = {lo_r[0], lo_r[1], lo_r[3], lo_r[4], lo_r[6], lo_r[8], hi_r[0], hi_r[1], hi_r[2], hi_r[3], hi_r[4], hi_r[5], hi_r[7]};
+#pragma unroll
+            for (int k = 0; k < kNearSlabs; ++k) o[(size_t)k * L] = v[k];
+        }
         if (leaf == 0) *reinterpret_cast<float4*>(bounds + near_centres_at(gridDim.y, L) + (size_t)b * 4) = make_float4(c[0], c[1], c[2], 0.f);
     }
 }
@@ -554,42 +573,41 @@ __device__ __forceinline__ void ray_flush(RayQueue& q, uint32_t& head, uint32_t 
 // descent: with ~215 leaves the flat test is four rounds of 64 lanes, and nothing in it waits on a parent's verdict.
 constexpr int kFallbackChunks = 8;            // wavefronts per query block when a body falls back to block-major order
 
-__device__ __forceinline__ float wave_min(float v) { return wave_min_uniform(v); }      // common.h: DPP, no LDS trips
-__device__ __forceinline__ float wave_max(float v) { return wave_max_uniform(v); }
+__device__ __forceinline__ int wave_min_i32(int v)                                      // as common.h's wave_max_uniform_i32
+{
+    TUCH_WAVE_REDUCE("v_min_i32_dpp");
+    return __builtin_amdgcn_readlane(v, 63);
+}
+__device__ __forceinline__ int wave_max_i32(int v) { return wave_max_uniform_i32(v); }
+// v_writelane_b32: `old` with lane `lane` (wave-uniform) replaced by the wave-uniform `value`.  Declared by the intrinsic's own
+// name (clang has no builtin for it), so that the compiler sees it and keeps the wait states behind a compare
+extern "C" __device__ int tuch_writelane(int value, int lane, int old) __asm("llvm.amdgcn.writelane.i32");
 
 // One (query block, leaf) the block has to visit: which of its 64 rays pass the leaf's slabs.
 // (RayEntry, RayTile, RayBody: model.h)
 
-// (half in the low / high 16 bits of s) - q and q - (half of s) in single precision, one instruction each; the largest of three
-__device__ __forceinline__ float lo_minus(uint32_t s, float q)
+// ---- the 13-slab test on packed 16-bit levels -------------------------------------------------------------------------------
+// record (ray_leaf_bounds_kernel): s0 = (lo0,lo1) (lo3,lo4) (lo6,lo8) (hi0,hi1)   s1 = (hi2,hi3) (hi4,hi5) (hi7,leaf) node
+// with the slabs 0..8 = x y z x+y x-y x+z x-z y+z y-z.  A ray (or a block's range) is the seven dwords that pair up with
+// them: u* hold the values set against LOWER bounds, rounded UP (the block: their maxima), d* those set against UPPER
+// bounds, rounded DOWN (the block: their minima); the upper half of d3 faces the record's leaf number and holds kNearMin.
+struct NearSide { uint32_t u0, u1, u2, d0, d1, d2, d3; };
+typedef short near_s16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t pk_sub_sat(uint32_t a, uint32_t b)      // v_pk_sub_i16 ... clamp: a - b per half, saturating
 {
-    float d;
-    asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel_hi:[1,0,0]" : "=v"(d) : "v"(s), "v"(q));
-    return d;
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_sub_sat(__builtin_bit_cast(near_s16x2, a), __builtin_bit_cast(near_s16x2, b)));
 }
-__device__ __forceinline__ float hi_minus(uint32_t s, float q)
+// Outside some slab: lo > u or d > hi for one of the 13 pairs, i.e. one of the saturating differences u - lo, hi - d is
+// NEGATIVE (a saturating difference has the sign of the exact one; 0 passes).  Seven packed subtractions, the sign bits
+// gathered by three 3-input ORs and one AND: 12 vector instructions with the compare, where 13 single-precision
+// differences (v_fma_mix_f32) under six v_max3_f32 were 20.  leaf - kNearMin >= 0 for every 16-bit leaf: the 14th half
+// never rejects.  One routine for both stages: stage 1 passes the block's ranges as `r` (wave-uniform) with 64 records in
+// the lanes, stage 2 the lanes' rays with one record.
+__device__ __forceinline__ bool near_outside(const uint4& s0, const uint4& s1, const NearSide& r)
 {
-    float d;
-    asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(s), "v"(q));
-    return d;
-}
-__device__ __forceinline__ float minus_lo(float q, uint32_t s)
-{
-    float d;
-    asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(d) : "v"(s), "v"(q));
-    return d;
-}
-__device__ __forceinline__ float minus_hi(float q, uint32_t s)
-{
-    float d;
-    asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(s), "v"(q));
-    return d;
-}
-__device__ __forceinline__ float max3(float a, float b, float c)
-{
-    float d;
-    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-    return d;
+    const uint32_t neg = pk_sub_sat(r.u0, s0.x) | pk_sub_sat(r.u1, s0.y) | pk_sub_sat(r.u2, s0.z) | pk_sub_sat(s0.w, r.d0) |
+                         pk_sub_sat(s1.x, r.d1) | pk_sub_sat(s1.y, r.d2) | pk_sub_sat(s1.z, r.d3);
+    return (neg & 0x80008000u) != 0u;
 }
 // One unit of work of ray_leaf_kernel: up to 64 rays (pairs[first .. first + n)) against one leaf's strip run.
 // per body: number of tiles, whether the pair list overflowed (the body is then walked block-major)
@@ -599,27 +617,51 @@ __device__ __forceinline__ float max3(float a, float b, float c)
 //   rounds : the wavefronts take one chunk of 64 leaves each, lanes over LEAVES: block ranges against the slabs
 //            (stage 1); the records of the passing leaves go to a queue in LDS; the queue is then dealt out evenly,
 //            two entries per wavefront and trip: every ray against the record (stage 2).
-// A trip of stage 2 is a dependent chain (LDS read -> 19 VALU -> ballot -> branch, ~450 clocks measured with the cycle
-// counter) and the blocks through the trunk pass five times the average number of leaves: the time of the kernel is
-// that of its slowest workgroup plus the rounds of workgroups the chip needs.  With one wavefront testing a block's
-// leaves one at a time it was 59 us at batch 64 and 41 us at batch 8.  Four wavefronts and two chains per trip: 16 us
-// at batch 8.  At batch 64 the search runs beside this kernel on another stream and leaves 7 wave slots and < 4 KB of
+// A trip of stage 2 is a dependent chain (LDS read -> test -> compare -> hand-over; ~450 clocks measured with the cycle
+// counter when the test was 19 single-precision instructions) and the blocks through the trunk pass five times the
+// average number of leaves: the time of the kernel is that of its slowest workgroup plus the rounds of workgroups the chip
+// needs -- at batch 64, with 6.75 wavefronts resident per SIMD, the vector instructions of its heaviest SIMDs.  With one
+// wavefront testing a block's leaves one at a time it was 59 us at batch 64 and 41 us at batch 8.  Four wavefronts and
+// two chains per trip: 16 us at batch 8 (10 us with the packed test).  At batch 64 the search runs beside this kernel on another stream and leaves 7 wave slots and < 4 KB of
 // LDS per CU (v2v.hip, leave_room): there the one-wavefront form (2 KB) is used -- workgroups of four with an 8 KB
 // queue waited for LDS until the search had drained (202 us, tools/graph_timeline.py).
+//
+// THE NUMBERS.  Records and rays are near_encode levels (16-bit fixed point, one scale).  ray_leaf_bounds_kernel forms the
+// padded single-precision bounds lo, hi of a leaf relative to the body's reference point -- the numbers the test trusted
+// when it compared in single precision -- and stores floor(lo S), ceil(hi S); this kernel forms the rays' nine values r in
+// single precision as it always did and converts each ONCE per wavefront: ceil(r S) where it meets a lower bound,
+// floor(r S) where it meets an upper bound, every conversion saturating to the code that cannot reject.
+// NO PAIR IS DROPPED: a rejection is lo_fx > up(r) (or dn(r) > hi_fx, its mirror image).  A lo_fx that saturated to kNearMin
+// exceeds nothing and an up(r) that saturated to kNearMax is exceeded by nothing; in every other case lo_fx <= lo S and
+// up(r) >= r S (a clamp from the far side moves a level the same way as its rounding).  So lo_fx > up(r) implies
+// lo S > r S, lo > r: the single-precision
+// bound, whose pads cover the roundings of the projections and are unchanged, rejects as well.  Directed, monotone,
+// saturating conversion can only turn a rejection into a pass.  The lists are a superset of the pairs that can cross; the
+// walk filters every (ray, element) by its box and then tests exactly (ray_exact), so an extra pair costs lanes, never a
+// count: crossing counts and flags are what they were, bit for bit.
+// STAGE 1 IS A SUPERSET OF STAGE 2: the block's side holds, half by half, the maximum of the lanes' u-levels and the
+// minimum of their d-levels (padding lanes repeat a real query), both stages run near_outside on the same record, and a
+// saturating difference is monotone in either operand: u_block - lo >= u_ray - lo and hi - d_block >= hi - d_ray.  A
+// negative difference in stage 1 is therefore negative for every ray; a leaf that some ray passes in stage 2 passed stage 1.
+// ENTRIES ARE WRITTEN BY LANES: a stage-2 trip leaves its hit masks (wave-uniform) in the lanes that own the trip's queue
+// positions (v_writelane); after the round's trips every owner of a non-empty mask takes the next slot in queue order and
+// writes its entry and its leaf's ray count: one store and one atomic INSTRUCTION per round, where every hit had its own
+// single-lane region.  Queue order is leaf order, so a one-wavefront block's list ascends in the leaf number.
 template <bool kVerts, int kWaves>
 __global__ __launch_bounds__(64 * kWaves) void ray_near_kernel(
     const float* __restrict__ pts, const TreeNode* __restrict__ nodes, const float* __restrict__ bounds, int N,
     int num_leaves, const int32_t* __restrict__ qperm,
     const int32_t* __restrict__ counts, int Q, int qblocks, RayEntry* __restrict__ lists, int32_t* __restrict__ list_len,
     int32_t* __restrict__ leaf_cnt,             // [B][num_leaves], zeroed: rays per leaf
-    unsigned long long* __restrict__ stats)     // measurement (or nullptr): [1] += (ray, element) pairs inside a listed
+    unsigned long long* __restrict__ stats,     // measurement (or nullptr): [1] += (ray, element) pairs inside a listed
                                                 // leaf's slabs, [2] += 64 x elements listed
+    float* __restrict__ rays_out)               // tuch_ray_near_debug (or nullptr): [B][qblocks * 64][9], the rays' values
 {
     __builtin_amdgcn_s_setprio(3);               // (see ray_tiles_fill_kernel)
     const int qb = blockIdx.x, b = blockIdx.y, lane = threadIdx.x & 63;
     const int wave = kWaves > 1 ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : 0;
     __shared__ uint4 queue[64 * kWaves][2];     // records of the round's leaves that passed stage 1
-    __shared__ float range[16];
+    __shared__ int range[16];
     __shared__ int queued[2], slots;            // queue entries (rounds in turn); list entries written (slots are taken from it)
     int i0;
     bool real;                                  // padding lanes repeat a query; they are left out of the masks
@@ -636,14 +678,14 @@ __global__ __launch_bounds__(64 * kWaves) void ray_near_kernel(
         real = qb * kRayQueries + lane < n;
     }
     if (threadIdx.x == 0) { queued[0] = 0; queued[1] = 0; slots = 0; }
-    // every load that does not wait for the block's ranges is issued here: the body's reference point and the slab
-    // values / records of the wavefront's first chunk of leaves
+    const unsigned long long real_mask = __builtin_amdgcn_ballot_w64(real);
+    // every load that does not wait for the block's ranges is issued here: the body's reference point and the
+    // records of the wavefront's first chunk of leaves
     const float4 ctr = *reinterpret_cast<const float4*>(bounds + near_centres_at(gridDim.y, num_leaves) + (size_t)b * 4);
     const uint4* recs = reinterpret_cast<const uint4*>(bounds + near_records_at(gridDim.y, num_leaves)) + (size_t)b * num_leaves * 2;
-    // stage 1 reads the leaves' 32-byte RECORDS only (half precision, relative to the body's reference point, bounds rounded
-    // outwards: what stage 2 tests every ray against) -- with the 13 single-precision slab values beside them every
-    // block fetched 84 bytes per leaf, 257 MB per launch at batch 64 out of the L2s: the kernel's time.  A leaf that some
-    // ray passes in stage 2 passes stage 1 (the block's range holds the ray's value, the record is the same).
+    // stage 1 reads the leaves' 32-byte RECORDS only (what stage 2 tests every ray against) -- with 13 single-precision
+    // slab values beside them every block fetched 84 bytes per leaf, 257 MB per launch at batch 64 out of the L2s: the
+    // kernel's time then.
     struct Chunk { uint4 r0, r1; };
     auto load_chunk = [&](int base) {
         Chunk c;
@@ -659,62 +701,51 @@ __global__ __launch_bounds__(64 * kWaves) void ray_near_kernel(
     // the queries relative to the body's reference point, as the records are
     const float rx = qx - ctr.x, ry = qy - ctr.y, rz = qz - ctr.z;
     const float r4 = rx + ry, r5 = rx - ry, r6 = rx + rz, r7 = rx - rz, r8 = ry + rz, r9 = ry - rz;
-    // the block's ranges of these nine values, the side each record bound is compared with
-    float bx0, bx1, by0, by1, b40, b41, b50, b51, bz0, b60, b71, b80, b91;
+    if (rays_out && wave == 0) {
+        float* o = rays_out + (((size_t)b * qblocks + qb) * kRayQueries + lane) * 9;
+        o[0] = rx; o[1] = ry; o[2] = rz; o[3] = r4; o[4] = r5; o[5] = r6; o[6] = r7; o[7] = r8; o[8] = r9;
+    }
+    // ... as levels, once per wavefront: up against the lower bounds, down against the upper bounds
+    const int ux = near_encode(rx, true), uy = near_encode(ry, true), u4 = near_encode(r4, true), u5 = near_encode(r5, true);
+    const int u7 = near_encode(r7, true), u9 = near_encode(r9, true);
+    const int dx = near_encode(rx, false), dy = near_encode(ry, false), dz = near_encode(rz, false), d4 = near_encode(r4, false);
+    const int d5 = near_encode(r5, false), d6 = near_encode(r6, false), d8 = near_encode(r8, false);
+    const NearSide me = {near_pack(ux, uy), near_pack(u4, u5), near_pack(u7, u9), near_pack(dx, dy),
+                         near_pack(dz, d4), near_pack(d5, d6), near_pack(d8, kNearMin)};
+    // the block's side: the largest u and the smallest d of its lanes (integers: a NaN query is a saturated level here)
+    NearSide blk;
     if (kWaves == 4) {
         if (wave == 0) {
-            const float a = wave_min(rx), c = wave_max(rx), d = wave_min(ry), e = wave_max(ry);
+            const int a = wave_max_i32(ux), c = wave_max_i32(uy), d = wave_min_i32(dx), e = wave_min_i32(dy);
             if (lane == 0) { range[0] = a; range[1] = c; range[2] = d; range[3] = e; }
         } else if (wave == 1) {
-            const float a = wave_min(r4), c = wave_max(r4), d = wave_min(r5), e = wave_max(r5);
+            const int a = wave_max_i32(u4), c = wave_max_i32(u5), d = wave_min_i32(d4), e = wave_min_i32(d5);
             if (lane == 0) { range[4] = a; range[5] = c; range[6] = d; range[7] = e; }
         } else if (wave == 2) {
-            const float a = wave_min(rz), c = wave_min(r6), d = wave_max(r7);
+            const int a = wave_min_i32(dz), c = wave_min_i32(d6), d = wave_max_i32(u7);
             if (lane == 0) { range[8] = a; range[9] = c; range[10] = d; }
         } else {
-            const float a = wave_min(r8), c = wave_max(r9);
+            const int a = wave_min_i32(d8), c = wave_max_i32(u9);
             if (lane == 0) { range[11] = a; range[12] = c; }
         }
         __syncthreads();
-        bx0 = range[0]; bx1 = range[1]; by0 = range[2]; by1 = range[3]; b40 = range[4]; b41 = range[5]; b50 = range[6];
-        b51 = range[7]; bz0 = range[8]; b60 = range[9]; b71 = range[10]; b80 = range[11]; b91 = range[12];
+        auto at = [&](int k) { return __builtin_amdgcn_readfirstlane(range[k]); };
+        blk = NearSide{near_pack(at(0), at(1)), near_pack(at(4), at(5)), near_pack(at(10), at(12)), near_pack(at(2), at(3)),
+                       near_pack(at(8), at(6)), near_pack(at(7), at(9)), near_pack(at(11), kNearMin)};
     } else {
-        bx0 = wave_min(rx); bx1 = wave_max(rx); by0 = wave_min(ry); by1 = wave_max(ry);
-        b40 = wave_min(r4); b41 = wave_max(r4); b50 = wave_min(r5); b51 = wave_max(r5);
-        bz0 = wave_min(rz); b60 = wave_min(r6); b71 = wave_max(r7); b80 = wave_min(r8); b91 = wave_max(r9);
+        blk = NearSide{near_pack(wave_max_i32(ux), wave_max_i32(uy)), near_pack(wave_max_i32(u4), wave_max_i32(u5)),
+                       near_pack(wave_max_i32(u7), wave_max_i32(u9)), near_pack(wave_min_i32(dx), wave_min_i32(dy)),
+                       near_pack(wave_min_i32(dz), wave_min_i32(d4)), near_pack(wave_min_i32(d5), wave_min_i32(d6)),
+                       near_pack(wave_min_i32(d8), kNearMin)};
     }
     RayEntry* list = lists + ((size_t)b * qblocks + qb) * num_leaves;
-    unsigned long long useful = 0, listed = 0;
-    // record: s0 = (lo0,lo1) (lo3,lo4) (lo6,lo8) (hi0,hi1)   s1 = (hi2,hi3) (hi4,hi5) (hi7,leaf) node
-    // > 0: outside some slab.  x1 .. : the value set against the slab's LOWER bound, x0 .. : against its UPPER bound (a
-    // ray's value twice; the block's largest and smallest)
-    auto outside13 = [&](const uint4& s0, const uint4& s1, float x1, float x0, float y1, float y0, float p1, float p0,
-                         float m1, float m0, float z0, float xz0, float xz1, float yz0, float yz1) {
-        float out = max3(lo_minus(s0.x, x1), minus_lo(x0, s0.w), hi_minus(s0.x, y1));
-        out = max3(out, minus_hi(y0, s0.w), lo_minus(s0.y, p1));
-        out = max3(out, minus_hi(p0, s1.x), hi_minus(s0.y, m1));
-        out = max3(out, minus_lo(m0, s1.y), minus_lo(z0, s1.x));
-        out = max3(out, minus_hi(xz0, s1.y), lo_minus(s0.z, xz1));
-        return max3(out, minus_lo(yz0, s1.z), hi_minus(s0.z, yz1));
-    };
-    auto outside = [&](const uint4& s0, const uint4& s1) {
-        return outside13(s0, s1, rx, rx, ry, ry, r4, r4, r5, r5, rz, r6, r7, r8, r9);
-    };
+    unsigned long long useful = 0, listed = 0;  // (per lane: summed by the atomics at the end)
     int nslots = 0;                             // one wavefront: the list's length in a (scalar) register, no LDS atomic
-    auto emit = [&](const uint4& s1, unsigned long long hit) {
-        if (!hit) return;
-        const int leaf = (int)(s1.z >> 16), nd = (int)s1.w;
-        if (kWaves == 1) ++nslots;
-        if (lane == 0) {
-            const int slot = kWaves == 1 ? nslots - 1 : atomicAdd(&slots, 1);
-            list[slot] = RayEntry{leaf, nd, (uint32_t)hit, (uint32_t)(hit >> 32)};
-            atomicAdd(&leaf_cnt[(size_t)b * num_leaves + leaf], __builtin_popcountll(hit));
-        }
-        if (stats) {
-            const int len = nodes[nd].ex_len;
-            useful += (unsigned long long)__builtin_popcountll(hit) * len;
-            listed += 64ull * len;
-        }
+    // the hit mask of one queue position, handed to the lane that owns the position
+    uint32_t own_lo = 0u, own_hi = 0u;
+    auto hand = [&](unsigned long long hit, int owner) {
+        own_lo = (uint32_t)tuch_writelane((int)(uint32_t)hit, owner, (int)own_lo);
+        own_hi = (uint32_t)tuch_writelane((int)(uint32_t)(hit >> 32), owner, (int)own_hi);
     };
     // (one wavefront: its LDS accesses are served in order, nothing to wait for between the stages)
     auto sync = [&] { if (kWaves > 1) __syncthreads(); else __builtin_amdgcn_wave_barrier(); };
@@ -722,9 +753,10 @@ __global__ __launch_bounds__(64 * kWaves) void ray_near_kernel(
         const int base = (round * kWaves + wave) * 64;
         const Chunk c = nxt;
         if (base + 64 * kWaves < num_leaves) nxt = load_chunk(base + 64 * kWaves);
-        const bool pass = (base + lane < num_leaves) &
-                          !(outside13(c.r0, c.r1, bx1, bx0, by1, by0, b41, b40, b51, b50, bz0, b60, b71, b80, b91) > 0.0f);
-        const unsigned long long mask = __builtin_amdgcn_ballot_w64(pass);
+        // (the two conditions meet as masks: a ballot of their conjunction is rebuilt from a 0 / 1 register)
+        const unsigned long long mask = __builtin_amdgcn_ballot_w64(!near_outside(c.r0, c.r1, blk)) &
+                                        __builtin_amdgcn_ballot_w64(base + lane < num_leaves);
+        const bool pass = (mask >> lane) & 1ull;
         if (mask) {
             int at = 0;
             if (kWaves > 1) {
@@ -735,38 +767,66 @@ __global__ __launch_bounds__(64 * kWaves) void ray_near_kernel(
             if (pass) { queue[at][0] = c.r0; queue[at][1] = c.r1; }
         }
         sync();
-        const int n = kWaves > 1 ? queued[round & 1] : __builtin_popcountll(mask);
+        const int n = kWaves > 1 ? __builtin_amdgcn_readfirstlane(queued[round & 1]) : __builtin_popcountll(mask);
         if (kWaves > 1 && threadIdx.x == 0) queued[(round + 1) & 1] = 0;    // (last read before this round's first barrier)
+        own_lo = 0u; own_hi = 0u;
+        int pos;                                // the queue position this lane owns in this round
         if (kWaves == 1) {
             // one wavefront per block (large batches): FOUR records per trip -- the trip is a dependent chain (LDS read ->
-            // 19 vector instructions -> ballot -> branch) and the blocks through the trunk have ~200 of them
+            // 12 vector instructions -> compare -> two v_writelane) and the blocks through the trunk have ~200 records
+            pos = lane;
             for (int i = 0; i < n; i += 4) {
-                const int k1 = min(i + 1, n - 1), k2 = min(i + 2, n - 1), k3 = min(i + 3, n - 1);
-                const uint4 a0 = queue[i][0], a1 = queue[i][1], c0 = queue[k1][0], c1 = queue[k1][1];
-                const uint4 d0 = queue[k2][0], d1 = queue[k2][1], f0 = queue[k3][0], f1 = queue[k3][1];
-                const float out_a = outside(a0, a1), out_c = outside(c0, c1), out_d = outside(d0, d1), out_f = outside(f0, f1);
-                const unsigned long long hit_a = __builtin_amdgcn_ballot_w64(real && !(out_a > 0.0f));
-                const unsigned long long hit_c = __builtin_amdgcn_ballot_w64(real && !(out_c > 0.0f) && i + 1 < n);
-                const unsigned long long hit_d = __builtin_amdgcn_ballot_w64(real && !(out_d > 0.0f) && i + 2 < n);
-                const unsigned long long hit_f = __builtin_amdgcn_ballot_w64(real && !(out_f > 0.0f) && i + 3 < n);
-                emit(a1, hit_a);
-                emit(c1, hit_c);
-                emit(d1, hit_d);
-                emit(f1, hit_f);
+                // (i + 3 <= 63: n <= 64, i % 4 == 0.  Positions behind the queue's end hold whatever LDS held: their masks go
+                // to owners >= n, which write nothing)
+                const uint4 a0 = queue[i][0], a1 = queue[i][1], c0 = queue[i + 1][0], c1 = queue[i + 1][1];
+                const uint4 d0 = queue[i + 2][0], d1 = queue[i + 2][1], f0 = queue[i + 3][0], f1 = queue[i + 3][1];
+                const bool out_a = near_outside(a0, a1, me), out_c = near_outside(c0, c1, me);
+                const bool out_d = near_outside(d0, d1, me), out_f = near_outside(f0, f1, me);
+                hand(__builtin_amdgcn_ballot_w64(!out_a) & real_mask, i);
+                hand(__builtin_amdgcn_ballot_w64(!out_c) & real_mask, i + 1);
+                hand(__builtin_amdgcn_ballot_w64(!out_d) & real_mask, i + 2);
+                hand(__builtin_amdgcn_ballot_w64(!out_f) & real_mask, i + 3);
             }
-        } else
-        for (int i = wave * 2; i < n; i += kWaves * 2) {
-            const int k = i + 1 < n ? i + 1 : i;
-            const uint4 a0 = queue[i][0], a1 = queue[i][1], c0 = queue[k][0], c1 = queue[k][1];
-            const float out_a = outside(a0, a1), out_c = outside(c0, c1);
-            const unsigned long long hit_a = __builtin_amdgcn_ballot_w64(real && !(out_a > 0.0f));
-            const unsigned long long hit_c = __builtin_amdgcn_ballot_w64(real && !(out_c > 0.0f) && k != i);
-            emit(a1, hit_a);
-            emit(c1, hit_c);
+        } else {
+            // trip t of wavefront w tests the positions w * 2 + t * 8 + {0, 1}; lanes 2 t, 2 t + 1 own them (t < 32: the queue
+            // holds at most 64 kWaves records)
+            pos = wave * 2 + (lane >> 1) * (kWaves * 2) + (lane & 1);
+            int owner = 0;
+            for (int i = wave * 2; i < n; i += kWaves * 2, owner += 2) {
+                const uint4 a0 = queue[i][0], a1 = queue[i][1], c0 = queue[i + 1][0], c1 = queue[i + 1][1];   // (i + 1 <= 255)
+                const bool out_a = near_outside(a0, a1, me), out_c = near_outside(c0, c1, me);
+                hand(__builtin_amdgcn_ballot_w64(!out_a) & real_mask, owner);
+                hand(__builtin_amdgcn_ballot_w64(!out_c) & real_mask, owner + 1);       // (i + 1 == n: its owner writes nothing)
+            }
+        }
+        // the owners of non-empty masks write the entries
+        const bool has = pos < n && (own_lo | own_hi) != 0u;
+        const unsigned long long hm = __builtin_amdgcn_ballot_w64(has);
+        if (hm) {
+            int at = nslots;
+            if (kWaves == 1) {
+                nslots += __builtin_popcountll(hm);
+            } else {
+                if (lane == 0) at = atomicAdd(&slots, __builtin_popcountll(hm));
+                at = __builtin_amdgcn_readfirstlane(at);
+            }
+            if (has) {
+                const uint4 who = queue[pos][1];
+                const int leaf = (int)(who.z >> 16), nd = (int)who.w;
+                const int rays = __builtin_popcount(own_lo) + __builtin_popcount(own_hi);
+                const int slot = at + __builtin_amdgcn_mbcnt_hi((uint32_t)(hm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hm, 0));
+                list[slot] = RayEntry{leaf, nd, own_lo, own_hi};
+                atomicAdd(&leaf_cnt[(size_t)b * num_leaves + leaf], rays);
+                if (stats) {
+                    const int len = nodes[nd].ex_len;
+                    useful += (unsigned long long)rays * len;
+                    listed += 64ull * len;
+                }
+            }
         }
         sync();
     }
-    if (stats && lane == 0) { atomicAdd(stats + 1, useful); atomicAdd(stats + 2, listed); }
+    if (stats && listed) { atomicAdd(stats + 1, useful); atomicAdd(stats + 2, listed); }
     if (threadIdx.x == 0) list_len[(size_t)b * qblocks + qb] = kWaves == 1 ? nslots : slots;
 }
 
@@ -1901,7 +1961,7 @@ size_t tuch_ray_workspace_bytes(const tuch_contact_model* m, int B, int Q)
 
 // sheared leaf strips and the slabs of every LEAF (inner nodes are not used by the flat near test)
 static void launch_ray_boxes(const tuch_contact_model* m, const RayLayout& l, const float* verts, int B, char* ws, hipStream_t s,
-                             bool one_launch)
+                             bool one_launch, int keep_bounds = 0)
 {
     RayElem* st = (RayElem*)(ws + l.stream);
     float* bounds = (float*)(ws + l.bounds);
@@ -1912,7 +1972,7 @@ static void launch_ray_boxes(const tuch_contact_model* m, const RayLayout& l, co
                            s, (const RayElem*)st, l.T, (const TreeNode*)m->tree_node, m->tree_nodes,
                            (const int32_t*)m->tree_height_off, (const int32_t*)m->tree_height_nodes, bounds, verts,
                            (const int32_t*)m->tree_vidx, (const float*)m->tree_sign_word, m->V, m->tree_exact_len, st,
-                           (uint4*)(ws + l.zeroed), l.zeroed_bytes / sizeof(uint4), (float4*)(ws + l.boxes));
+                           (uint4*)(ws + l.zeroed), l.zeroed_bytes / sizeof(uint4), (float4*)(ws + l.boxes), keep_bounds);
         return;
     }
     hipLaunchKernelGGL(ray_stream_kernel, dim3(ceil_div(l.T, kBlock), B), dim3(kBlock), 0, s, verts,
@@ -1922,7 +1982,29 @@ static void launch_ray_boxes(const tuch_contact_model* m, const RayLayout& l, co
                        (const RayElem*)st, l.T, (const TreeNode*)m->tree_node, m->tree_nodes,
                        (const int32_t*)m->tree_height_off, (const int32_t*)m->tree_height_nodes, bounds,
                        (const float*)nullptr, (const int32_t*)nullptr, (const float*)nullptr, 0, m->tree_exact_len, (RayElem*)nullptr,
-                       (uint4*)nullptr, (size_t)0, (float4*)(ws + l.boxes));
+                       (uint4*)nullptr, (size_t)0, (float4*)(ws + l.boxes), keep_bounds);
+}
+
+// the near test.  waves = 0: four wavefronts per query block while the blocks alone do not fill the chip (see the kernel),
+// one otherwise; 1 / 4: that form (tuch_ray_near_debug)
+template <bool kVerts>
+static void launch_ray_near(const tuch_contact_model* m, const RayLayout& l, const float* queries, const int32_t* counts, int B,
+                            int Q, char* ws, hipStream_t s, unsigned long long* stats, float* rays_out, int waves)
+{
+    const int L = m->tree_leaves;
+    const TreeNode* nodes = (const TreeNode*)m->tree_node;
+    const int32_t* qperm = kVerts ? (const int32_t*)m->tree_qperm : nullptr;
+    RayEntry* lists = (RayEntry*)(ws + l.lists);
+    int32_t* list_len = (int32_t*)(ws + l.list_len);
+    int32_t* leaf_cnt = (int32_t*)(ws + l.leaf_cnt);
+    if (waves == 4 || (waves == 0 && (long)l.qblocks * B <= 2048))
+        hipLaunchKernelGGL((ray_near_kernel<kVerts, 4>), dim3(l.qblocks, B), dim3(256), 0, s, queries, nodes,
+                           (const float*)(ws + l.bounds), m->tree_nodes, L, qperm, counts, Q, l.qblocks, lists, list_len,
+                           leaf_cnt, stats, rays_out);
+    else
+        hipLaunchKernelGGL((ray_near_kernel<kVerts, 1>), dim3(l.qblocks, B), dim3(64), 0, s, queries, nodes,
+                           (const float*)(ws + l.bounds), m->tree_nodes, L, qperm, counts, Q, l.qblocks, lists, list_len,
+                           leaf_cnt, stats, rays_out);
 }
 
 // near leaves -> rays per leaf -> tiles -> crossing counts (count[b][slot])
@@ -1943,15 +2025,7 @@ static int launch_ray_counts(const tuch_contact_model* m, const RayLayout& l, co
     RayTile* tiles = (RayTile*)(ws + l.tiles);
     RayBody* body = (RayBody*)(ws + l.body);
     int32_t* pairs = (int32_t*)(ws + l.pairs);
-    // four wavefronts per query block while the blocks alone do not fill the chip (see the kernel)
-    if ((long)l.qblocks * B <= 2048)
-        hipLaunchKernelGGL((ray_near_kernel<kVerts, 4>), dim3(l.qblocks, B), dim3(256), 0, s, queries, nodes,
-                           (const float*)(ws + l.bounds), m->tree_nodes, L, qperm, counts, Q, l.qblocks, lists, list_len,
-                           leaf_cnt, stats);
-    else
-        hipLaunchKernelGGL((ray_near_kernel<kVerts, 1>), dim3(l.qblocks, B), dim3(64), 0, s, queries, nodes,
-                           (const float*)(ws + l.bounds), m->tree_nodes, L, qperm, counts, Q, l.qblocks, lists, list_len,
-                           leaf_cnt, stats);
+    launch_ray_near<kVerts>(m, l, queries, counts, B, Q, ws, s, stats, nullptr, 0);
     const size_t tf_lds = (2 * (size_t)L + l.qblocks + 1) * sizeof(int32_t);
     if (l.qblocks <= kFillMaxBlocks && tf_lds <= 48u * 1024)
         // (one-wave workgroups per body: 64, more for small batches -- the kernel is a chain of dependent steps per workgroup, and a
@@ -2027,6 +2101,75 @@ int tuch_ray_exterior_points(const tuch_contact_model* m, const float* verts, co
     hipLaunchKernelGGL(ray_finalize_points_kernel, dim3(ceil_div(Q, kBlock), B), dim3(kBlock), 0, s,
                        (const int32_t*)(ws + l.count), counts, Q, l.qblocks * kRayQueries, thresh, w, exterior);
     return tuch_check_launch("tuch_ray_exterior_points");
+}
+
+// ---- tuch_ray_near_debug / tuch_near_encode_host: what the near lists hold, for the tests -------------------------------------
+// bitmap [B][L][qblocks * 8]: bit (slot & 7) of byte (slot >> 3) is set where (leaf, slot) is listed (zeroed by the caller);
+// leaves [B][qblocks][L]: the leaf of every entry of a block's list in list order, -1 behind its end
+__global__ __launch_bounds__(64) void ray_near_bitmap_kernel(
+    const RayEntry* __restrict__ lists, const int32_t* __restrict__ list_len, int L, int qblocks, uint8_t* __restrict__ bitmap,
+    int32_t* __restrict__ leaves)
+{
+    const int qb = blockIdx.x, b = blockIdx.y;
+    const size_t at = ((size_t)b * qblocks + qb) * L;
+    const int n = min(list_len[(size_t)b * qblocks + qb], L);
+    for (int j = threadIdx.x; j < L; j += 64) {
+        const RayEntry e = j < n ? lists[at + j] : RayEntry{-1, 0, 0u, 0u};
+        if (leaves) leaves[at + j] = e.leaf;
+        if (bitmap && e.leaf >= 0 && e.leaf < L)
+            *reinterpret_cast<uint2*>(bitmap + ((size_t)b * L + e.leaf) * ((size_t)qblocks * 8) + (size_t)qb * 8) = make_uint2(e.mask_lo, e.mask_hi);
+    }
+}
+
+static int tuch_ray_near_debug_run(const tuch_contact_model* m, const float* verts, const float* points, const int32_t* counts,
+                            int B, int Q, int waves, void* workspace, float* out_bounds, uint32_t* out_records,
+                            float* out_rays, uint8_t* out_bitmap, int32_t* out_leaves, int32_t* out_len, hipStream_t s)
+{
+    const bool by_verts = points == nullptr;
+    const RayLayout l = full_layout(m, B, by_verts ? m->V : Q, by_verts);
+    char* ws = (char*)workspace;
+    const int L = m->tree_leaves;
+    launch_ray_boxes(m, l, verts, B, ws, s, by_verts, 1);
+    if (by_verts) launch_ray_near<true>(m, l, verts, nullptr, B, m->V, ws, s, nullptr, out_rays, waves);
+    else launch_ray_near<false>(m, l, points, counts, B, Q, ws, s, nullptr, out_rays, waves);
+    const float* bounds = (const float*)(ws + l.bounds);
+    if (out_bitmap && hipMemsetAsync(out_bitmap, 0, (size_t)B * L * l.qblocks * 8, s) != hipSuccess) return TUCH_ERR_HIP;
+    hipLaunchKernelGGL(ray_near_bitmap_kernel, dim3(l.qblocks, B), dim3(64), 0, s, (const RayEntry*)(ws + l.lists),
+                       (const int32_t*)(ws + l.list_len), L, l.qblocks, out_bitmap, out_leaves);
+    if ((out_bounds && hipMemcpyAsync(out_bounds, bounds, (size_t)B * kNearSlabs * L * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) ||
+        (out_records && hipMemcpyAsync(out_records, bounds + near_records_at(B, L), (size_t)B * L * 8 * sizeof(uint32_t), hipMemcpyDeviceToDevice, s) != hipSuccess) ||
+        (out_len && hipMemcpyAsync(out_len, ws + l.list_len, (size_t)B * l.qblocks * sizeof(int32_t), hipMemcpyDeviceToDevice, s) != hipSuccess))
+        return TUCH_ERR_HIP;
+    return tuch_check_launch("tuch_ray_near_debug");
+}
+
+extern "C" int tuch_ray_near_debug(const tuch_contact_model* m, const float* verts, const float* points, const int32_t* counts,
+                                   int B, int Q, int waves, void* workspace, size_t workspace_bytes, long long* dims_host,
+                                   float* out_bounds, uint32_t* out_records, float* out_rays, uint8_t* out_bitmap,
+                                   int32_t* out_leaves, int32_t* out_len, void* stream)
+{
+    TUCH_REQUIRE(m && dims_host, "tuch_ray_near_debug: null pointer");
+    TUCH_REQUIRE(tuch_ray_available(m), "tuch_ray_near_debug: the model has no cluster tree / vertex rings");
+    TUCH_REQUIRE(B > 0 && B <= 65535 && (!points || Q > 0), "tuch_ray_near_debug: bad sizes B=%d Q=%d", B, Q);
+    TUCH_REQUIRE(waves == 0 || waves == 1 || waves == 4, "tuch_ray_near_debug: waves %d is not 0, 1 or 4", waves);
+    dims_host[0] = m->tree_leaves;
+    dims_host[1] = points ? ceil_div(Q, kRayQueries) : 2 * m->tree_qblocks;
+    const size_t need = tuch_ray_workspace_bytes(m, B, points ? Q : 0);
+    dims_host[2] = (long long)need;
+    if (!verts) return TUCH_OK;                     // the sizes only
+    if (!workspace || workspace_bytes < need) {
+        tuch_set_error("tuch_ray_near_debug: workspace %zu < %zu bytes", workspace_bytes, need);
+        return TUCH_ERR_WORKSPACE;
+    }
+    return tuch_ray_near_debug_run(m, verts, points, counts, B, Q, waves, workspace, out_bounds, out_records, out_rays,
+                                   out_bitmap, out_leaves, out_len, (hipStream_t)stream);
+}
+
+extern "C" int tuch_near_encode_host(float value, int round_up, int* out)
+{
+    if (!out) return TUCH_ERR_ARG;
+    *out = near_encode(value, round_up != 0);
+    return TUCH_OK;
 }
 
 // The segment filter (winding.hip: caps, compacted interior vertices per (body, segment) in seg_count / seg_list) by

@@ -1040,6 +1040,14 @@ def segment_faces(body_faces: np.ndarray, vidx: np.ndarray, bands: Sequence[np.n
     return np.concatenate([body_faces[inside]] + fans, 0) if fans else body_faces[inside]
 
 
+def near_encode_host(value: float, round_up: bool) -> int:
+    """The near test's 16-bit fixed-point level of a single-precision value, by the kernels' own conversion run on the
+    host (tests only; tuch_near_encode_host in include/tuch_amd.h)."""
+    out = ctypes.c_int(0)
+    _C.check(_C.lib().tuch_near_encode_host(ctypes.c_float(value), int(bool(round_up)), ctypes.byref(out)))
+    return out.value
+
+
 def cluster_tree(faces, num_verts: int, leaf_faces: int = 64) -> dict:
     """The face-cluster tree used by the hierarchical winding numbers (host only; see include/tuch_amd.h,
     tuch_cluster_tree_build).  Returns numpy arrays: nodes [N,8], vidx, sign, qperm, frontier_off,
@@ -1268,6 +1276,39 @@ class ContactModel:
         _C.check(L.tuch_ray_work(self._handle, _C.ptr(verts), b, _C.ptr(ws), nbytes, out, _C.stream()))
         return dict(elements=int(out[0]), wavefronts=int(out[3]), queries_per_step=64,
                     lanes_inside_leaf_slabs=int(out[1]) / max(int(out[2]), 1))
+
+    def ray_near_debug(self, verts: torch.Tensor, points: Optional[torch.Tensor] = None,
+                       counts: Optional[torch.Tensor] = None, waves: int = 0) -> dict:
+        """What the near stage of the ray-crossing inside test holds for these vertices (or points): the leaves' padded
+        bounds, their 16-bit records, the rays' values and the listed (leaf, slot) pairs (tests only; see
+        tuch_ray_near_debug in include/tuch_amd.h).  waves: 0 as the step would, 1 / 4 wavefronts per query block."""
+        verts = _f32(verts)
+        b, dev = verts.shape[0], verts.device
+        L = _C.lib()
+        q = 0
+        if points is not None:
+            points = _f32(points)
+            q = points.shape[1]
+            if counts is not None:
+                counts = counts.to(device=dev, dtype=torch.int32).contiguous()
+        dims = (ctypes.c_longlong * 3)()
+        null = ctypes.c_void_p(0)
+        _C.check(L.tuch_ray_near_debug(self._handle, null, _C.ptr(points) if points is not None else null, null, b, q, waves,
+                                       null, 0, dims, null, null, null, null, null, null, _C.stream()))
+        leaves, blocks, nbytes = int(dims[0]), int(dims[1]), int(dims[2])
+        ws = _workspace(nbytes, dev)
+        out = dict(bounds=torch.zeros(b, 13, leaves, dtype=torch.float32, device=dev),
+                   records=torch.zeros(b, leaves, 8, dtype=torch.int32, device=dev),
+                   rays=torch.full((b, blocks * 64, 9), float('nan'), dtype=torch.float32, device=dev),
+                   bitmap=torch.zeros(b, leaves, blocks * 8, dtype=torch.uint8, device=dev),
+                   leaves=torch.full((b, blocks, leaves), -1, dtype=torch.int32, device=dev),
+                   lengths=torch.zeros(b, blocks, dtype=torch.int32, device=dev))
+        _C.check(L.tuch_ray_near_debug(self._handle, _C.ptr(verts), _C.ptr(points) if points is not None else null,
+                                       _C.ptr(counts) if counts is not None else null, b, q, waves, _C.ptr(ws), nbytes, dims,
+                                       *[_C.ptr(out[k]) for k in ('bounds', 'records', 'rays', 'bitmap', 'leaves', 'lengths')],
+                                       _C.stream()))
+        torch.cuda.synchronize(dev)
+        return {k: v.cpu().numpy() for k, v in out.items()}
 
     # K2 + K3
     def exterior_flags(self, verts: torch.Tensor, apply_segments: bool = True, thresh: float = 0.99,
