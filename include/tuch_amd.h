@@ -422,6 +422,35 @@ int tuch_closest_point_hinted(const tuch_contact_model* model, const float* vert
                               const int32_t* hint /* [B,Q] or NULL */, int B, int Q, float* d2 /* [B,Q] */,
                               int32_t* face /* [B,Q] */, float* bary /* [B,Q,3] */, void* workspace,
                               size_t workspace_bytes, void* stream);
+/* The normal-compatible search: tuch_closest_point_hinted's arguments plus normals [B,Q,3] (float32, any length, in
+ * the frame of verts) and max_angle_cos = c, the float32 cosine of an angle in (0, 90] degrees (the caller computes the
+ * cosine in double and rounds it once).  A query is (p, n); a face is a candidate only if it is ADMISSIBLE for n.
+ *   The admissibility rule, one fixed float32 sequence, every product, sum and difference rounded on its own (nothing
+ * fused), for a face with posed corners a, b, c (the bits of verts) and c2 = c * c formed once in float32:
+ *     e1 = b - a, e2 = c - a                       (one subtraction per component)
+ *     m = e1 x e2                                  (each component as (x * y) - (z * w))
+ *     mm = (mx*mx + my*my) + mz*mz,  nn = (nx*nx + ny*ny) + nz*nz,  s = (mx*nx + my*ny) + mz*nz
+ *     admissible  <=>  s > 0  and  s * s >= c2 * (mm * nn).
+ * A face without area (mm = 0, s = 0) is never admissible for a constrained query; neither is one with NaN corners
+ * (every comparison is false).  A query whose nn is 0 or not finite (a missing normal: a zero row, NaN, Inf, overflow)
+ * is UNCONSTRAINED: every face is admissible and its three outputs have tuch_closest_point's bits.
+ *   The winner is the smallest packed key d2 bits << 32 | face over the admissible faces, d2 from the unchanged
+ * distance sequence; a query without an admissible face gets d2 = +inf, face = -1, bary = 0.  A query gives the same
+ * bits alone or in any batch, for any order of the queries, eager or replayed, for any grouping of the faces and for
+ * every content of hint: the outputs equal an unpruned sweep over all faces under this rule, bit for bit (groups are
+ * skipped by their boxes as before, and by per-group normal cones whose margins are conservative: derivation in the
+ * source file).  A hinted query starts from its hint only if the face is in [0, F), admissible for it and at a finite
+ * d2; any other hint takes the unhinted path.  hint may alias face.  counts, NaN bodies, B = 0 or Q = 0 as for
+ * tuch_closest_point.  max_angle_cos outside [0, 1) or not finite is an argument error.  The workspace is
+ * tuch_closest_point's plus the cones [B,G,8], guarded under option canary.  tuch_closest_point_bwd applies to the
+ * outputs unchanged (face = -1 contributes nothing); normals are constants and get no gradient. */
+size_t tuch_closest_point_oriented_workspace_bytes(const tuch_contact_model* model, int B, int Q);
+int tuch_closest_point_oriented(const tuch_contact_model* model, const float* verts /* [B,V,3] */,
+                                const float* points /* [B,Q,3] */, const float* normals /* [B,Q,3] */,
+                                float max_angle_cos, const int32_t* counts /* [B] or NULL */,
+                                const int32_t* hint /* [B,Q] or NULL */, int B, int Q, float* d2 /* [B,Q] */,
+                                int32_t* face /* [B,Q] */, float* bary /* [B,Q,3] */, void* workspace,
+                                size_t workspace_bytes, void* stream);
 /* The face groups the search walks, as host copies (any may be NULL): *num_groups = G, group_off_host [G+1],
  * face_list_host [F] (the faces of group g are face_list[group_off[g] .. group_off[g+1])), face_group_host [F] (the
  * group of every face: the inverse of face_list, where a hinted query starts). */
@@ -462,6 +491,23 @@ int tuch_scan_fit_terms(const tuch_contact_model* model, const float* verts /* [
                         float* per_body /* [B] */, float* total /* [1] */, float* grad_verts /* [B,V,3] */,
                         float* grad_transl /* [B,3] */, float* grad_points /* [B,Q,3] or NULL */, void* workspace,
                         size_t workspace_bytes, void* stream);
+/* The same term over the normal-compatible search: tuch_scan_fit_terms plus normals [B,Q,3] and max_angle_cos as in
+ * tuch_closest_point_oriented.  The queries are points - transl as above; normals are not translated and get no
+ * gradient.  d2, face, bary are tuch_closest_point_oriented's on these queries, bit for bit.  A real point without an
+ * admissible face (face = -1) contributes 0 to the loss and to every gradient and KEEPS its weight in the normaliser:
+ * an unmatched point adds nothing and the denominator does not move.  Workspace:
+ * tuch_scan_fit_oriented_workspace_bytes. */
+size_t tuch_scan_fit_oriented_workspace_bytes(const tuch_contact_model* model, int B, int Q);
+int tuch_scan_fit_terms_oriented(const tuch_contact_model* model, const float* verts /* [B,V,3] */,
+                                 const float* transl /* [B,3] */, const float* points /* [B,Q,3] */,
+                                 const float* normals /* [B,Q,3] */, float max_angle_cos,
+                                 const int32_t* counts /* [B] or NULL */, const float* weights /* [B,Q] or NULL */,
+                                 const int32_t* hint /* [B,Q] or NULL */, int B, int Q, int rho, float sigma,
+                                 float* d2 /* [B,Q] */, int32_t* face /* [B,Q] */, float* bary /* [B,Q,3] */,
+                                 int* ticket, float* per_body /* [B] */, float* total /* [1] */,
+                                 float* grad_verts /* [B,V,3] */, float* grad_transl /* [B,3] */,
+                                 float* grad_points /* [B,Q,3] or NULL */, void* workspace, size_t workspace_bytes,
+                                 void* stream);
 
 /* Nearest point of a static point cloud; the model -> scan term of a two-sided fit (csrc/point_cloud.hip).  No model
  * is involved: a cloud has no mesh.

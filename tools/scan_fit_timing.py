@@ -6,6 +6,7 @@ closest-point search (csrc/closest_point.hip: tuch_closest_point_hinted), DESIGN
     python tools/scan_fit_timing.py --only search   # the search alone
     python tools/scan_fit_timing.py --only fit      # warm-up + ONE call of --iters replayed iterations: for a
                                                     # rocprofv3 --kernel-trace --stats run of its own (launches per iteration)
+    python tools/scan_fit_timing.py --normals 60    # + the normal-compatible search and fit at that angle (degrees)
 
 Batch 64 on the synthetic full body (V = 6890, F = 13776).  The scan of a body is the surface of that body at a random
 pose + a translation: its vertices in vertex order (Q = 6890) and three points per face in face order (Q = 41 328).
@@ -19,6 +20,12 @@ pose + a translation: its vertices in vertex order (Q = 6890) and three points p
 * the loop: device events around whole calls of --iters iterations, `ScanFitter` on a kept session (replays) with and
   without the hint, and the baseline -- what the package lets a user write without this module: SMPL(...) +
   closest_point + torch ops for rho + torch.optim.Adam(capturable=True), eager on the device.
+* --normals ANGLE: the scan carries the true body's normals (area-weighted vertex normals for the vertex scan, the face's
+  normal for the face samples, computed with torch).  On the same two states the oriented search
+  (tuch_closest_point_oriented) against the unoriented one, unhinted and hinted, the versions alternating; the share of
+  matched points, the share of answers the filter changed, the group visits of both searches (the oriented ones: the box
+  test under the lane's final d2 -- +inf for an unmatched lane -- and the group's normal cone, restated here, not proving
+  the group inadmissible); `ScanFitter` per iteration with and without normals.
 """
 import argparse
 import json
@@ -31,8 +38,9 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from closest_point_timing import group_visits, spread, timed      # noqa: E402
+from closest_point_timing import MARGIN, group_visits, spread, timed      # noqa: E402
 from synthetic import make_body, random_poses      # noqa: E402
+from tuch_amd import _C, ops                       # noqa: E402
 from tuch_amd.fit import ScanFitter                # noqa: E402
 from tuch_amd.models.smpl import SMPL              # noqa: E402
 from tuch_amd.ops import ContactModel              # noqa: E402
@@ -54,6 +62,70 @@ def graph_of(fn):
     graph.replay()
     torch.cuda.synchronize()
     return graph, kept
+
+
+def scan_normals(model, true):
+    """(vertex normals [B,V,3]: the area-weighted sum of the faces around every vertex, normalised; three copies of every
+    face's unit normal [B,3F,3]) of the true bodies."""
+    faces = model.faces_i32.long()
+    tri = true[:, faces]
+    m = torch.cross(tri[:, :, 1] - tri[:, :, 0], tri[:, :, 2] - tri[:, :, 0], dim=-1)           # twice the area, along the normal
+    vn = torch.zeros_like(true)
+    for k in range(3):
+        vn.index_add_(1, faces[:, k], m)
+    unit = lambda x: x / x.norm(dim=-1, keepdim=True).clamp_min(1e-30)
+    return unit(vn).contiguous(), unit(m)[:, :, None].expand(-1, -1, 3, -1).reshape(true.shape[0], -1, 3).contiguous()
+
+
+CONE_MARGIN = 256.0 * 2.0 ** -24    # kCpConeMargin of csrc/closest_point.hip
+
+
+def oriented_group_visits(model, verts, points, normals, d2, cosine):
+    """group_visits for the oriented search: a group counts for a lane when its box is within the lane's final d2 AND its
+    normal cone (the kernel's, restated) does not prove every face of it inadmissible for the lane's normal."""
+    import numpy as np
+    leaf = np.zeros(model.num_faces, np.int32)
+    _C.check(_C.lib().tuch_contact_model_tree_order(model._handle, None, leaf.ctypes.data_as(_C.c_void_p)))
+    dev = verts.device
+    leaf_t = torch.as_tensor(leaf, device=dev).long()
+    groups = int(leaf.max()) + 1
+    size = torch.bincount(leaf_t, minlength=groups).float()
+    faces = model.faces_i32.long()
+    visits, tests = [], []
+    dot = lambda a, b: (a * b).sum(-1)
+    for b in range(0, verts.shape[0], 4):
+        tri = verts[b:b + 4][:, faces]                                                          # [b,F,3,3]
+        nb = tri.shape[0]
+        m = torch.cross(tri[:, :, 1] - tri[:, :, 0], tri[:, :, 2] - tri[:, :, 0], dim=-1)
+        u = m / m.norm(dim=-1, keepdim=True).clamp_min(1e-30)
+        axis = torch.zeros(nb, groups, 3, device=dev).index_add_(1, leaf_t, u)
+        axis = axis / axis.norm(dim=-1, keepdim=True).clamp_min(1e-30)
+        cos_f = dot(axis[:, leaf_t], u)                                                         # [b,F]
+        cb = torch.full((nb, groups), 2.0, device=dev).scatter_reduce(1, leaf_t[None].expand(nb, -1), cos_f, 'amin')
+        sb = torch.sqrt((1.0 - cb * cb).clamp_min(0.0))
+        idx = leaf_t[None, :, None].expand(nb, -1, 3)
+        lo = torch.full((nb, groups, 3), float('inf'), device=dev)
+        hi = -lo
+        for k in range(3):
+            lo = lo.scatter_reduce(1, idx, tri[:, :, k], 'amin')
+            hi = hi.scatter_reduce(1, idx, tri[:, :, k], 'amax')
+        p = points[b:b + 4][:, :, None]
+        near = torch.maximum(torch.maximum(lo[:, None] - p, p - hi[:, None]), torch.zeros((), device=dev))
+        far = torch.maximum(p - lo[:, None], hi[:, None] - p)
+        admit = dot(near, near) - MARGIN * dot(far, far) <= d2[b:b + 4][:, :, None]              # [b,Q,G]
+        n = normals[b:b + 4]
+        n = n / n.norm(dim=-1, keepdim=True).clamp_min(1e-30)
+        ca = torch.einsum('bqc,bgc->bqg', n, axis)
+        sa = torch.sqrt((1.0 - ca * ca).clamp_min(0.0))
+        out = (ca < cb[:, None] - CONE_MARGIN) & (ca * cb[:, None] + sa * sb[:, None] <= cosine - CONE_MARGIN)
+        admit = admit & ~out
+        pad = (-admit.shape[1]) % 64
+        if pad:
+            admit = torch.cat([admit, torch.zeros(nb, pad, groups, dtype=torch.bool, device=dev)], 1)
+        wave = admit.view(nb, -1, 64, groups).any(2)
+        visits.append(wave.sum(2).float().flatten())
+        tests.append((wave.float() * size).sum(2).flatten())
+    return torch.cat(visits), torch.cat(tests), groups
 
 
 def baseline_loop(smpl, model, points, global_orient, iters):
@@ -84,6 +156,8 @@ def main():
     ap.add_argument('--calls', type=int, default=10, help='search calls per timed block')
     ap.add_argument('--at', type=int, default=10, help='the search is timed on the fit\'s states before updates AT and AT + 1')
     ap.add_argument('--only', choices=('fit', 'search'), default=None)
+    ap.add_argument('--normals', type=float, default=None, metavar='ANGLE',
+                    help='also the normal-compatible search and fit, at this max angle in degrees')
     a = ap.parse_args()
     dev = torch.device('cuda:0')
     body = make_body(with_geodesics=False)
@@ -99,7 +173,9 @@ def main():
         w = torch.rand(len(faces), 3, 3, device=dev, generator=gen)
         w = w / w.sum(2, keepdim=True)
         hd = (w[None, :, :, :, None] * true[:, faces][:, :, None]).sum(3).reshape(BATCH, -1, 3).contiguous()
+        vertex_normals, face_normals = scan_normals(model, true) if a.normals is not None else (None, None)
     scans = {'Q=6890 vertex order': true.contiguous(), 'Q=41328 face order': hd}
+    normals_of = {'Q=6890 vertex order': vertex_normals, 'Q=41328 face order': face_normals}
     if a.only != 'fit':
         for name, points in scans.items():
             probe = ScanFitter(smpl, model, num_iters=a.at + 2, fit_global_orient=False, use_graph=False, record_history=True)
@@ -113,6 +189,14 @@ def main():
                 graphs['hinted'] = graph_of(lambda: model.closest_point(verts[1], queries[1], hint=earlier.face))
                 for x, y in zip(graphs['unhinted'][1], graphs['hinted'][1]):
                     assert torch.equal(x, y)
+                if a.normals is not None:
+                    nrm = normals_of[name]
+                    oriented = lambda v, q, **kw: model.closest_point(v, q, normals=nrm, max_angle=a.normals, **kw)
+                    earlier_oriented = oriented(verts[0], queries[0])
+                    graphs['oriented unhinted'] = graph_of(lambda: oriented(verts[1], queries[1]))
+                    graphs['oriented hinted'] = graph_of(lambda: oriented(verts[1], queries[1], hint=earlier_oriented.face))
+                    for x, y in zip(graphs['oriented unhinted'][1], graphs['oriented hinted'][1]):
+                        assert torch.equal(x, y)
             t = {k: [] for k in graphs}
             for _ in range(a.repeats):
                 for k, (graph, _) in graphs.items():
@@ -135,6 +219,17 @@ def main():
                 line.update(hinted_start_mean_at_most=round(float(hv.mean()), 2),
                             hinted_start_tests_mean_at_most=round(float(ht.mean()), 1))
                 print(json.dumps(line), flush=True)
+                if a.normals is not None:
+                    found = graphs['oriented unhinted'][1]
+                    cosine = ops._max_angle_cos(nrm, a.normals, queries[1], 'scan_fit_timing')
+                    ov, ot, _ = oriented_group_visits(model, verts[1], queries[1], nrm, found.d2, cosine)
+                    print(json.dumps({'what': 'oriented search at %g degrees, %s' % (a.normals, name),
+                                      'matched': round(float((found.face >= 0).float().mean()), 5),
+                                      'answers_the_filter_changed': round(float((found.face != answer.face).float().mean()), 5),
+                                      'hints_not_the_answer': round(float((earlier_oriented.face != found.face).float().mean()), 4),
+                                      'group_visits_mean': round(float(ov.mean()), 2), 'tests_mean': round(float(ot.mean()), 1),
+                                      'unoriented_group_visits_mean': round(float(visits.mean()), 2),
+                                      'unoriented_tests_mean': round(float(tests.mean()), 1)}), flush=True)
         if a.only == 'search':
             return
     points = scans['Q=6890 vertex order']
@@ -148,22 +243,37 @@ def main():
         return
     plain = ScanFitter(smpl, model, num_iters=a.iters, fit_global_orient=False, use_hint=False)
     plain(points, go)
+    if a.normals is not None:
+        with_normals = ScanFitter(smpl, model, num_iters=a.iters, fit_global_orient=False, use_hint=True,
+                                  max_normal_angle=a.normals)
+        fit_normals = with_normals(points, go, normals=vertex_normals)
     base_iters = max(a.iters // 5, 10)
     baseline_loop(smpl, model, points, go, 5)
     torch.cuda.synchronize()
     t = {'hint': [], 'plain': [], 'baseline': []}
+    if a.normals is not None:
+        t['normals'] = []
     for _ in range(a.repeats):
         t['hint'].append(timed(lambda: fitter(points, go)) / a.iters)
+        if a.normals is not None:
+            t['normals'].append(timed(lambda: with_normals(points, go, normals=vertex_normals)) / a.iters)
         t['plain'].append(timed(lambda: plain(points, go)) / a.iters)
         t['baseline'].append(timed(lambda: baseline_loop(smpl, model, points, go, base_iters)) / base_iters)
     for name, what in (('hint', 'ScanFitter(use_hint=True), kept session (replays)'),
+                       ('normals', 'ScanFitter(use_hint=True, max_normal_angle=%s) with normals, kept session (replays)' % a.normals),
                        ('plain', 'ScanFitter(use_hint=False), kept session (replays)'),
                        ('baseline', 'SMPL + closest_point + torch ops + torch.optim.Adam(capturable), eager')):
+        if name not in t:
+            continue
         print(json.dumps(dict({'what': what, 'batch': BATCH, 'Q': 6890, 'iters': a.iters if name != 'baseline' else base_iters,
                                'repeats': a.repeats}, **spread(t[name]))), flush=True)
     start = ScanFitter(smpl, model, num_iters=0, fit_global_orient=False)(points, go)
     print(json.dumps({'what': 'final / initial loss after %d iterations (largest body)' % a.iters,
                       'value': float((fit.loss / start.loss).max())}), flush=True)
+    if a.normals is not None:
+        print(json.dumps({'what': 'with normals: final / initial loss after %d iterations (largest body)' % a.iters,
+                          'value': float((fit_normals.loss / start.loss).max()),
+                          'matched_at_the_end': round(float((fit_normals.face >= 0).float().mean()), 5)}), flush=True)
 
 
 if __name__ == '__main__':

@@ -120,9 +120,15 @@ _SIGNATURES = {
     'tuch_closest_point_bwd': (c_int, [c_void_p] * 6 + [c_int, c_int] + [c_void_p] * 4),
     'tuch_closest_point_hinted': (c_int, [c_void_p] * 5 + [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                           c_void_p]),
+    'tuch_closest_point_oriented_workspace_bytes': (c_size_t, [c_void_p, c_int, c_int]),
+    'tuch_closest_point_oriented': (c_int, [c_void_p] * 4 + [c_float, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                            c_void_p, c_void_p, c_size_t, c_void_p]),
     'tuch_contact_model_face_groups': (c_int, [c_void_p, POINTER(c_int), c_void_p, c_void_p, c_void_p]),
     'tuch_scan_fit_workspace_bytes': (c_size_t, [c_void_p, c_int, c_int]),
     'tuch_scan_fit_terms': (c_int, [c_void_p] * 7 + [c_int, c_int, c_int, c_float] + [c_void_p] * 10 + [c_size_t, c_void_p]),
+    'tuch_scan_fit_oriented_workspace_bytes': (c_size_t, [c_void_p, c_int, c_int]),
+    'tuch_scan_fit_terms_oriented': (c_int, [c_void_p] * 5 + [c_float] + [c_void_p] * 3 + [c_int, c_int, c_int, c_float]
+                                     + [c_void_p] * 10 + [c_size_t, c_void_p]),
     'tuch_point_cloud_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
     'tuch_point_cloud_build': (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_void_p, c_size_t, c_void_p]),
     'tuch_point_cloud_nearest': (c_int, [c_void_p, c_size_t] + [c_void_p] * 7 + [c_float, c_int, c_int, c_int] + [c_void_p] * 3),

@@ -40,6 +40,61 @@
 // compare false with everything and admit nothing), takes the unhinted path.  So the outputs equal the unhinted
 // call's bit for bit for every content of hint.  hint may alias the face output: a lane reads only its own entry, and
 // before it writes its face (a wholly padded block writes without reading).
+//
+// The oriented search (tuch_closest_point_oriented; cp_search_kernel<*, true>, cp_group_bounds_kernel<true>).  A query
+// is (p, n).  cp_admissible below is THE admissibility of a (normal, triangle) pair, stated in include/tuch_amd.h: with
+// m = (b - a) x (c - a), mm = |m|^2, nn = |n|^2, s = m . n, every operation rounded to float32 on its own,
+//     admissible  <=>  s > 0  and  s s >= c2 (mm nn),      c2 = c c,  c = (float)cos(max_angle).
+// It is a function of the pair's bits and c only, so the admissible set of a query never depends on group, lane, batch
+// or order, and the winner -- the smallest key over that set, cp_eval untouched -- is the unpruned sweep's whatever is
+// pruned conservatively.  A lane whose nn is 0 or not finite is unconstrained: cp_admissible is not asked, and all
+// that follows treats every group as wholly admissible for it, which is the unoriented search.
+//   The upper bound.  "min_g far(g) (1 + 64 u)" bounds the answer only if group g holds a face the lane may take.  A
+// constrained lane therefore starts its bound from (a) the exact d2 of its hint, if that face is admissible for it,
+// or (b) far(g) (1 + 64 u) of a group that is WHOLLY ADMISSIBLE for it: not empty, every slot a face, every face
+// admissible (then the inequality of the pruning margin holds for an admissible face of g), or (c) +inf.  Under a bound
+// of +inf every group whose lb is finite is admitted until an admissible face has been found; the first group a lane
+// tests (its seed) is then the nearest group, by far(g), that is not wholly inadmissible.  A seed is only a group
+// tested first: it carries no bound.
+//   The cones.  cp_group_bounds_kernel<true> stores per (body, group) an axis A (the normalised sum of the faces' unit
+// normals m / |m|), cos beta and sin beta of the largest angle beta between A and one of them, the smallest and the
+// largest mm, and a flag: usable only if every slot of the group is a face with kCpSaneLo <= mm <= kCpSaneHi and the
+// sum has a direction.  Nothing in it depends on the queries.  With alpha the angle between A and n, every face normal
+// of the group makes an angle in [alpha - beta, alpha + beta] with n, so for a lane with kCpNormalLo <= nn <= kCpNormalHi,
+// kCpPairLo <= mm nn <= kCpPairHi for every face of the group, and max_angle = theta <= 90 deg:
+//     wholly admissible    if  cos alpha > 0, cos beta > 0 and cos(alpha + beta) >= c + kCpConeMargin
+//                          (alpha, beta < 90 deg, so alpha + beta < 180 deg where the cosine is monotone:
+//                          alpha + beta < theta, every face is within theta of n);
+//     wholly inadmissible  if  cos alpha < cos beta - kCpConeMargin (alpha > beta: the cone does not hold n) and
+//                          cos(alpha - beta) <= c - kCpConeMargin (0 < alpha - beta <= 180 deg, monotone again:
+//                          alpha - beta > theta, no face is within theta of n);
+//     mixed otherwise, and always for an unusable cone or a lane outside the sane range: the rule decides per face.
+// cos(alpha +- beta) = cos alpha cos beta -+ sin alpha sin beta, with sin alpha = |A x n| / |n| and sin beta = |A x m^|
+// of the face that attains beta: cross products, not sqrt(1 - cos^2), which loses half the digits near 0.
+//   The margin.  With mm nn in [1e-24, 1e24] nothing in the rule overflows, and what underflows is harmless: s s and
+// c2 (mm nn) are compared with an absolute error of one denormal step, 1.4e-45, that is 1.4e-21 relative to mm nn,
+// which moves the cosine the comparison decides on by less than sqrt(1.4e-21) = 4e-11.  (The lane's own range,
+// kCpNormalLo <= nn <= kCpNormalHi, is narrower than the faces': |A x n|^2 is formed before the division by |n| and
+// must neither overflow nor lose a sine above 1e-9 to underflow.)  So with u = 2^-24: s carries an absolute error
+// below 3 u |m| |n|, mm nn and c2 (mm nn) and s s a relative one below 7 u together, and the computed rule decides
+// "cos angle(m, n) >= c" for the m it
+// computed with the threshold moved by less than 8 u.  A, m^ and n / |n| are unit vectors to 3 u each; a dot or cross
+// product of two of them adds 3 u; so each of cos alpha, sin alpha, cos beta, sin beta is within 10 u, a product of two
+// of them within 21 u, cos(alpha +- beta) within 43 u, and with the rule's 8 u the two sides of either comparison
+// differ from the exact ones by less than 51 u.  kCpConeMargin = 256 u is five times that: a misclassification can
+// only go towards "mixed", which costs time and no bit.  (A wrong "wholly admissible" would make the bound invalid, a
+// wrong "wholly inadmissible" would drop the winner: tests/test_gpu_oriented_point.py regroups the faces to catch
+// either.)  The cones are computed from the m the rule computes, so a thin face whose computed m is far from its true
+// normal is classified by what the rule will see.
+//   How the sweeps use it.  Sweep 1 takes bound and seed from wholly admissible groups (and the nearest mixed group as
+// the seed where it is nearer); a wholly inadmissible group is never tested by the lane -- cp_next_group gives it a
+// NaN lower bound, which no bound admits -- and a group no lane admits is not staged.  Mixed groups are admitted by the
+// box bound alone; in the exact test cp_eval runs only for the faces cp_admissible passes (a branch: where a wavefront's
+// queries face the same way, whole faces are skipped by all 64 lanes).  m is recomputed from the staged corners by the
+// lane, by the same sequence the cone kernel and the hinted start use.
+//   The hint.  A hinted lane starts from its hint only if the face is in [0, F), admissible for the lane and at a finite
+// d2; then its key is one the unpruned sweep computes too, and the argument of the hinted start holds.  Any other hint
+// takes the unhinted path.
 #include "model.h"
 #include "workspace.h"
 
@@ -50,16 +105,23 @@ constexpr int kCpTri = 9;                           // floats per staged triangl
 constexpr int kCpBox = 8;                           // floats per box
 constexpr float kCpMargin = 64.0f * 5.9604645e-8f;  // 64 * 2^-24, relative to far(g)
 constexpr float kCpDegenerate = 1e-8f;              // |ab x ac|^2 <= this * |ab|^2 |ac|^2: the triangle is its edges
+constexpr int kCpCone = 8;                          // floats per normal cone
+constexpr float kCpConeMargin = 256.0f * 5.9604645e-8f;   // 256 * 2^-24, absolute, on cosines (file header: the cones)
+constexpr float kCpSaneLo = 1e-30f, kCpSaneHi = 1e30f;    // |m|^2 of a face inside: its square root and unit normal are sound
+constexpr float kCpNormalLo = 1e-20f, kCpNormalHi = 1e20f; // |n|^2 inside: |A x n|^2 neither overflows nor underflows
+constexpr float kCpPairLo = 1e-24f, kCpPairHi = 1e24f;    // |m|^2 |n|^2 inside: no under- or overflow that matters in the rule
 constexpr unsigned long long kCpNoKey = 0x7f800000ffffffffull;     // d2 = +inf, face = -1
 
-struct CpLayout { size_t boxes, tris, total; };
+struct CpLayout { size_t boxes, tris, cones, total; };
 
-CpLayout cp_layout(const tuch_contact_model* m, int B)
+// oriented: the unoriented layout, then the cones
+CpLayout cp_layout(const tuch_contact_model* m, int B, bool oriented)
 {
     CpLayout l;
     size_t o = 0;
     l.boxes = tuch_ws_take(o, (size_t)B * m->cp_groups * kCpBox * sizeof(float));
     l.tris = tuch_ws_take(o, (size_t)B * m->F * kCpTri * sizeof(float));
+    l.cones = oriented ? tuch_ws_take(o, (size_t)B * m->cp_groups * kCpCone * sizeof(float)) : o;
     l.total = o;
     return l;
 }
@@ -152,12 +214,73 @@ static __device__ __forceinline__ void cp_box(float px, float py, float pz, cons
     lb = cp_dot(nx, ny, nz, nx, ny, nz);
     far = cp_dot(fx, fy, fz, fx, fy, fz);
 }
+
+// The face normal of the admissibility rule: m = (b - a) x (c - a), one subtraction per component, each component of the
+// product as (x y) - (z w), every operation rounded to float32 on its own (contraction is off here).
+static __device__ __forceinline__ void cp_face_normal(const float* __restrict__ t, float& mx, float& my, float& mz)
+{
+    const float e1x = t[3] - t[0], e1y = t[4] - t[1], e1z = t[5] - t[2];
+    const float e2x = t[6] - t[0], e2y = t[7] - t[1], e2z = t[8] - t[2];
+    mx = (e1y * e2z) - (e1z * e2y);
+    my = (e1z * e2x) - (e1x * e2z);
+    mz = (e1x * e2y) - (e1y * e2x);
+}
+
+static __device__ __forceinline__ float cp_sq3(float x, float y, float z) { return (x * x + y * y) + z * z; }
+
+// THE admissibility of a (query normal, triangle) pair (file header: the oriented search): s > 0 and s^2 >= c2 (mm nn),
+// one sequence wherever it runs; false for a face without area (s = 0) and for NaN corners
+static __device__ __forceinline__ bool cp_admissible(const float* __restrict__ t, float nx, float ny, float nz, float nn, float c2)
+{
+    float mx, my, mz;
+    cp_face_normal(t, mx, my, mz);
+    const float mm = cp_sq3(mx, my, mz);
+    const float s = (mx * nx + my * ny) + mz * nz;
+    return s > 0.0f && s * s >= c2 * (mm * nn);
+}
 #pragma clang fp contract(fast)
 
+// A group's normal cone against one lane's normal n with inv = 1 / |n|: 0 mixed, 1 wholly admissible, 2 wholly
+// inadmissible (file header: the cones).  cone = axis.xyz, cos beta, sin beta, usable (> 0), the smallest and the
+// largest |m|^2 of the group's faces
+static __device__ __forceinline__ int cp_cone_class(const float* __restrict__ cone, float nx, float ny, float nz, float inv, float c)
+{
+    const float ax = cone[0], ay = cone[1], az = cone[2], cb = cone[3], sb = cone[4];
+    const float ca = (ax * nx + ay * ny + az * nz) * inv;
+    const float wx = ay * nz - az * ny, wy = az * nx - ax * nz, wz = ax * ny - ay * nx;
+    const float sa = __builtin_sqrtf(wx * wx + wy * wy + wz * wz) * inv;
+    const float sum = ca * cb - sa * sb;            // cos(alpha + beta)
+    const float dif = ca * cb + sa * sb;            // cos(alpha - beta)
+    int cls = 0;
+    if (ca > 0.0f && cb > 0.0f && sum >= c + kCpConeMargin) cls = 1;
+    if (ca < cb - kCpConeMargin && dif <= c - kCpConeMargin) cls = 2;
+    const float nn = nx * nx + ny * ny + nz * nz;
+    return cone[5] > 0.0f && cone[6] * nn >= kCpPairLo && cone[7] * nn <= kCpPairHi ? cls : 0;
+}
+
+// what a lane of the oriented search knows of its normal: n and nn as the rule takes them, 1 / |n| for the cones
+struct CpNormal {
+    float x, y, z, nn;          // the rule's operands
+    float inv;                  // 1 / |n| (cones only; 0 where they may not classify)
+    bool constrained;           // nn is positive and finite: the rule applies (otherwise every face is admissible)
+    bool conable;               // nn in [kCpNormalLo, kCpNormalHi]: the cones may classify for this lane
+};
+
+// the class of group g for a lane: an unconstrained lane admits everything, a constrained lane outside the sane range
+// leaves every group to the exact rule
+static __device__ __forceinline__ int cp_lane_class(const CpNormal& nm, const float* __restrict__ cones, int g, float c)
+{
+    if (!nm.constrained) return 1;
+    if (!nm.conable) return 0;
+    return cp_cone_class(cones + (size_t)g * kCpCone, nm.x, nm.y, nm.z, nm.inv, c);
+}
+
+template <bool kCone>
 __global__ __launch_bounds__(64) void cp_group_bounds_kernel(const float* __restrict__ verts, const int32_t* __restrict__ faces,
                                                             const int32_t* __restrict__ face_list,
                                                             const int32_t* __restrict__ group_off, int V, int F, int G,
-                                                            float* __restrict__ boxes, float* __restrict__ tris)
+                                                            float* __restrict__ boxes, float* __restrict__ tris,
+                                                            float* __restrict__ cones)
 {
     const int g = blockIdx.x, b = blockIdx.y, lane = threadIdx.x;
     const int first = group_off[g];
@@ -166,7 +289,9 @@ __global__ __launch_bounds__(64) void cp_group_bounds_kernel(const float* __rest
     const float inf = __builtin_huge_valf();
     float lo[3] = {inf, inf, inf}, hi[3] = {-inf, -inf, -inf};
     const int slot = first + lane;
-    if (lane < n && slot >= 0 && slot < F) {
+    const bool has_face = lane < n && slot >= 0 && slot < F;
+    float t[kCpTri] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (has_face) {
         const int f = cp_clamp_index(face_list[slot], F);
         float* out = tris + ((size_t)b * F + slot) * kCpTri;
         for (int k = 0; k < 3; ++k) {
@@ -174,9 +299,50 @@ __global__ __launch_bounds__(64) void cp_group_bounds_kernel(const float* __rest
             const float* x = verts + ((size_t)b * V + vi) * 3;
             for (int c = 0; c < 3; ++c) {
                 out[3 * k + c] = x[c];
+                if (kCone) t[3 * k + c] = x[c];
                 lo[c] = __builtin_fminf(lo[c], x[c]);
                 hi[c] = __builtin_fmaxf(hi[c], x[c]);
             }
+        }
+    }
+    if (kCone) {
+        // The group's normal cone (file header): the axis is the normalised sum of the unit face normals, beta the
+        // largest angle between the axis and one of them, kept as the (cos, sin) of the face that attains it.  Usable
+        // only when every slot of the group is a face whose |m|^2 is in the sane range and the sum has a direction.
+        float mx, my, mz;
+        cp_face_normal(t, mx, my, mz);
+        const float mm = cp_sq3(mx, my, mz);
+        const bool sane = has_face && mm >= kCpSaneLo && mm <= kCpSaneHi;
+        const float inv = sane ? 1.0f / __builtin_sqrtf(mm) : 0.0f;
+        const float ux = mx * inv, uy = my * inv, uz = mz * inv;
+        float sx = ux, sy = uy, sz = uz;
+        for (int d = 32; d > 0; d >>= 1) {
+            sx += __shfl_xor(sx, d, 64);
+            sy += __shfl_xor(sy, d, 64);
+            sz += __shfl_xor(sz, d, 64);
+        }
+        sx = __shfl(sx, 0, 64); sy = __shfl(sy, 0, 64); sz = __shfl(sz, 0, 64);
+        const float len2 = sx * sx + sy * sy + sz * sz;
+        const bool usable = n > 0 && __popcll(__ballot(sane)) == n && len2 >= 1e-6f && len2 <= 1e8f;
+        const float il = usable ? 1.0f / __builtin_sqrtf(len2) : 0.0f;
+        const float ax = sx * il, ay = sy * il, az = sz * il;
+        const float wx = ay * uz - az * uy, wy = az * ux - ax * uz, wz = ax * uy - ay * ux;
+        const float ca = sane ? ax * ux + ay * uy + az * uz : 2.0f;
+        const float sa = __builtin_sqrtf(wx * wx + wy * wy + wz * wz);
+        float cb = ca;
+        for (int d = 32; d > 0; d >>= 1) cb = __builtin_fminf(cb, __shfl_xor(cb, d, 64));
+        cb = __shfl(cb, 0, 64);
+        const unsigned long long who = __ballot(ca == cb);
+        const float sb = __shfl(sa, who ? __ffsll((long long)who) - 1 : 0, 64);
+        float mm_lo = sane ? mm : inf, mm_hi = sane ? mm : 0.0f;
+        for (int d = 32; d > 0; d >>= 1) {
+            mm_lo = __builtin_fminf(mm_lo, __shfl_xor(mm_lo, d, 64));
+            mm_hi = __builtin_fmaxf(mm_hi, __shfl_xor(mm_hi, d, 64));
+        }
+        if (lane == 0) {
+            float* cone = cones + ((size_t)b * G + g) * kCpCone;
+            cone[0] = ax; cone[1] = ay; cone[2] = az; cone[3] = cb;
+            cone[4] = sb; cone[5] = usable && who ? 1.0f : 0.0f; cone[6] = mm_lo; cone[7] = mm_hi;
         }
     }
     for (int d = 32; d > 0; d >>= 1)
@@ -192,14 +358,18 @@ __global__ __launch_bounds__(64) void cp_group_bounds_kernel(const float* __rest
 }
 
 // the first group at or behind g that some lane admits (G: none) and that was not visited as a seed; lbm = this lane's
-// lb - margin * far of that group
+// lb - margin * far of that group.  kOriented: NaN (admitted under no bound) where the group's cone shows that no face
+// of it is admissible for this lane.
+template <bool kOriented>
 static __device__ __forceinline__ int cp_next_group(const float* __restrict__ box, int G, int g, float px, float py, float pz,
-                                                    float bound, bool active, int seed, float& lbm)
+                                                    float bound, bool active, int seed, float& lbm, const CpNormal& nm,
+                                                    const float* __restrict__ cones, float c)
 {
     for (; g < G; ++g) {
         float lb, far;
         cp_box(px, py, pz, box + (size_t)g * kCpBox, lb, far);
         lbm = lb - kCpMargin * far;
+        if (kOriented && cp_lane_class(nm, cones, g, c) == 2) lbm = __builtin_nanf("");
         if (__ballot(active && seed == g) == 0ull && __ballot(active && lbm <= bound) != 0ull) break;
     }
     return g;
@@ -237,11 +407,13 @@ static __device__ __forceinline__ void cp_group_range(const int32_t* __restrict_
     if (first < 0 || first + n > F) n = 0;
 }
 
-// the exact test of one lane over a staged group: the smallest key
+// the exact test of one lane over a staged group: the smallest key (kOriented: over the faces admissible for the lane)
+template <bool kOriented>
 static __device__ __forceinline__ unsigned long long cp_test_group(float px, float py, float pz, const float* s_tri, const int32_t* s_fid,
-                                                                   int n, unsigned long long key)
+                                                                   int n, unsigned long long key, const CpNormal& nm, float c2)
 {
     for (int i = 0; i < n; ++i) {
+        if (kOriented && nm.constrained && !cp_admissible(s_tri + i * kCpTri, nm.x, nm.y, nm.z, nm.nn, c2)) continue;
         float v, w;
         const float d = cp_eval(px, py, pz, s_tri + i * kCpTri, v, w);
         const unsigned long long k2 = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)s_fid[i];
@@ -265,14 +437,18 @@ static __device__ __forceinline__ void cp_face_corners(const int32_t* __restrict
 // __restrict__.  Without it the kernel is the unhinted search, instruction for instruction.
 // shift [B,3] or nullptr: the query is points - shift[b], one float32 subtraction per component (scan_fit.hip: the
 // scan in the frame of the untranslated mesh); p - 0 has p's bits.
-template <bool kHinted>
+// kOriented: normals [B,Q,3] and cones [B,G,8] are read, c = cos(max_angle) and c2 = c * c as the host rounded them (file
+// header: the oriented search).  Without it none of the four is touched.
+template <bool kHinted, bool kOriented>
 __global__ __launch_bounds__(64) void cp_search_kernel(const float* __restrict__ points, const float* __restrict__ shift,
                                                       const int32_t* __restrict__ counts, const int32_t* hint, const int32_t* __restrict__ face_group,
                                                       const float* __restrict__ boxes, const float* __restrict__ tris,
                                                       const int32_t* __restrict__ group_off, const int32_t* __restrict__ face_list,
                                                       const int32_t* __restrict__ faces, const float* __restrict__ verts,
                                                       int V, int F, int G, int Q, float* __restrict__ out_d2,
-                                                      int32_t* out_face, float* __restrict__ out_bary)
+                                                      int32_t* out_face, float* __restrict__ out_bary,
+                                                      const float* __restrict__ normals, const float* __restrict__ all_cones,
+                                                      float c, float c2)
 {
     __shared__ float s_tri[2][kCpGroupFaces * kCpTri];
     __shared__ int32_t s_fid[2][kCpGroupFaces];
@@ -301,6 +477,19 @@ __global__ __launch_bounds__(64) void cp_search_kernel(const float* __restrict__
     }
     const float* box = boxes + (size_t)b * G * kCpBox;
     const float* body_tris = tris + (size_t)b * F * kCpTri;
+    CpNormal nm = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, false, false};
+    const float* cones = nullptr;
+    if (kOriented) {
+        cones = all_cones + (size_t)b * G * kCpCone;
+        if (active) {
+            const float* nq = normals + ((size_t)b * Q + q) * 3;
+            nm.x = nq[0]; nm.y = nq[1]; nm.z = nq[2];
+            nm.nn = cp_sq3(nm.x, nm.y, nm.z);
+            nm.constrained = nm.nn > 0.0f && nm.nn < __builtin_huge_valf();
+            nm.conable = nm.nn >= kCpNormalLo && nm.nn <= kCpNormalHi;
+            nm.inv = nm.conable ? 1.0f / __builtin_sqrtf(nm.nn) : 0.0f;
+        }
+    }
     // the hinted start: the hinted face's own key, its exact d2 as the bound, its group as the seed
     unsigned long long key = kCpNoKey;
     bool hinted = false;
@@ -312,7 +501,9 @@ __global__ __launch_bounds__(64) void cp_search_kernel(const float* __restrict__
             float t[kCpTri], v, w;
             cp_face_corners(faces, verts + (size_t)b * V * 3, V, h, t);
             const float d = cp_eval(px, py, pz, t, v, w);
-            if (hg >= 0 && hg < G && d < __builtin_huge_valf()) {       // (false for a NaN d: that lane falls back)
+            // (false for a NaN d: that lane falls back; kOriented: so does one whose hinted face the rule rejects)
+            if (hg >= 0 && hg < G && d < __builtin_huge_valf() &&
+                (!kOriented || !nm.constrained || cp_admissible(t, nm.x, nm.y, nm.z, nm.nn, c2))) {
                 hinted = true;
                 seed = hg;
                 key = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)h;
@@ -322,12 +513,27 @@ __global__ __launch_bounds__(64) void cp_search_kernel(const float* __restrict__
     // sweep 1: an upper bound of the answer, and the group that gives it (this lane's seed); not for a hinted lane, and
     // not at all where every query of the wavefront is hinted
     float ub = __builtin_huge_valf();
-    if (!kHinted || __ballot(active && !hinted) != 0ull)
+    if (!kOriented) {
+        if (!kHinted || __ballot(active && !hinted) != 0ull)
+            for (int g = 0; g < G; ++g) {
+                float lb, far;
+                cp_box(px, py, pz, box + (size_t)g * kCpBox, lb, far);
+                if (far < ub && !(kHinted && hinted)) { ub = far; seed = g; }
+            }
+    } else if (__ballot(active && !hinted) != 0ull) {
+        // the bound only from groups wholly admissible for the lane; the nearest mixed group is remembered and is the
+        // seed where it is nearer (a seed is only a group tested first: it carries no bound)
+        float ub_mixed = __builtin_huge_valf();
+        int seed_mixed = -1;
         for (int g = 0; g < G; ++g) {
             float lb, far;
             cp_box(px, py, pz, box + (size_t)g * kCpBox, lb, far);
-            if (far < ub && !(kHinted && hinted)) { ub = far; seed = g; }
+            const int cls = cp_lane_class(nm, cones, g, c);
+            if (cls == 1 && far < ub && !hinted) { ub = far; seed = g; }
+            if (cls == 0 && far < ub_mixed && !hinted) { ub_mixed = far; seed_mixed = g; }
         }
+        if (ub_mixed < ub) seed = seed_mixed;
+    }
     // a lane without a query admits nothing (its bound is below every lb - margin, NaN included)
     float bound = active ? __builtin_fmaf(ub, kCpMargin, ub) : -__builtin_huge_valf();
     if (kHinted && hinted) bound = __uint_as_float((unsigned)(key >> 32));
@@ -347,8 +553,10 @@ __global__ __launch_bounds__(64) void cp_search_kernel(const float* __restrict__
         __syncthreads();
         float lb, far;
         cp_box(px, py, pz, box + (size_t)g * kCpBox, lb, far);
-        if (active && lb - kCpMargin * far <= bound) {
-            key = cp_test_group(px, py, pz, s_tri[buf], s_fid[buf], n, key);
+        bool admit = active && lb - kCpMargin * far <= bound;
+        if (kOriented) admit = admit && cp_lane_class(nm, cones, g, c) != 2;
+        if (admit) {
+            key = cp_test_group<kOriented>(px, py, pz, s_tri[buf], s_fid[buf], n, key, nm, c2);
             bound = __builtin_fminf(bound, __uint_as_float((unsigned)(key >> 32)));
         }
         pending = pending && seed != g;
@@ -356,7 +564,7 @@ __global__ __launch_bounds__(64) void cp_search_kernel(const float* __restrict__
     }
     // sweep 2: the other groups in index order
     float lbm = 0.0f;
-    int g = cp_next_group(box, G, 0, px, py, pz, bound, active, seed, lbm);
+    int g = cp_next_group<kOriented>(box, G, 0, px, py, pz, bound, active, seed, lbm, nm, cones, c);
     if (g < G) {
         cp_group_range(group_off, g, F, first, n);
         cp_stage_load(r, body_tris, face_list, first, n, lane);
@@ -367,13 +575,13 @@ __global__ __launch_bounds__(64) void cp_search_kernel(const float* __restrict__
         const float lbm_now = lbm;
         const int n_now = n;
         // the next group's loads, before this group's tests
-        g = cp_next_group(box, G, g + 1, px, py, pz, bound, active, seed, lbm);
+        g = cp_next_group<kOriented>(box, G, g + 1, px, py, pz, bound, active, seed, lbm, nm, cones, c);
         if (g < G) {
             cp_group_range(group_off, g, F, first, n);
             cp_stage_load(r, body_tris, face_list, first, n, lane);
         }
         if (active && lbm_now <= bound) {
-            key = cp_test_group(px, py, pz, s_tri[buf], s_fid[buf], n_now, key);
+            key = cp_test_group<kOriented>(px, py, pz, s_tri[buf], s_fid[buf], n_now, key, nm, c2);
             bound = __builtin_fminf(bound, __uint_as_float((unsigned)(key >> 32)));
         }
         buf ^= 1;
@@ -461,38 +669,53 @@ extern "C" size_t tuch_closest_point_workspace_bytes(const tuch_contact_model* m
 {
     if (!m || B <= 0 || Q <= 0) return 0;
     tuch_ws_scope scope(m->opt.canary != 0);
-    return cp_layout(m, B).total;
+    return cp_layout(m, B, false).total;
+}
+
+extern "C" size_t tuch_closest_point_oriented_workspace_bytes(const tuch_contact_model* m, int B, int Q)
+{
+    if (!m || B <= 0 || Q <= 0) return 0;
+    tuch_ws_scope scope(m->opt.canary != 0);
+    return cp_layout(m, B, true).total;
 }
 
 // every entry point that searches (scan_fit.hip's too): `name` is the one the errors speak of; hint == nullptr launches
-// the unhinted instantiation, shift == nullptr leaves the points as they are
+// the unhinted instantiation, shift == nullptr leaves the points as they are; normals != nullptr launches the oriented
+// forms with max_angle_cos (the workspace is then tuch_closest_point_oriented_workspace_bytes)
 int tuch_cp_search(const char* name, const tuch_contact_model* m, const float* verts, const float* points, const float* shift,
-                   const int32_t* counts, const int32_t* hint, int B, int Q, float* d2, int32_t* face, float* bary,
-                   void* workspace, size_t workspace_bytes, void* stream)
+                   const float* normals, float max_angle_cos, const int32_t* counts, const int32_t* hint, int B, int Q,
+                   float* d2, int32_t* face, float* bary, void* workspace, size_t workspace_bytes, void* stream)
 {
     TUCH_REQUIRE(m && verts && points && d2 && face && bary, "%s: null pointer", name);
     TUCH_REQUIRE(B >= 0 && B <= 65535 && Q >= 0, "%s: bad sizes B=%d Q=%d", name, B, Q);
+    const bool oriented = normals != nullptr;
     if (B == 0 || Q == 0) return TUCH_OK;
     TUCH_REQUIRE(m->cp_groups > 0 && m->cp_group_off && m->cp_face_list && m->cp_face_group, "%s: the model has no face groups",
                  name);
-    const size_t need = tuch_closest_point_workspace_bytes(m, B, Q);
+    const size_t need = oriented ? tuch_closest_point_oriented_workspace_bytes(m, B, Q) : tuch_closest_point_workspace_bytes(m, B, Q);
     if (!workspace || workspace_bytes < need) {
         tuch_set_error("%s: workspace %zu < %zu bytes", name, workspace_bytes, need);
         return TUCH_ERR_WORKSPACE;
     }
     hipStream_t s = (hipStream_t)stream;
     tuch_ws_scope scope(m->opt.canary != 0);
-    const CpLayout l = scope.record(0, [&] { return cp_layout(m, B); });
+    const CpLayout l = scope.record(0, [&] { return cp_layout(m, B, oriented); });
     scope.arm(workspace, m->canary_hits, s);
     float* boxes = (float*)((char*)workspace + l.boxes);
     float* tris = (float*)((char*)workspace + l.tris);
+    float* cones = oriented ? (float*)((char*)workspace + l.cones) : nullptr;
     const int G = m->cp_groups;
-    hipLaunchKernelGGL(cp_group_bounds_kernel, dim3(G, B), dim3(64), 0, s, verts, (const int32_t*)m->faces,
-                       (const int32_t*)m->cp_face_list, (const int32_t*)m->cp_group_off, m->V, m->F, G, boxes, tris);
-    hipLaunchKernelGGL(hint ? cp_search_kernel<true> : cp_search_kernel<false>, dim3(ceil_div(Q, 64), B), dim3(64), 0, s, points,
-                       shift, counts, hint, (const int32_t*)m->cp_face_group, (const float*)boxes, (const float*)tris,
+    hipLaunchKernelGGL(oriented ? cp_group_bounds_kernel<true> : cp_group_bounds_kernel<false>, dim3(G, B), dim3(64), 0, s, verts,
+                       (const int32_t*)m->faces, (const int32_t*)m->cp_face_list, (const int32_t*)m->cp_group_off, m->V, m->F, G,
+                       boxes, tris, cones);
+    // c2 = c * c in float32, once, here (the rule's threshold)
+    const float c2 = max_angle_cos * max_angle_cos;
+    auto* kernel = oriented ? (hint ? cp_search_kernel<true, true> : cp_search_kernel<false, true>)
+                            : (hint ? cp_search_kernel<true, false> : cp_search_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3(ceil_div(Q, 64), B), dim3(64), 0, s, points, shift, counts, hint,
+                       (const int32_t*)m->cp_face_group, (const float*)boxes, (const float*)tris,
                        (const int32_t*)m->cp_group_off, (const int32_t*)m->cp_face_list, (const int32_t*)m->faces, verts, m->V,
-                       m->F, G, Q, d2, face, bary);
+                       m->F, G, Q, d2, face, bary, normals, (const float*)cones, max_angle_cos, c2);
     return tuch_check_launch(name);
 }
 
@@ -500,16 +723,29 @@ extern "C" int tuch_closest_point(const tuch_contact_model* m, const float* vert
                                   int B, int Q, float* d2, int32_t* face, float* bary, void* workspace, size_t workspace_bytes,
                                   void* stream)
 {
-    return tuch_cp_search("tuch_closest_point", m, verts, points, nullptr, counts, nullptr, B, Q, d2, face, bary, workspace, workspace_bytes,
-                     stream);
+    return tuch_cp_search("tuch_closest_point", m, verts, points, nullptr, nullptr, 0.0f, counts, nullptr, B, Q, d2, face, bary,
+                          workspace, workspace_bytes, stream);
 }
 
 extern "C" int tuch_closest_point_hinted(const tuch_contact_model* m, const float* verts, const float* points,
                                          const int32_t* counts, const int32_t* hint, int B, int Q, float* d2, int32_t* face,
                                          float* bary, void* workspace, size_t workspace_bytes, void* stream)
 {
-    return tuch_cp_search("tuch_closest_point_hinted", m, verts, points, nullptr, counts, hint, B, Q, d2, face, bary, workspace,
-                     workspace_bytes, stream);
+    return tuch_cp_search("tuch_closest_point_hinted", m, verts, points, nullptr, nullptr, 0.0f, counts, hint, B, Q, d2, face, bary,
+                          workspace, workspace_bytes, stream);
+}
+
+extern "C" int tuch_closest_point_oriented(const tuch_contact_model* m, const float* verts, const float* points,
+                                           const float* normals, float max_angle_cos, const int32_t* counts, const int32_t* hint,
+                                           int B, int Q, float* d2, int32_t* face, float* bary, void* workspace,
+                                           size_t workspace_bytes, void* stream)
+{
+    TUCH_REQUIRE(max_angle_cos >= 0.0f && max_angle_cos < 1.0f,
+                 "tuch_closest_point_oriented: max_angle_cos %g is not in [0, 1) (the cosine of an angle in (0, 90] degrees)",
+                 (double)max_angle_cos);
+    TUCH_REQUIRE(normals, "tuch_closest_point_oriented: null pointer");
+    return tuch_cp_search("tuch_closest_point_oriented", m, verts, points, nullptr, normals, max_angle_cos, counts, hint, B, Q, d2,
+                          face, bary, workspace, workspace_bytes, stream);
 }
 
 extern "C" int tuch_closest_point_bwd(const tuch_contact_model* m, const float* verts, const float* points, const int32_t* face,

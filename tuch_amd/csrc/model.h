@@ -112,10 +112,12 @@ extern "C" int tuch_winding_points(const tuch_contact_model* m, const float* ver
 
 // The closest-point search behind every entry point that needs it (closest_point.hip): queries points [B,Q,3] - shift[b]
 // (shift [B,3] or nullptr), hint [B,Q] or nullptr (may alias face); `name` is the entry point the errors speak of.
+// normals [B,Q,3] or nullptr: with them the oriented search under max_angle_cos, whose workspace is the oriented size.
 extern "C" size_t tuch_closest_point_workspace_bytes(const tuch_contact_model* m, int B, int Q);
+extern "C" size_t tuch_closest_point_oriented_workspace_bytes(const tuch_contact_model* m, int B, int Q);
 int tuch_cp_search(const char* name, const tuch_contact_model* m, const float* verts, const float* points, const float* shift,
-                   const int32_t* counts, const int32_t* hint, int B, int Q, float* d2, int32_t* face, float* bary,
-                   void* workspace, size_t workspace_bytes, void* stream);
+                   const float* normals, float max_angle_cos, const int32_t* counts, const int32_t* hint, int B, int Q,
+                   float* d2, int32_t* face, float* bary, void* workspace, size_t workspace_bytes, void* stream);
 // rho of tuch_scan_fit_terms (scan_fit.hip), as include/tuch_amd.h numbers them
 enum { TUCH_SCAN_RHO_SQUARED = 0, TUCH_SCAN_RHO_DISTANCE = 1, TUCH_SCAN_RHO_GMOF = 2 };
 

@@ -30,12 +30,13 @@ typedef __attribute__((address_space(1))) float gfloat;
 
 struct ScanLayout { size_t search, fixed, partial, total; };
 
-ScanLayout scan_layout(const tuch_contact_model* m, int B, int Q)
+ScanLayout scan_layout(const tuch_contact_model* m, int B, int Q, bool oriented)
 {
     ScanLayout l;
     size_t o = 0;
     // (the search guards its own regions: its layout is recorded by its own scope at this offset)
-    l.search = tuch_ws_take(o, tuch_closest_point_workspace_bytes(m, B, Q), false);
+    l.search = tuch_ws_take(o, oriented ? tuch_closest_point_oriented_workspace_bytes(m, B, Q)
+                                        : tuch_closest_point_workspace_bytes(m, B, Q), false);
     l.fixed = tuch_ws_take(o, (size_t)B * m->V * 3 * sizeof(long long));
     l.partial = tuch_ws_take(o, (size_t)B * ceil_div(Q, kBlock) * kPart * sizeof(float));
     l.total = o;
@@ -217,32 +218,43 @@ extern "C" size_t tuch_scan_fit_workspace_bytes(const tuch_contact_model* m, int
 {
     if (!m || B <= 0 || Q <= 0) return 0;
     tuch_ws_scope scope(m->opt.canary != 0);
-    return scan_layout(m, B, Q).total;
+    return scan_layout(m, B, Q, false).total;
 }
 
-extern "C" int tuch_scan_fit_terms(const tuch_contact_model* m, const float* verts, const float* transl, const float* points,
-                                   const int32_t* counts, const float* weights, const int32_t* hint, int B, int Q, int rho,
-                                   float sigma, float* d2, int32_t* face, float* bary, int* ticket, float* per_body,
-                                   float* total, float* grad_verts, float* grad_transl, float* grad_points, void* workspace,
-                                   size_t workspace_bytes, void* stream)
+extern "C" size_t tuch_scan_fit_oriented_workspace_bytes(const tuch_contact_model* m, int B, int Q)
+{
+    if (!m || B <= 0 || Q <= 0) return 0;
+    tuch_ws_scope scope(m->opt.canary != 0);
+    return scan_layout(m, B, Q, true).total;
+}
+
+// both entry points: normals == nullptr is tuch_scan_fit_terms
+static int scan_fit_terms(const char* name, const tuch_contact_model* m, const float* verts, const float* transl, const float* points,
+                          const float* normals, float max_angle_cos, const int32_t* counts, const float* weights,
+                          const int32_t* hint, int B, int Q, int rho, float sigma, float* d2, int32_t* face, float* bary,
+                          int* ticket, float* per_body, float* total, float* grad_verts, float* grad_transl, float* grad_points,
+                          void* workspace, size_t workspace_bytes, void* stream)
 {
     TUCH_REQUIRE(m && verts && transl && points && d2 && face && bary && ticket && per_body && total && grad_verts && grad_transl,
-                 "tuch_scan_fit_terms: null pointer");
-    TUCH_REQUIRE(B > 0 && B <= 65535 && Q > 0 && (long long)B * ceil_div(Q, kBlock) < (1ll << 30),
-                 "tuch_scan_fit_terms: bad sizes B=%d Q=%d", B, Q);
+                 "%s: null pointer", name);
+    TUCH_REQUIRE(B > 0 && B <= 65535 && Q > 0 && (long long)B * ceil_div(Q, kBlock) < (1ll << 30), "%s: bad sizes B=%d Q=%d", name,
+                 B, Q);
     TUCH_REQUIRE(rho == TUCH_SCAN_RHO_SQUARED || rho == TUCH_SCAN_RHO_DISTANCE || (rho == TUCH_SCAN_RHO_GMOF && sigma > 0.0f),
-                 "tuch_scan_fit_terms: rho %d (0 squared, 1 distance, 2 gmof with sigma > 0; sigma = %g)", rho, (double)sigma);
-    const size_t need = tuch_scan_fit_workspace_bytes(m, B, Q);
+                 "%s: rho %d (0 squared, 1 distance, 2 gmof with sigma > 0; sigma = %g)", name, rho, (double)sigma);
+    const bool oriented = normals != nullptr;
+    const size_t need = oriented ? tuch_scan_fit_oriented_workspace_bytes(m, B, Q) : tuch_scan_fit_workspace_bytes(m, B, Q);
     if (!workspace || workspace_bytes < need) {
-        tuch_set_error("tuch_scan_fit_terms: workspace %zu < %zu bytes", workspace_bytes, need);
+        tuch_set_error("%s: workspace %zu < %zu bytes", name, workspace_bytes, need);
         return TUCH_ERR_WORKSPACE;
     }
     hipStream_t s = (hipStream_t)stream;
     tuch_ws_scope scope(m->opt.canary != 0);
-    const ScanLayout l = scope.record(0, [&] { return scan_layout(m, B, Q); });
+    const ScanLayout l = scope.record(0, [&] { return scan_layout(m, B, Q, oriented); });
     scope.arm(workspace, m->canary_hits, s);
-    const int rc = tuch_cp_search("tuch_scan_fit_terms", m, verts, points, transl, counts, hint, B, Q, d2, face, bary,
-                                  (char*)workspace + l.search, tuch_closest_point_workspace_bytes(m, B, Q), stream);
+    const int rc = tuch_cp_search(name, m, verts, points, transl, normals, max_angle_cos, counts, hint, B, Q, d2, face, bary,
+                                  (char*)workspace + l.search,
+                                  oriented ? tuch_closest_point_oriented_workspace_bytes(m, B, Q)
+                                           : tuch_closest_point_workspace_bytes(m, B, Q), stream);
     if (rc != TUCH_OK) return rc;
     long long* fixed = (long long*)((char*)workspace + l.fixed);
     float* partial = (float*)((char*)workspace + l.partial);
@@ -265,5 +277,32 @@ extern "C" int tuch_scan_fit_terms(const tuch_contact_model* m, const float* ver
                            Q, rho, sigma2, partial, ticket, per_body, total, grad_points, grad_verts, (long long*)nullptr,
                            grad_transl);
     }
-    return tuch_check_launch("tuch_scan_fit_terms");
+    return tuch_check_launch(name);
+}
+
+extern "C" int tuch_scan_fit_terms(const tuch_contact_model* m, const float* verts, const float* transl, const float* points,
+                                   const int32_t* counts, const float* weights, const int32_t* hint, int B, int Q, int rho,
+                                   float sigma, float* d2, int32_t* face, float* bary, int* ticket, float* per_body,
+                                   float* total, float* grad_verts, float* grad_transl, float* grad_points, void* workspace,
+                                   size_t workspace_bytes, void* stream)
+{
+    return scan_fit_terms("tuch_scan_fit_terms", m, verts, transl, points, nullptr, 0.0f, counts, weights, hint, B, Q, rho, sigma,
+                          d2, face, bary, ticket, per_body, total, grad_verts, grad_transl, grad_points, workspace,
+                          workspace_bytes, stream);
+}
+
+extern "C" int tuch_scan_fit_terms_oriented(const tuch_contact_model* m, const float* verts, const float* transl,
+                                            const float* points, const float* normals, float max_angle_cos,
+                                            const int32_t* counts, const float* weights, const int32_t* hint, int B, int Q,
+                                            int rho, float sigma, float* d2, int32_t* face, float* bary, int* ticket,
+                                            float* per_body, float* total, float* grad_verts, float* grad_transl,
+                                            float* grad_points, void* workspace, size_t workspace_bytes, void* stream)
+{
+    TUCH_REQUIRE(max_angle_cos >= 0.0f && max_angle_cos < 1.0f,
+                 "tuch_scan_fit_terms_oriented: max_angle_cos %g is not in [0, 1) (the cosine of an angle in (0, 90] degrees)",
+                 (double)max_angle_cos);
+    TUCH_REQUIRE(normals, "tuch_scan_fit_terms_oriented: null pointer");
+    return scan_fit_terms("tuch_scan_fit_terms_oriented", m, verts, transl, points, normals, max_angle_cos, counts, weights, hint,
+                          B, Q, rho, sigma, d2, face, bary, ticket, per_body, total, grad_verts, grad_transl, grad_points,
+                          workspace, workspace_bytes, stream);
 }

@@ -149,6 +149,14 @@ class ScanFitter:
     where it writes its indices; the cloud is rebuilt and the tensor reset to -1 at the start of every call, outside the
     replayed loop.  With the default 0.0 nothing of this exists: the bits and the launches are those of the one-sided fit.
 
+    ``max_normal_angle`` (degrees, in (0, 90]) with ``normals`` [B,Q,3] at the call makes the scan -> model term
+    normal-compatible (ops.scan_fit with normals: a point is matched only to faces whose normal is within the angle of
+    its own; zero rows are unconstrained; a point left without a match adds nothing and keeps its weight in the
+    normaliser).  The session then holds a static normals buffer.  Normals affect the scan -> model term only: the
+    model -> scan term stays as it is and keeps ``max_distance`` as its rejection.  Without normals every launch and every
+    bit is that of the fit without the option.  ``face`` is -1 for the points left without a match at the final
+    evaluation: the share matched is ``(face >= 0)``.
+
     ``vertices`` [B,V,3] include the translation; ``loss`` [B] (the scan -> model term), ``face`` [B,Q] and ``bary``
     [B,Q,3] are those of the evaluation after the last update; the other direction's is ``self.model_to_scan_result`` =
     CloudFit(loss [B], d2 [B,V], index [B,V]) (None when the option is off).  ``global_orient`` is held fixed unless ``fit_global_orient`` is set.  Inputs are
@@ -156,7 +164,7 @@ class ScanFitter:
 
     def __init__(self, smpl, model, step_size=1e-2, num_iters=300, fit_global_orient=True, rho='distance', sigma=None,
                  use_hint=True, use_graph=True, record_history=False, model_to_scan=0.0, vertex_weights=None,
-                 max_distance=None, resolution=64):
+                 max_distance=None, resolution=64, max_normal_angle=None):
         if rho not in ops.SCAN_RHO:
             raise ValueError('ScanFitter: rho must be one of %s, got %r' % (sorted(ops.SCAN_RHO), rho))
         if rho == 'gmof' and not (sigma is not None and float(sigma) > 0.0):
@@ -165,6 +173,8 @@ class ScanFitter:
             raise ValueError('ScanFitter: model_to_scan must be >= 0, got %r' % (model_to_scan,))
         if max_distance is not None and not float(max_distance) > 0.0:
             raise ValueError('ScanFitter: max_distance must be > 0 (or None), got %r' % (max_distance,))
+        if max_normal_angle is not None and not (0.0 < float(max_normal_angle) <= 90.0):
+            raise ValueError('ScanFitter: max_normal_angle must be in (0, 90] degrees (or None), got %r' % (max_normal_angle,))
         if not (isinstance(resolution, int) and 1 <= resolution <= 256):
             raise ValueError('ScanFitter: resolution must be an int in 1 .. 256, got %r' % (resolution,))
         num_verts = int(smpl.v_template.shape[0])
@@ -182,6 +192,7 @@ class ScanFitter:
         self.vertex_weights = vertex_weights
         self.max_distance = None if max_distance is None else float(max_distance)
         self.resolution = resolution
+        self.max_normal_angle = None if max_normal_angle is None else float(max_normal_angle)
         self.model_to_scan_result = None
         self.use_graph = use_graph
         # as MeshFitter: the objective and the parameters *before* every update in self.history['fit'], the parameters in
@@ -193,12 +204,13 @@ class ScanFitter:
         self.graph_replayed = {}
         self._sessions = {}
 
-    def _session(self, batch, num_points, with_counts, with_weights, device):
+    def _session(self, batch, num_points, with_counts, with_weights, device, with_normals=False):
         """(key, session): the static tensors, the iteration closure and the loop of a fit with these constants."""
         key = (batch, num_points, bool(with_counts), bool(with_weights), device.index, float(self.step_size),
                bool(self.fit_global_orient), self.rho, None if self.sigma is None else float(self.sigma), bool(self.use_hint),
                bool(self.record_history), self.model_to_scan,
-               id(self.vertex_weights) if self.vertex_weights is not None else None, self.max_distance, self.resolution)
+               id(self.vertex_weights) if self.vertex_weights is not None else None, self.max_distance, self.resolution,
+               bool(with_normals), self.max_normal_angle if with_normals else None)
         sess = self._sessions.get(key)
         if sess is not None:
             return key, sess
@@ -206,8 +218,10 @@ class ScanFitter:
         t = dict(body_pose=z(batch, 69), betas=z(batch, 10), transl=z(batch, 3), global_orient=z(batch, 3),
                  points=z(batch, num_points, 3), hint=z(batch, num_points, dtype=torch.int32),
                  counts=z(batch, dtype=torch.int32) if with_counts else None,
-                 weights=z(batch, num_points) if with_weights else None)
+                 weights=z(batch, num_points) if with_weights else None,
+                 normals=z(batch, num_points, 3) if with_normals else None)
         smpl, model = self.smpl, self.model
+        angle = self.max_normal_angle if with_normals else None
         hint = t['hint'] if self.use_hint else None
         cloud = vw = near = None
         if self.model_to_scan > 0.0:
@@ -226,7 +240,7 @@ class ScanFitter:
             out = smpl(global_orient=t['global_orient'], body_pose=t['body_pose'], betas=t['betas'])
             # (the hint tensor receives the new faces: the aliasing tuch_closest_point_hinted allows)
             total, _, _ = ops.scan_fit(model, out.vertices, t['transl'], t['points'], t['counts'], t['weights'], hint,
-                                       self.rho, self.sigma, face_out=hint)
+                                       self.rho, self.sigma, face_out=hint, normals=t['normals'], max_angle=angle)
             if cloud is not None:
                 # the two vertex gradients meet in autograd's accumulation (one add of [B,V,3])
                 other, _, _ = ops.cloud_fit(cloud, out.vertices, t['transl'], vw, near, self.rho, self.sigma,
@@ -240,7 +254,8 @@ class ScanFitter:
                     stage=SMPLifyDC._Stage(self, 'fit', params, iteration, {}))
         return key, sess
 
-    def __call__(self, points, global_orient, counts=None, weights=None, body_pose=None, betas=None, transl=None):
+    def __call__(self, points, global_orient, counts=None, weights=None, body_pose=None, betas=None, transl=None,
+                 normals=None):
         if points.dim() != 3 or points.shape[2] != 3 or points.shape[0] == 0 or points.shape[1] == 0:
             raise ValueError('ScanFitter: points must be [B,Q,3], got %s' % (tuple(points.shape),))
         batch, num_points = points.shape[0], points.shape[1]
@@ -249,6 +264,10 @@ class ScanFitter:
                                    ('weights', weights, (batch, num_points))):
             if value is not None and tuple(value.shape) != shape:
                 raise ValueError('ScanFitter: %s has shape %s, expected %s' % (name, tuple(value.shape), shape))
+        if normals is not None and self.max_normal_angle is None:
+            raise ValueError('ScanFitter: normals need max_normal_angle (the fitter was created without it)')
+        if normals is not None and tuple(normals.shape) != (batch, num_points, 3):
+            raise ValueError('ScanFitter: normals has shape %s, expected %s' % (tuple(normals.shape), (batch, num_points, 3)))
         device = points.device
         if device.type != 'cuda':
             raise RuntimeError('ScanFitter runs on a HIP device (there is no host fallback); got tensors on %s' % device)
@@ -263,7 +282,7 @@ class ScanFitter:
             self.history = {'fit': []}
         # graph replays never run on the NULL stream (ops.py)
         with ops.off_default_stream(device) if on_gpu else contextlib.nullcontext():
-            key, sess = self._session(batch, num_points, counts is not None, weights is not None, device)
+            key, sess = self._session(batch, num_points, counts is not None, weights is not None, device, normals is not None)
             t = sess['t']
             with torch.no_grad():
                 t['points'].copy_(points)
@@ -273,6 +292,8 @@ class ScanFitter:
                     t['counts'].copy_(counts.clamp(0, num_points))
                 if weights is not None:
                     t['weights'].copy_(weights)
+                if normals is not None:
+                    t['normals'].copy_(normals)
                 for name, value in (('body_pose', body_pose), ('betas', betas)):
                     t[name].zero_() if value is None else t[name].copy_(value)
                 if transl is not None:
@@ -303,7 +324,8 @@ class ScanFitter:
                 verts = self.smpl(global_orient=t['global_orient'], body_pose=t['body_pose'], betas=t['betas']).vertices
                 hint = t['hint'] if self.use_hint else None
                 _, loss, near = ops.scan_fit(self.model, verts, t['transl'], t['points'], t['counts'], t['weights'], hint,
-                                             self.rho, self.sigma)
+                                             self.rho, self.sigma, normals=t['normals'],
+                                             max_angle=self.max_normal_angle if normals is not None else None)
                 vertices = verts + t['transl'][:, None]
                 self.model_to_scan_result = None
                 if sess['cloud'] is not None:

@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import math
 import os
 import weakref
 from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
@@ -1386,7 +1387,8 @@ class ContactModel:
         return w, ext
 
     def closest_point(self, verts: torch.Tensor, points: torch.Tensor, counts: Optional[torch.Tensor] = None,
-                      hint: Optional[torch.Tensor] = None) -> 'ClosestPoint':
+                      hint: Optional[torch.Tensor] = None, normals: Optional[torch.Tensor] = None,
+                      max_angle: Optional[float] = None) -> 'ClosestPoint':
         """The nearest point of this mesh posed by verts [B,V,3] for arbitrary points [B,Q,3] (csrc/closest_point.hip):
         ``ClosestPoint(d2 [B,Q], face [B,Q] int32, bary [B,Q,3])`` with the nearest point = sum_k bary[k] *
         verts[faces[face][k]].  counts [B] int32 marks how many points per body are real; the others get d2 = inf,
@@ -1398,13 +1400,23 @@ class ContactModel:
         hint [B,Q] int32: per query a face that is probably the answer (a fitting loop passes the previous iteration's
         ``face``).  It changes no bit of the result, whatever it holds (wrong faces and indices out of range included);
         a valid one lets the query start from that face's exact distance instead of from a walk over every box of the
-        body (tuch_closest_point_hinted)."""
+        body (tuch_closest_point_hinted).
+        normals [B,Q,3] with max_angle in degrees, in (0, 90]: the normal-compatible search (tuch_closest_point_oriented).
+        A face is a candidate for a query only if its normal (b - a) x (c - a) is within max_angle of the query's normal
+        (any length, in the frame of verts) -- decided by one fixed float32 sequence (include/tuch_amd.h), so the same
+        bits hold alone or in a batch, for any order, any hint and any grouping of the faces.  A query with a zero or
+        non-finite normal is unconstrained (the plain call's bits); one without an admissible face gets d2 = inf,
+        face = -1, bary = 0 and no gradient.  Normals are constants: they get no gradient.  Both or neither must be
+        given; with neither the call is the plain one."""
+        cos = _max_angle_cos(normals, max_angle, points, 'closest_point')
         if verts.dim() != 3 or points.dim() != 3 or verts.shape[0] != points.shape[0] or verts.shape[1] != self.num_verts:
             raise _C.TuchError('closest_point: verts [B,%d,3] and points [B,Q,3] expected, got %s and %s'
                                % (self.num_verts, tuple(verts.shape), tuple(points.shape)))
         if counts is not None:
             counts = counts.to(torch.int32).contiguous()
         hint = _hint_of(hint, points, 'closest_point')
+        if cos is not None:
+            return ClosestPoint(*_ClosestPoint.apply(verts, points, self, counts, hint, _f32(normals.detach()), cos))
         return ClosestPoint(*_ClosestPoint.apply(verts, points, self, counts, hint))
 
     def face_groups(self):
@@ -1492,21 +1504,48 @@ def _hint_of(hint, points, what):
     return hint.to(torch.int32).contiguous()
 
 
+def _max_angle_cos(normals, max_angle, points, what):
+    """None without normals and angle; otherwise the float32 cosine the C entry points take: cos(max_angle) in double,
+    rounded once.  One of the two alone, an angle outside (0, 90] degrees or normals of another shape raise ValueError."""
+    if normals is None and max_angle is None:
+        return None
+    if normals is None or max_angle is None:
+        raise ValueError('%s: normals and max_angle go together, got %s' % (what, 'normals only' if max_angle is None
+                                                                             else 'max_angle only'))
+    angle = float(max_angle)
+    if not (0.0 < angle <= 90.0):
+        raise ValueError('%s: max_angle must be in (0, 90] degrees, got %r' % (what, max_angle))
+    if not torch.is_tensor(normals) or tuple(normals.shape) != tuple(points.shape) or normals.device != points.device:
+        raise ValueError('%s: normals must be [B,Q,3] = %s on %s, got %s'
+                         % (what, tuple(points.shape), points.device,
+                            (tuple(normals.shape), normals.device) if torch.is_tensor(normals) else type(normals)))
+    cos = float(np.float32(math.cos(math.radians(angle))))
+    # (90 degrees: cos is 6e-17 in double; anything in [0, 1) is the contract)
+    return min(max(cos, 0.0), float(np.nextafter(np.float32(1.0), np.float32(0.0))))
+
+
 class _ClosestPoint(torch.autograd.Function):
     """ContactModel.closest_point: tuch_closest_point_hinted forward (hint None: tuch_closest_point's search),
-    tuch_closest_point_bwd (the envelope form) backward."""
+    tuch_closest_point_bwd (the envelope form) backward.  With normals and the cosine: tuch_closest_point_oriented."""
 
     @staticmethod
-    def forward(ctx, verts, points, model: ContactModel, counts, hint):
+    def forward(ctx, verts, points, model: ContactModel, counts, hint, normals=None, cos=None):
         v, pts = _f32(verts), _f32(points)
         b, q, _ = pts.shape
         L = _C.lib()
         d2 = torch.empty(b, q, dtype=torch.float32, device=pts.device)
         face = torch.empty(b, q, dtype=torch.int32, device=pts.device)
         bary = torch.empty(b, q, 3, dtype=torch.float32, device=pts.device)
-        nbytes = L.tuch_closest_point_workspace_bytes(model._handle, b, q)
+        if normals is not None:
+            nbytes = L.tuch_closest_point_oriented_workspace_bytes(model._handle, b, q)
+        else:
+            nbytes = L.tuch_closest_point_workspace_bytes(model._handle, b, q)
         ws = _workspace(nbytes, pts.device)
-        if b and q:
+        if b and q and normals is not None:
+            _C.check(L.tuch_closest_point_oriented(model._handle, _C.ptr(v), _C.ptr(pts), _C.ptr(normals), cos, _C.ptr(counts),
+                                                   _C.ptr(hint), b, q, _C.ptr(d2), _C.ptr(face), _C.ptr(bary), _C.ptr(ws),
+                                                   nbytes, _C.stream()))
+        elif b and q:
             _C.check(L.tuch_closest_point_hinted(model._handle, _C.ptr(v), _C.ptr(pts), _C.ptr(counts), _C.ptr(hint), b, q,
                                                  _C.ptr(d2), _C.ptr(face), _C.ptr(bary), _C.ptr(ws), nbytes, _C.stream()))
         ctx.save_for_backward(v, pts, face, bary)
@@ -1519,8 +1558,9 @@ class _ClosestPoint(torch.autograd.Function):
         v, pts, face, bary = ctx.saved_tensors
         b, q, _ = pts.shape
         want_v, want_p = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        extra = (None,) * (len(ctx.needs_input_grad) - 2)
         if b == 0 or q == 0 or not (want_v or want_p):
-            return (torch.zeros_like(v) if want_v else None), (torch.zeros_like(pts) if want_p else None), None, None, None
+            return ((torch.zeros_like(v) if want_v else None), (torch.zeros_like(pts) if want_p else None)) + extra
         g = grad_d2.to(torch.float32).contiguous()
         gp = torch.empty_like(pts) if want_p else None
         gv = fixed = None
@@ -1531,7 +1571,7 @@ class _ClosestPoint(torch.autograd.Function):
             gv = torch.zeros_like(v)
         _C.check(_C.lib().tuch_closest_point_bwd(ctx.model._handle, _C.ptr(v), _C.ptr(pts), _C.ptr(face), _C.ptr(bary),
                                                  _C.ptr(g), b, q, _C.ptr(gp), _C.ptr(fixed), _C.ptr(gv), _C.stream()))
-        return gv, gp, None, None, None
+        return (gv, gp) + extra
 
 
 SCAN_RHO = {'squared': 0, 'distance': 1, 'gmof': 2}
@@ -1543,7 +1583,8 @@ class _ScanFit(torch.autograd.Function):
     unless the upstream gradient is the cached unit seed of ops.backward_scalar)."""
 
     @staticmethod
-    def forward(ctx, verts, transl, points, model: ContactModel, counts, weights, hint, rho, sigma, face):
+    def forward(ctx, verts, transl, points, model: ContactModel, counts, weights, hint, rho, sigma, face, normals=None,
+                cos=None):
         v, tr, pts = _f32(verts), _f32(transl), _f32(points)
         b, q, _ = pts.shape
         dev = pts.device
@@ -1555,12 +1596,22 @@ class _ScanFit(torch.autograd.Function):
         gv = torch.empty_like(v)
         gt = torch.empty(b, 3, dtype=torch.float32, device=dev)
         gp = torch.empty_like(pts) if ctx.needs_input_grad[2] else None
-        nbytes = L.tuch_scan_fit_workspace_bytes(model._handle, b, q)
-        ws = _workspace(nbytes, dev)
-        _C.check(L.tuch_scan_fit_terms(model._handle, _C.ptr(v), _C.ptr(tr), _C.ptr(pts), _C.ptr(counts), _C.ptr(weights),
-                                       _C.ptr(hint), b, q, rho, sigma, _C.ptr(d2), _C.ptr(face), _C.ptr(bary),
-                                       _C.ptr(_ticket(dev)), _C.ptr(per_body), _C.ptr(out), _C.ptr(gv), _C.ptr(gt), _C.ptr(gp),
-                                       _C.ptr(ws), nbytes, _C.stream()))
+        if normals is not None:
+            nbytes = L.tuch_scan_fit_oriented_workspace_bytes(model._handle, b, q)
+            ws = _workspace(nbytes, dev)
+            _C.check(L.tuch_scan_fit_terms_oriented(model._handle, _C.ptr(v), _C.ptr(tr), _C.ptr(pts), _C.ptr(normals), cos,
+                                                    _C.ptr(counts), _C.ptr(weights), _C.ptr(hint), b, q, rho, sigma, _C.ptr(d2),
+                                                    _C.ptr(face), _C.ptr(bary), _C.ptr(_ticket(dev)), _C.ptr(per_body),
+                                                    _C.ptr(out), _C.ptr(gv), _C.ptr(gt), _C.ptr(gp), _C.ptr(ws), nbytes,
+                                                    _C.stream()))
+        else:
+            nbytes = L.tuch_scan_fit_workspace_bytes(model._handle, b, q)
+            ws = _workspace(nbytes, dev)
+            _C.check(L.tuch_scan_fit_terms(model._handle, _C.ptr(v), _C.ptr(tr), _C.ptr(pts), _C.ptr(counts), _C.ptr(weights),
+                                           _C.ptr(hint), b, q, rho, sigma, _C.ptr(d2), _C.ptr(face), _C.ptr(bary),
+                                           _C.ptr(_ticket(dev)), _C.ptr(per_body), _C.ptr(out), _C.ptr(gv), _C.ptr(gt),
+                                           _C.ptr(gp), _C.ptr(ws), nbytes, _C.stream()))
+        ctx.num_inputs = 10 if normals is None else 12
         ctx.save_for_backward(gv, gt, gp)
         ctx.in_dtypes = (verts.dtype, transl.dtype, points.dtype)
         ctx.mark_non_differentiable(per_body, d2, bary)
@@ -1571,17 +1622,17 @@ class _ScanFit(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, g, *_others):
         if g is None:
-            return (None,) * 10
+            return (None,) * ctx.num_inputs
         gv, gt, gp = ctx.saved_tensors
         if not backward_pass.is_unit_seed(g):
             g = g.reshape(()).to(torch.float32)
             gv, gt, gp = gv * g, gt * g, (gp * g if gp is not None else None)
         dv, dt, dp = ctx.in_dtypes
-        return (gv.to(dv), gt.to(dt), gp.to(dp) if gp is not None else None) + (None,) * 7
+        return (gv.to(dv), gt.to(dt), gp.to(dp) if gp is not None else None) + (None,) * (ctx.num_inputs - 3)
 
 
 def scan_fit(model: ContactModel, verts, transl, points, counts=None, weights=None, hint=None, rho='distance', sigma=None,
-             face_out=None):
+             face_out=None, normals=None, max_angle=None):
     """Point-to-surface data term of a fit to unregistered points: ``(total, per_body, ClosestPoint)``.  The queries are
     ``points[b,q] - transl[b]`` against ``model``'s mesh posed by ``verts[b]``; the ClosestPoint has the bits of
     ``model.closest_point(verts, points - transl[:, None], counts, hint)``.  per_body[b] = sum_q w_q rho(d2_q) / sum_q w_q
@@ -1592,7 +1643,11 @@ def scan_fit(model: ContactModel, verts, transl, points, counts=None, weights=No
     transl and points with the weights of the nearest point held fixed; the sums into the vertex rows are 64-bit
     fixed-point under ``deterministic()`` and float atomics otherwise, every per-body sum is fixed-order in both modes.
     hint [B,Q] int32 as in ``closest_point``; face_out: a contiguous int32 [B,Q] tensor to receive the faces -- it may be
-    the hint tensor itself (a loop's memory of its last answer).  There is no host fallback."""
+    the hint tensor itself (a loop's memory of its last answer).
+    normals [B,Q,3] with max_angle in degrees, in (0, 90], as in ``closest_point``: the search is the normal-compatible
+    one (tuch_scan_fit_terms_oriented); normals are not translated and get no gradient.  A real point without an
+    admissible face (face = -1) adds 0 to the loss and to every gradient and keeps its weight in the normaliser.  Both or
+    neither must be given; with neither the call is the plain one.  There is no host fallback."""
     if rho not in SCAN_RHO:
         raise ValueError('scan_fit: rho must be one of %s, got %r' % (sorted(SCAN_RHO), rho))
     if rho == 'gmof' and not (sigma is not None and float(sigma) > 0.0):
@@ -1607,19 +1662,21 @@ def scan_fit(model: ContactModel, verts, transl, points, counts=None, weights=No
         raise ValueError('scan_fit: transl has shape %s, expected %s' % (tuple(transl.shape), (b, 3)))
     if b == 0 or q == 0:
         raise ValueError('scan_fit: empty input %s' % (tuple(points.shape),))
+    cos = _max_angle_cos(normals, max_angle, points, 'scan_fit')
     if weights is not None and tuple(weights.shape) != (b, q):
         raise ValueError('scan_fit: weights must be [%d,%d], got %s' % (b, q, tuple(weights.shape)))
     if counts is not None and tuple(counts.shape) != (b,):
         raise ValueError('scan_fit: counts must be [%d], got %s' % (b, tuple(counts.shape)))
-    _need_hip('scan_fit', verts, transl, points, weights, counts, hint, face_out)
+    _need_hip('scan_fit', verts, transl, points, weights, counts, hint, face_out, normals)
     if face_out is not None and (tuple(face_out.shape) != (b, q) or face_out.dtype != torch.int32 or not face_out.is_contiguous()):
         raise ValueError('scan_fit: face_out must be a contiguous int32 [%d,%d] tensor' % (b, q))
     counts = None if counts is None else counts.to(torch.int32).contiguous()
     weights = None if weights is None else _f32(weights.detach())
     hint = _hint_of(hint, points, 'scan_fit')
     face = face_out if face_out is not None else torch.empty(b, q, dtype=torch.int32, device=points.device)
+    extra = () if cos is None else (_f32(normals.detach()), cos)
     total, per_body, d2, bary = _ScanFit.apply(verts, transl, points, model, counts, weights, hint, SCAN_RHO[rho],
-                                               float(sigma) if sigma is not None else 0.0, face)
+                                               float(sigma) if sigma is not None else 0.0, face, *extra)
     return total, per_body, ClosestPoint(d2, face, bary)
 
 
