@@ -547,6 +547,46 @@ int tuch_point_cloud_nearest(const void* workspace, size_t workspace_bytes, cons
                              const int32_t* query_counts /* [B] or NULL */, const int32_t* hint /* [B,N] or NULL */,
                              float max_distance, int B, int Q, int N, float* d2 /* [B,N] */, int32_t* index /* [B,N] */,
                              void* stream);
+/* k nearest points, and PCA normals over them.  The rule above, verbatim -- the valid points, q = x + shift[b], THE
+ * squared distance, the packed key d2 bits << 32 | index, max_distance, query_counts -- for the k (1 .. 32; anything
+ * else is an argument error) smallest keys of a query, in ascending order: index [B,N,k], d2 [B,N,k].  With fewer than
+ * k admissible points (finite d2, within tau) the tail is -1 / +inf; a non-finite query, an empty cloud or an entry at
+ * or beyond query_counts[b] gives all -1 / +inf.  A point that coincides with the query is an ordinary neighbour with
+ * d2 = 0: querying a cloud with its own points returns each point itself first, or the smallest index among its
+ * duplicates.  The outputs equal a sorted float32 brute-force sweep bit for bit, alone or in a batch, for any order of
+ * queries or points, any resolution, eager or replayed.  One launch, no workspace beyond the cloud's; capturable.
+ *   Neighbourhood statistics: one fixed float32 sequence, every product, sum and difference rounded on its own.  With
+ * the n <= k neighbours found, in key order, s_j read from `points` (pass the array the cloud was built from):
+ *   d_j = s_j - q per component;  m = (...((d_1 + d_2) + d_3)... + d_n) / (float)n;  e_j = d_j - m;
+ *   C_ab = ((0 + e_1,a e_1,b) + e_2,a e_2,b) + ... for ab = xx, xy, xz, yy, yz, zz  (cov [B,N,6] or NULL, in that order).
+ * C has the same bits whatever the grid, the batch or the order of the points; centring on the query keeps the sums
+ * free of the cloud's distance from the origin.
+ *   normals [B,N,3]: the unit eigenvector of C's smallest eigenvalue lambda0 <= lambda1 <= lambda2, by cyclic Jacobi in
+ * float32 with a fixed number of sweeps.  With T = trace C + n |m|^2 = sum_j |d_j|^2 and E = (n + 256) 2^-24 T (derived
+ * in the source file: it bounds the error of C and of the solver against the float64 scatter matrix of the same
+ * neighbours; T = trace C for a query at the centroid and T <= (n + 1) trace C for a query that is one of its own
+ * neighbours), the sine of the normal's angle error is at most 2 E / (lambda1 - lambda0).  The row is ZERO when n < 3
+ * or 2 E >= lambda1 - lambda0 --
+ * collinear, coincident or isotropic neighbours, where the bound says nothing; also when T is not finite or below
+ * 1e-30, or the solver's residual exceeds 2^-24 T -- which is what tuch_closest_point_oriented treats as unconstrained.
+ *   variation [B,N] = lambda0 / (lambda0 + lambda1 + lambda2), within 2 E / trace C + 2^-23 of the float64 value; 0 where
+ * the normal is zero.  count [B,N] = n.
+ *   Sign: first canonical -- the component of the largest magnitude is positive, the first among equals --; then with a
+ * viewpoint c (layout 1: [B,3], layout 2: [B,N,3]; the sensor's position in the frame of the queries q) t = c - q,
+ * s = (n_x t_x + n_y t_y) + n_z t_z, and the normal is negated when s < 0, kept when s >= 0 or s is not finite.  A
+ * query's normal has the same bits alone or in any batch, order or resolution.  weights decide validity only; the PCA
+ * is unweighted.  No gradients: the cloud is data. */
+int tuch_point_cloud_knn(const void* workspace, size_t workspace_bytes, const float* points /* [B,Q,3] */,
+                         const int32_t* counts /* [B] or NULL */, const float* weights /* [B,Q] or NULL */,
+                         const float* queries /* [B,N,3] */, const float* shift /* [B,3] or NULL */,
+                         const int32_t* query_counts /* [B] or NULL */, float max_distance, int B, int Q, int N, int k,
+                         float* d2 /* [B,N,k] */, int32_t* index /* [B,N,k] */, void* stream);
+int tuch_point_cloud_normals(const void* workspace, size_t workspace_bytes, const float* points, const int32_t* counts,
+                             const float* weights, const float* queries, const float* shift, const int32_t* query_counts,
+                             float max_distance, int B, int Q, int N, int k, const float* viewpoint,
+                             int viewpoint_layout /* 0 none, 1 [B,3], 2 [B,N,3] */, float* normals /* [B,N,3] */,
+                             float* variation /* [B,N] */, int32_t* count /* [B,N] */, float* cov /* [B,N,6] or NULL */,
+                             void* stream);
 /* The term: the query for q = verts[b,v] + transl[b] (d2, index [B,V] as tuch_point_cloud_nearest gives them; a vertex
  * of weight 0 is not computed from and gets -1 / +inf), vertex weights w NULL (ones; layout 0), [V] (layout 1) or [B,V]
  * (layout 2), rho / sigma as tuch_scan_fit_terms, and

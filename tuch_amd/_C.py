@@ -132,6 +132,10 @@ _SIGNATURES = {
     'tuch_point_cloud_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
     'tuch_point_cloud_build': (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_void_p, c_size_t, c_void_p]),
     'tuch_point_cloud_nearest': (c_int, [c_void_p, c_size_t] + [c_void_p] * 7 + [c_float, c_int, c_int, c_int] + [c_void_p] * 3),
+    'tuch_point_cloud_knn': (c_int, [c_void_p, c_size_t] + [c_void_p] * 6 + [c_float, c_int, c_int, c_int, c_int]
+                             + [c_void_p] * 3),
+    'tuch_point_cloud_normals': (c_int, [c_void_p, c_size_t] + [c_void_p] * 6 + [c_float, c_int, c_int, c_int, c_int, c_void_p,
+                                         c_int] + [c_void_p] * 5),
     'tuch_point_cloud_fit_scratch_bytes': (c_size_t, [c_int, c_int]),
     'tuch_point_cloud_fit_terms': (c_int, [c_void_p, c_size_t] + [c_void_p] * 6 + [c_float, c_int, c_int, c_int, c_void_p, c_int,
                                            c_int, c_float, c_float] + [c_void_p] * 8 + [c_size_t, c_void_p]),

@@ -56,6 +56,36 @@
 // sweep computes too, so it cannot undercut the sweep's minimum; it only shortens the walk.  Anything else takes the
 // unhinted path.  hint may alias the index output: a lane reads its own entry before it writes it.
 //
+// k nearest points and normals (tuch_point_cloud_knn / _normals; pc_knn_search, pc_knn_kernel, pc_normals_kernel).  The
+// rule above, verbatim, for the k (1 .. 32) smallest keys of a query in ascending order: index [B,N,k], d2 [B,N,k]; with
+// fewer than k admissible points (finite d2, within tau) the tail is -1 / +inf; a non-finite query, an empty cloud or
+// an entry beyond query_counts gives all -1 / +inf.  A point that coincides with the query is an ordinary neighbour with
+// d2 = 0.  The outputs equal a sorted float32 brute-force sweep bit for bit, alone or in a batch, for any order of
+// queries or points, any resolution, eager or replayed.
+//   pc_knn_search walks the same Chebyshev rings with the same gap bounds and the same 2^-20 margin as pc_search.  The
+// pruning bound is the lane's k-th key so far; while its list is not full the bound is (limit, -1).  The derivation
+// above carries over unchanged: a cell, a block, a row, a slab or the rest of the grid is skipped only when its lower
+// bound exceeds the bound's d2, so no point whose key is below the bound is ever skipped, and the k smallest keys are
+// found whatever was visited in whatever order.  With no tau the ring test cannot end the walk before the list is full
+// (limit is then the largest finite float): the walk ends after a ring only once the list is full (or nothing beyond
+// the ring is within tau), or when the grid is exhausted.
+//   The list needs dynamic indexing, so it lives in LDS, not in registers: [k][lanes] 64-bit keys (PcList).  It fills in
+// arrival order; once full it is a binary max-heap whose root, the bound, is kept in a register.  An accepted candidate
+// takes the root's place and sifts down (at most 2 log2 k reads; accepts become rare once the list has warmed up); after
+// the walk the lane sorts its keys in place (heap sort) and writes them.  The first form kept the list unsorted with the
+// slot of its maximum and rescanned all k slots after every accept; the heap gives the same bits and measured 2.1 x faster
+// at k = 32 and 100 000 points (1.4 x at 6 890), 1.1 - 1.4 x at k = 16 and 3 - 10 % slower at k = 8 (DESIGN.md
+// section 3).  One launch, no atomics, no cross-lane traffic, no workspace beyond the cloud's: capturable.
+//   Neighbourhood statistics, one fixed float32 sequence under this file's contract(off), n <= k neighbours in key order,
+// re-read from the caller's `points` by index (clamped): d_j = s_j - q per component; m = (...((d_1 + d_2) + d_3)... +
+// d_n) / (float)n; e_j = d_j - m; C_xx, C_xy, C_xz, C_yy, C_yz, C_zz each 0 + e_1,a e_1,b + e_2,a e_2,b + ... left to
+// right.  The list is sorted by key, so C has the same bits whatever the grid, the batch or the filing order.  The
+// normal is the unit eigenvector of C's smallest eigenvalue (Jacobi, a fixed number of sweeps: above pc_rotate, with
+// the derivation of the error bound E and of the zero rows); variation = lambda0 / (lambda0 + lambda1 + lambda2), 0
+// where the normal is zero; count = n.  Sign: first canonical (the component of the largest magnitude positive, the
+// first among equals); then, with a viewpoint c, t = c - q, s = (n_x t_x + n_y t_y) + n_z t_z, negated when s < 0 (kept
+// when s >= 0 or not finite).  Weights decide validity only; the PCA is unweighted.
+//
 // The term (pc_fit_kernel; tuch_point_cloud_fit_terms): the query for q = verts[b,v] + transl[b], then per vertex
 // g_v = scale w_v rho'(d2_v) / sum w and grad_verts[b,v] = 2 g_v (q - s) written by the lane that owns the row (no
 // atomics); the per-body loss, the normaliser and grad_transl = sum_v grad_verts[b,v] cross to the workgroup that arrives
@@ -452,6 +482,307 @@ __global__ __launch_bounds__(kBlock) void pc_nearest_kernel(PcTables w, const fl
     index_out[o] = won ? (int32_t)(uint32_t)best : -1;
 }
 
+// ------------------------------------------------------------------------------------------- k nearest points, normals
+// A lane's list: k keys in LDS, slot j of lane t at list[j * lanes + t] (the lanes of a wavefront are contiguous, so
+// every ds_read_b64 / ds_write_b64 is free of bank conflicts, whatever slot each lane is at: a row of slots is a multiple
+// of 256 bytes).  While the walk runs `n` slots are filled, in arrival order until n == k; from then on the k slots are
+// a binary max-heap (children of slot i at 2 i + 1 and 2 i + 2) whose root is `bound`, the lane's k-th key so far.
+// Until then bound is (limit bits, -1), above every admissible key.
+struct PcList {
+    unsigned long long* at;      // the lane's slot 0
+    int lanes, k, n;
+    unsigned long long bound;
+};
+
+// v into slot i of the max-heap of the first n slots: the larger child moves up until v is no smaller than both
+static __device__ __forceinline__ void pc_list_sift(unsigned long long* at, int lanes, int n, int i, unsigned long long v)
+{
+    for (;;) {
+        int c = 2 * i + 1;
+        if (c >= n) break;
+        unsigned long long a = at[(size_t)c * lanes];
+        if (c + 1 < n) {
+            const unsigned long long b = at[(size_t)(c + 1) * lanes];
+            if (b > a) { a = b; ++c; }
+        }
+        if (a <= v) break;
+        at[(size_t)i * lanes] = a;
+        i = c;
+    }
+    at[(size_t)i * lanes] = v;
+}
+
+static __device__ __forceinline__ void pc_list_offer(PcList& l, float d2, float limit, unsigned long long key)
+{
+    if (!(d2 <= limit) || key >= l.bound) return;
+    if (l.n < l.k) {
+        l.at[(size_t)l.n * l.lanes] = key;
+        if (++l.n < l.k) return;                               // not full: the bound stays at limit
+        for (int i = l.k / 2 - 1; i >= 0; --i) pc_list_sift(l.at, l.lanes, l.k, i, l.at[(size_t)i * l.lanes]);
+    } else {
+        pc_list_sift(l.at, l.lanes, l.k, 0, key);               // in place of the maximum
+    }
+    l.bound = l.at[0];
+}
+
+// the n keys of the list in ascending order, in place (heap sort: the root goes behind the shrinking heap)
+static __device__ __forceinline__ void pc_list_sort(PcList& l)
+{
+    if (l.n < l.k)
+        for (int i = l.n / 2 - 1; i >= 0; --i) pc_list_sift(l.at, l.lanes, l.n, i, l.at[(size_t)i * l.lanes]);
+    for (int end = l.n - 1; end > 0; --end) {
+        const unsigned long long v = l.at[(size_t)end * l.lanes];
+        l.at[(size_t)end * l.lanes] = l.at[0];
+        pc_list_sift(l.at, l.lanes, end, 0, v);
+    }
+}
+
+// pc_search with a list in place of the one key: the same rings, gaps, slack and 2^-20 margin, the same tests in the
+// same places, against l.bound.  Returns with the n <= k smallest admissible keys in the list, unsorted.
+static __device__ void pc_knn_search(const PcTables& w, int b, int Q, float qx, float qy, float qz, float limit, PcList& l)
+{
+    const PcGrid g = pc_grid(w.head, b);
+    const int n = pc_clampi(g.n, 0, Q);
+    if (n == 0) return;
+    const long long fine = (long long)g.res * g.res * g.res;
+    const int cres = (g.res + 3) >> 2;
+    const long long base = (long long)b * (fine + (long long)cres * cres * cres);
+    const float4* pts = w.sorted + (size_t)b * Q;
+    const float tx = pc_t(qx, g.ox, g.inv), ty = pc_t(qy, g.oy, g.inv), tz = pc_t(qz, g.oz, g.inv);
+    const float tmax = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(tx), __builtin_fabsf(ty)), __builtin_fabsf(tz));
+    const float slack = pc_mul(kPcMargin, pc_add(tmax, (float)(g.res + 2)));
+    const int hx = pc_axis_cell(tx, g.dx) >> 2, hy = pc_axis_cell(ty, g.dy) >> 2, hz = pc_axis_cell(tz, g.dz) >> 2;
+    int rmax = hx > g.cdx - 1 - hx ? hx : g.cdx - 1 - hx;
+    rmax = rmax > hy ? rmax : hy;
+    rmax = rmax > g.cdy - 1 - hy ? rmax : g.cdy - 1 - hy;
+    rmax = rmax > hz ? rmax : hz;
+    rmax = rmax > g.cdz - 1 - hz ? rmax : g.cdz - 1 - hz;
+    for (int r = 0; r <= rmax; ++r) {
+        if (r > 1 && pc_out(pc_sq(g.cell, pc_gap(0.0f, 4 * (r - 1), 4 * (r - 1) + 1, slack)), l.bound)) break;
+        const int z0 = hz - r < 0 ? 0 : hz - r, z1 = hz + r > g.cdz - 1 ? g.cdz - 1 : hz + r;
+        const int y0 = hy - r < 0 ? 0 : hy - r, y1 = hy + r > g.cdy - 1 ? g.cdy - 1 : hy + r;
+        const int x0 = hx - r < 0 ? 0 : hx - r, x1 = hx + r > g.cdx - 1 ? g.cdx - 1 : hx + r;
+        for (int bz = z0; bz <= z1; ++bz) {
+            const float lz = pc_sq(g.cell, pc_gap(tz, 4 * bz, 4 * bz + 4, slack));
+            if (pc_out(lz, l.bound)) continue;
+            const bool zface = bz - hz == r || hz - bz == r;
+            for (int by = y0; by <= y1; ++by) {
+                const float lyz = pc_add(pc_sq(g.cell, pc_gap(ty, 4 * by, 4 * by + 4, slack)), lz);
+                if (pc_out(lyz, l.bound)) continue;
+                const bool face = zface || by - hy == r || hy - by == r;
+                const int step = face ? 1 : 2 * r;
+                for (int bx = face ? x0 : (hx - r >= 0 ? hx - r : hx + r); bx <= x1; bx += step) {
+                    if (pc_table(w, base + fine + ((long long)bz * g.cdy + by) * g.cdx + bx) <= 0) continue;
+                    if (pc_out(pc_add(pc_sq(g.cell, pc_gap(tx, 4 * bx, 4 * bx + 4, slack)), lyz), l.bound)) continue;
+                    const int cz1 = 4 * bz + 4 < g.dz ? 4 * bz + 4 : g.dz, cy1 = 4 * by + 4 < g.dy ? 4 * by + 4 : g.dy,
+                              cx1 = 4 * bx + 4 < g.dx ? 4 * bx + 4 : g.dx;
+                    for (int cz = 4 * bz; cz < cz1; ++cz) {
+                        const float mz = pc_sq(g.cell, pc_gap(tz, cz, cz + 1, slack));
+                        if (pc_out(mz, l.bound)) continue;
+                        for (int cy = 4 * by; cy < cy1; ++cy) {
+                            const float myz = pc_add(pc_sq(g.cell, pc_gap(ty, cy, cy + 1, slack)), mz);
+                            if (pc_out(myz, l.bound)) continue;
+                            const long long row = base + ((long long)cz * g.dy + cy) * g.dx;
+                            for (int cx = 4 * bx; cx < cx1; ++cx) {
+                                const long long c = row + cx;
+                                const int end = pc_clampi(pc_table(w, c), 0, n);
+                                const int begin = c == base ? 0 : pc_clampi(pc_table(w, c - 1), 0, n);
+                                if (begin >= end) continue;
+                                if (pc_out(pc_add(pc_sq(g.cell, pc_gap(tx, cx, cx + 1, slack)), myz), l.bound)) continue;
+                                for (int p = begin; p < end; ++p) {
+                                    const float4 s = pts[p];
+                                    const float d2 = pc_d2(qx, qy, qz, s.x, s.y, s.z);
+                                    pc_list_offer(l, d2, limit,
+                                                  ((unsigned long long)__float_as_uint(d2) << 32) | (uint32_t)__float_as_int(s.w));
+                                }
+                            }
+                        }
+                    }
+                }
+            }
+        }
+    }
+}
+
+// The whole k-nearest query of lane `lane` of the workgroup for entry i of body b: the query, the search, the sort.
+// Returns n; the lane's slots 0 .. n - 1 then hold its keys in ascending order.  (qx, qy, qz) is the query where n > 0.
+static __device__ __forceinline__ int pc_knn_lane(const PcTables& w, const float* __restrict__ queries,
+                                                  const float* __restrict__ shift, const int32_t* __restrict__ query_counts,
+                                                  float limit, int b, int Q, int N, int i, int k, unsigned long long* list,
+                                                  int lanes, int lane, float& qx, float& qy, float& qz)
+{
+    int count = N;
+    if (query_counts) count = pc_clampi(query_counts[b], 0, N);
+    if (i >= count) return 0;
+    const size_t o = (size_t)b * N + i;
+    qx = queries[o * 3]; qy = queries[o * 3 + 1]; qz = queries[o * 3 + 2];
+    if (shift) {
+        qx = pc_add(qx, shift[3 * b]); qy = pc_add(qy, shift[3 * b + 1]); qz = pc_add(qz, shift[3 * b + 2]);
+    }
+    if (!pc_finite3(qx, qy, qz)) return 0;
+    PcList l;
+    l.at = list + lane;
+    l.lanes = lanes; l.k = k; l.n = 0;
+    l.bound = ((unsigned long long)__float_as_uint(limit) << 32) | 0xffffffffull;
+    pc_knn_search(w, b, Q, qx, qy, qz, limit, l);
+    pc_list_sort(l);
+    return l.n;
+}
+
+// blockDim.x lanes (a multiple of 64), k * blockDim.x keys of dynamic LDS
+__global__ __launch_bounds__(kBlock) void pc_knn_kernel(PcTables w, const float* __restrict__ queries,
+                                                       const float* __restrict__ shift,
+                                                       const int32_t* __restrict__ query_counts, float limit, int Q, int N,
+                                                       int k, float* __restrict__ d2_out, int32_t* __restrict__ index_out)
+{
+    extern __shared__ unsigned long long pc_keys[];
+    const int lanes = blockDim.x, lane = threadIdx.x;
+    const int b = blockIdx.y, i = blockIdx.x * lanes + lane;
+    if (i >= N) return;
+    float qx, qy, qz;
+    const int n = pc_knn_lane(w, queries, shift, query_counts, limit, b, Q, N, i, k, pc_keys, lanes, lane, qx, qy, qz);
+    const size_t o = ((size_t)b * N + i) * k;
+    for (int j = 0; j < k; ++j) {
+        const unsigned long long key = j < n ? pc_keys[(size_t)j * lanes + lane] : kPcNoKey;
+        d2_out[o + j] = j < n ? __uint_as_float((uint32_t)(key >> 32)) : __builtin_inff();
+        index_out[o + j] = j < n ? (int32_t)(uint32_t)key : -1;
+    }
+}
+
+// The normal of a neighbourhood.  C is the float32 scatter matrix of the rule, T = trace C + n |m|^2 = sum_j |d_j|^2.
+//
+// The error bound E = c u T, u = 2^-24, c = n + kPcSolverC, against the float64 scatter matrix of the same neighbours
+// (the SAME float32 points and query, every operation exact).  Write d, m, e, C for the exact values.
+//   The differences: fl(d_j) = d_j + a_j, |a_j| <= u |d_j| per component.  The mean: fl(m) = m + h with
+// |h| <= (n + 1) u mean|d| (n - 1 additions, the a_j, one division).  The centred rows: fl(e_j) = e_j + a_j - h + r_j,
+// |r_j| <= u |e_j|.  In sum_j fl(e_j) fl(e_j)^T the first-order share of h is -(sum_j e_j) h^T - h (sum_j e_j)^T = 0
+// EXACTLY, because the e_j sum to zero: the mean's error enters only as n h h^T, of norm <= (n + 1)^2 u^2 T < 0.001 u T
+// for n <= 32.  The first-order share of a and r is sum_j e_j (a_j + r_j)^T + its transpose, of Frobenius norm
+//     <= 2 u sum_j |e_j| (|d_j| + |e_j|)  <=  2 u (sqrt(trace C  T) + trace C)  <=  4 u T      (Cauchy-Schwarz, trace C <= T).
+// Each entry's sum: one rounding per product and n - 1 per left-to-right sum, n u sum_j |e_j,a e_j,b| <= n u sqrt(C_aa C_bb),
+// a matrix of Frobenius norm n u trace C <= n u T.  Together || fl(C) - C ||_F <= (n + 4.01) u T.
+//   The solver: kPcSweeps cyclic sweeps (0,1), (0,2), (1,2) of Jacobi rotations, t = sgn(theta) / (|theta| + sqrt(theta^2 + 1)),
+// c = 1 / sqrt(t^2 + 1), s = t c, no branch and no trigonometric call.  A computed rotation is the exact similarity of
+// a matrix 14 u ||A||_F away (t with 5 u relative error, which leaves 5 u |apq| where the update writes 0 and as much on
+// the two diagonal entries; c^2 + s^2 = 1 within 5 u; three operations per updated entry), ||A||_F <= trace C (1 + O(u))
+// throughout: 3 kPcSweeps 14 u = 210 u T for the 15 rotations.  What the
+// last sweep leaves off the diagonal is a perturbation of its own: rows whose residual sqrt(2 (a01^2 + a02^2 + a12^2))
+// exceeds u T are given up (a zero normal) -- quadratic convergence leaves none on any input tried -- so it adds 1 u T.
+// The vector itself: 15 updates of V at 3 u each and the normalisation, < 50 u of angle, not amplified by any gap; it is
+// counted as 25 u T in E because the angle bound below is 2 E / gap >= 2 E / T.  210 + 4.01 + 1 + 25 < kPcSolverC = 256
+// (the rest covers T's own rounding and second-order terms).
+//   By Weyl every eigenvalue is within E of the exact one; by Davis-Kahan (in the form sin <= 2 ||D|| / gap, the gap that
+// of the EXACT matrix) the sine of the angle between the computed and the exact normal is at most 2 E / (lambda1 -
+// lambda0).  The normal is a zero row where that says nothing: n < 3, 2 E >= lambda1 - lambda0 as computed, a
+// residual above u T, or T below kPcNormal (products without relative accuracy) or not finite.  variation = lambda0 /
+// (lambda0 + lambda1 + lambda2) is then within 2 E / trace C + 2 u of the float64 value (three eigenvalue errors in the
+// denominator weighted by lambda0 / trace <= 1 / 3, one in the numerator, the sum's and the division's roundings).
+constexpr int kPcSweeps = 5;
+constexpr float kPcSolverC = 256.0f;
+constexpr float kPcU = 5.9604644775390625e-8f;          // u = 2^-24
+
+// One Jacobi rotation in the (p, q) plane; r is the third index.  arp = A[r][p], arq = A[r][q]; vp, vq: columns p, q of V.
+static __device__ __forceinline__ void pc_rotate(float& app, float& aqq, float& apq, float& arp, float& arq, float (&vp)[3],
+                                                 float (&vq)[3])
+{
+    const float theta = (aqq - app) / (2.0f * apq);
+    float t = __builtin_copysignf(1.0f, theta) / (__builtin_fabsf(theta) + __builtin_sqrtf(theta * theta + 1.0f));
+    t = (apq != 0.0f && __builtin_isfinite(t)) ? t : 0.0f;    // (theta overflowing: the rotation is the identity)
+    const float c = 1.0f / __builtin_sqrtf(t * t + 1.0f), s = t * c;
+    app = app - t * apq;
+    aqq = aqq + t * apq;
+    apq = t != 0.0f ? 0.0f : apq;
+    const float np = c * arp - s * arq, nq = s * arp + c * arq;
+    arp = np; arq = nq;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const float a = c * vp[r] - s * vq[r], d = s * vp[r] + c * vq[r];
+        vp[r] = a; vq[r] = d;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void pc_normals_kernel(PcTables w, const float* __restrict__ points,
+                                                           const float* __restrict__ queries,
+                                                           const float* __restrict__ shift,
+                                                           const int32_t* __restrict__ query_counts, float limit, int Q, int N,
+                                                           int k, const float* __restrict__ viewpoint, int view_layout,
+                                                           float* __restrict__ normal_out, float* __restrict__ variation_out,
+                                                           int32_t* __restrict__ count_out, float* __restrict__ cov_out)
+{
+    extern __shared__ unsigned long long pc_keys[];
+    const int lanes = blockDim.x, lane = threadIdx.x;
+    const int b = blockIdx.y, i = blockIdx.x * lanes + lane;
+    if (i >= N) return;
+    float qx = 0.0f, qy = 0.0f, qz = 0.0f;
+    const int n = pc_knn_lane(w, queries, shift, query_counts, limit, b, Q, N, i, k, pc_keys, lanes, lane, qx, qy, qz);
+    const float* body = points + (size_t)b * Q * 3;
+    // the mean of d_j = s_j - q, in key order
+    float mx = 0.0f, my = 0.0f, mz = 0.0f;
+    for (int j = 0; j < n; ++j) {
+        const float* s = body + (size_t)pc_clampi((int)(uint32_t)pc_keys[(size_t)j * lanes + lane], 0, Q - 1) * 3;
+        const float dx = pc_sub(s[0], qx), dy = pc_sub(s[1], qy), dz = pc_sub(s[2], qz);
+        mx = j == 0 ? dx : pc_add(mx, dx); my = j == 0 ? dy : pc_add(my, dy); mz = j == 0 ? dz : pc_add(mz, dz);
+    }
+    if (n > 0) { mx = mx / (float)n; my = my / (float)n; mz = mz / (float)n; }
+    float cxx = 0.0f, cxy = 0.0f, cxz = 0.0f, cyy = 0.0f, cyz = 0.0f, czz = 0.0f;
+    for (int j = 0; j < n; ++j) {
+        const float* s = body + (size_t)pc_clampi((int)(uint32_t)pc_keys[(size_t)j * lanes + lane], 0, Q - 1) * 3;
+        const float ex = pc_sub(pc_sub(s[0], qx), mx), ey = pc_sub(pc_sub(s[1], qy), my), ez = pc_sub(pc_sub(s[2], qz), mz);
+        cxx = pc_add(cxx, pc_mul(ex, ex)); cxy = pc_add(cxy, pc_mul(ex, ey)); cxz = pc_add(cxz, pc_mul(ex, ez));
+        cyy = pc_add(cyy, pc_mul(ey, ey)); cyz = pc_add(cyz, pc_mul(ey, ez)); czz = pc_add(czz, pc_mul(ez, ez));
+    }
+    const size_t o = (size_t)b * N + i;
+    if (cov_out) {
+        float* c = cov_out + o * 6;
+        c[0] = cxx; c[1] = cxy; c[2] = cxz; c[3] = cyy; c[4] = cyz; c[5] = czz;
+    }
+    const float total = pc_add(pc_add(pc_add(cxx, cyy), czz),
+                               pc_mul((float)n, pc_add(pc_add(pc_mul(mx, mx), pc_mul(my, my)), pc_mul(mz, mz))));
+    const float err = pc_mul(pc_mul((float)n + kPcSolverC, kPcU), total);          // E
+    float a00 = cxx, a01 = cxy, a02 = cxz, a11 = cyy, a12 = cyz, a22 = czz;
+    float v0[3] = {1.0f, 0.0f, 0.0f}, v1[3] = {0.0f, 1.0f, 0.0f}, v2[3] = {0.0f, 0.0f, 1.0f};
+#pragma unroll
+    for (int sweep = 0; sweep < kPcSweeps; ++sweep) {
+        pc_rotate(a00, a11, a01, a02, a12, v0, v1);
+        pc_rotate(a00, a22, a02, a01, a12, v0, v2);
+        pc_rotate(a11, a22, a12, a01, a02, v1, v2);
+    }
+    const float residual = __builtin_sqrtf(2.0f * ((a01 * a01 + a02 * a02) + a12 * a12));
+    // the smallest eigenvalue's column, the two smallest eigenvalues
+    const bool first = a00 <= a11 && a00 <= a22, second = !first && a11 <= a22;
+    const float l0 = first ? a00 : (second ? a11 : a22);
+    const float l1 = first ? __builtin_fminf(a11, a22) : (second ? __builtin_fminf(a00, a22) : __builtin_fminf(a00, a11));
+    const float l2 = first ? __builtin_fmaxf(a11, a22) : (second ? __builtin_fmaxf(a00, a22) : __builtin_fmaxf(a00, a11));
+    float nx = first ? v0[0] : (second ? v1[0] : v2[0]), ny = first ? v0[1] : (second ? v1[1] : v2[1]),
+          nz = first ? v0[2] : (second ? v1[2] : v2[2]);
+    const float len = __builtin_sqrtf((nx * nx + ny * ny) + nz * nz);
+    const bool known = n >= 3 && total >= kPcNormal && total <= kPcMaxD2 && 2.0f * err < l1 - l0 &&
+                       residual <= kPcU * total && len > 0.5f;
+    float variation = 0.0f;
+    if (known) {
+        nx = nx / len; ny = ny / len; nz = nz / len;
+        // canonical sign: the component of the largest magnitude is positive, the first among equals
+        const float ax = __builtin_fabsf(nx), ay = __builtin_fabsf(ny), az = __builtin_fabsf(nz);
+        const float lead = (ax >= ay && ax >= az) ? nx : (ay >= az ? ny : nz);
+        bool flip = lead < 0.0f;
+        if (view_layout != 0) {
+            const float* c = viewpoint + (view_layout == 2 ? o : (size_t)b) * 3;
+            const float sx = flip ? -nx : nx, sy = flip ? -ny : ny, sz = flip ? -nz : nz;
+            const float side = pc_add(pc_add(pc_mul(sx, pc_sub(c[0], qx)), pc_mul(sy, pc_sub(c[1], qy))),
+                                      pc_mul(sz, pc_sub(c[2], qz)));
+            if (side < 0.0f) flip = !flip;
+        }
+        if (flip) { nx = -nx; ny = -ny; nz = -nz; }
+        const float low = __builtin_fmaxf(l0, 0.0f);
+        variation = low / ((low + l1) + l2);
+    } else {
+        nx = 0.0f; ny = 0.0f; nz = 0.0f;
+    }
+    normal_out[o * 3] = nx; normal_out[o * 3 + 1] = ny; normal_out[o * 3 + 2] = nz;
+    variation_out[o] = variation;
+    count_out[o] = n;
+}
+
 // ---------------------------------------------------------------------------------------------------------- the term
 #pragma clang fp contract(fast)
 
@@ -697,6 +1028,71 @@ extern "C" int tuch_point_cloud_nearest(const void* workspace, size_t workspace_
                        pc_tables((void*)workspace, workspace_bytes, B, Q), points, counts, weights, queries, shift,
                        query_counts, hint, limit, Q, N, d2, index);
     return tuch_check_launch("tuch_point_cloud_nearest");
+}
+
+namespace {
+
+// Lanes per workgroup of the k-nearest kernels: 256 up to k = 16, 128 beyond, so a workgroup's list (k x lanes x 8
+// bytes) never exceeds 32 KiB and five workgroups fit into a CU's 160 KiB of LDS -- 20 wavefronts at k <= 16, 10 beyond.
+int pc_knn_lanes(int k) { return k > 16 ? kBlock / 2 : kBlock; }
+
+// (called inside the entry point's tuch_ws_scope: the layout, like pc_tables' after it, is the guarded one under the
+// canary option)
+int pc_knn_check(const char* what, const void* workspace, size_t workspace_bytes, int B, int Q, int N, int k)
+{
+    TUCH_REQUIRE(pc_sizes_ok(B, Q, N) && (long long)B * N * k < (1ll << 31), "%s: bad sizes B=%d Q=%d N=%d k=%d", what, B, Q, N,
+                 k);
+    const size_t need = pc_layout(B, Q, 1).total;
+    if (workspace_bytes < need) {
+        tuch_set_error("%s: workspace %zu < %zu bytes", what, workspace_bytes, need);
+        return TUCH_ERR_WORKSPACE;
+    }
+    return TUCH_OK;
+}
+
+}  // namespace
+
+extern "C" int tuch_point_cloud_knn(const void* workspace, size_t workspace_bytes, const float* points, const int32_t* counts,
+                                    const float* weights, const float* queries, const float* shift,
+                                    const int32_t* query_counts, float max_distance, int B, int Q, int N, int k, float* d2,
+                                    int32_t* index, void* stream)
+{
+    TUCH_REQUIRE(workspace && points && queries && d2 && index, "tuch_point_cloud_knn: null pointer");
+    TUCH_REQUIRE(k >= 1 && k <= 32, "tuch_point_cloud_knn: k = %d (1 .. 32)", k);
+    tuch_ws_scope scope(g_pc_canary != 0);                     // alive up to the launch: pc_tables lays the regions out in it
+    const int rc = pc_knn_check("tuch_point_cloud_knn", workspace, workspace_bytes, B, Q, N, k);
+    if (rc != TUCH_OK) return rc;
+    (void)counts; (void)weights;        // (the build filed the valid points; the ABI keeps the triple together)
+    const float limit = max_distance > 0.0f ? fminf(max_distance * max_distance, kPcMaxD2) : kPcMaxD2;
+    const int lanes = pc_knn_lanes(k);
+    hipLaunchKernelGGL(pc_knn_kernel, dim3(ceil_div(N, lanes), B), dim3(lanes), (size_t)k * lanes * sizeof(unsigned long long),
+                       (hipStream_t)stream, pc_tables((void*)workspace, workspace_bytes, B, Q), queries, shift, query_counts,
+                       limit, Q, N, k, d2, index);
+    return tuch_check_launch("tuch_point_cloud_knn");
+}
+
+extern "C" int tuch_point_cloud_normals(const void* workspace, size_t workspace_bytes, const float* points,
+                                        const int32_t* counts, const float* weights, const float* queries, const float* shift,
+                                        const int32_t* query_counts, float max_distance, int B, int Q, int N, int k,
+                                        const float* viewpoint, int viewpoint_layout, float* normals, float* variation,
+                                        int32_t* count, float* cov, void* stream)
+{
+    TUCH_REQUIRE(workspace && points && queries && normals && variation && count, "tuch_point_cloud_normals: null pointer");
+    TUCH_REQUIRE(k >= 1 && k <= 32, "tuch_point_cloud_normals: k = %d (1 .. 32)", k);
+    TUCH_REQUIRE(viewpoint_layout >= 0 && viewpoint_layout <= 2 && (viewpoint_layout == 0 || viewpoint),
+                 "tuch_point_cloud_normals: viewpoint layout %d (0 none, 1 [B,3], 2 [B,N,3]) with viewpoint %p", viewpoint_layout,
+                 (const void*)viewpoint);
+    tuch_ws_scope scope(g_pc_canary != 0);
+    const int rc = pc_knn_check("tuch_point_cloud_normals", workspace, workspace_bytes, B, Q, N, k);
+    if (rc != TUCH_OK) return rc;
+    (void)counts; (void)weights;
+    const float limit = max_distance > 0.0f ? fminf(max_distance * max_distance, kPcMaxD2) : kPcMaxD2;
+    const int lanes = pc_knn_lanes(k);
+    hipLaunchKernelGGL(pc_normals_kernel, dim3(ceil_div(N, lanes), B), dim3(lanes),
+                       (size_t)k * lanes * sizeof(unsigned long long), (hipStream_t)stream,
+                       pc_tables((void*)workspace, workspace_bytes, B, Q), points, queries, shift, query_counts, limit, Q, N, k,
+                       viewpoint, viewpoint_layout, normals, variation, count, cov);
+    return tuch_check_launch("tuch_point_cloud_normals");
 }
 
 extern "C" int tuch_point_cloud_fit_terms(const void* workspace, size_t workspace_bytes, const float* points,

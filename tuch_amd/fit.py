@@ -157,6 +157,18 @@ class ScanFitter:
     bit is that of the fit without the option.  ``face`` is -1 for the points left without a match at the final
     evaluation: the share matched is ``(face >= 0)``.
 
+    ``estimate_normals`` k (1 .. 32; needs ``max_normal_angle``) is for points that arrive without normals, a depth point
+    cloud: at the start of every call, outside the replayed loop, the session's normals buffer is filled with
+    ``PointCloud.normals(k=k, viewpoint=viewpoint)`` of the scan itself (PCA over every real point's k nearest real
+    points; ``viewpoint`` [B,3] at the call, the sensor's position, turns them towards the sensor; points whose
+    neighbourhood determines no normal get a zero row and stay unconstrained).  The cloud is the two-sided fit's when
+    ``model_to_scan > 0``, otherwise one the session keeps for this.  The loop's launches and the bits of the result are
+    those of the same fit called with these normals; passing ``normals=`` as well is an error.  Pass ``viewpoint``
+    whenever the sensor's position is known: without it the normals carry the canonical sign (the component of the
+    largest magnitude positive), which has nothing to do with inside and outside, and every point whose normal so
+    signed faces away from the surface's outward normal is left without a match by ``max_normal_angle``, silently
+    -- about half of a closed body.
+
     ``vertices`` [B,V,3] include the translation; ``loss`` [B] (the scan -> model term), ``face`` [B,Q] and ``bary``
     [B,Q,3] are those of the evaluation after the last update; the other direction's is ``self.model_to_scan_result`` =
     CloudFit(loss [B], d2 [B,V], index [B,V]) (None when the option is off).  ``global_orient`` is held fixed unless ``fit_global_orient`` is set.  Inputs are
@@ -164,7 +176,7 @@ class ScanFitter:
 
     def __init__(self, smpl, model, step_size=1e-2, num_iters=300, fit_global_orient=True, rho='distance', sigma=None,
                  use_hint=True, use_graph=True, record_history=False, model_to_scan=0.0, vertex_weights=None,
-                 max_distance=None, resolution=64, max_normal_angle=None):
+                 max_distance=None, resolution=64, max_normal_angle=None, estimate_normals=None):
         if rho not in ops.SCAN_RHO:
             raise ValueError('ScanFitter: rho must be one of %s, got %r' % (sorted(ops.SCAN_RHO), rho))
         if rho == 'gmof' and not (sigma is not None and float(sigma) > 0.0):
@@ -177,6 +189,10 @@ class ScanFitter:
             raise ValueError('ScanFitter: max_normal_angle must be in (0, 90] degrees (or None), got %r' % (max_normal_angle,))
         if not (isinstance(resolution, int) and 1 <= resolution <= 256):
             raise ValueError('ScanFitter: resolution must be an int in 1 .. 256, got %r' % (resolution,))
+        if estimate_normals is not None:
+            ops._check_k('ScanFitter: estimate_normals', estimate_normals)
+            if max_normal_angle is None:
+                raise ValueError('ScanFitter: estimate_normals needs max_normal_angle')
         num_verts = int(smpl.v_template.shape[0])
         if vertex_weights is not None and (not torch.is_tensor(vertex_weights) or vertex_weights.dim() not in (1, 2)
                                            or vertex_weights.shape[-1] != num_verts):
@@ -193,6 +209,7 @@ class ScanFitter:
         self.max_distance = None if max_distance is None else float(max_distance)
         self.resolution = resolution
         self.max_normal_angle = None if max_normal_angle is None else float(max_normal_angle)
+        self.estimate_normals = estimate_normals
         self.model_to_scan_result = None
         self.use_graph = use_graph
         # as MeshFitter: the objective and the parameters *before* every update in self.history['fit'], the parameters in
@@ -250,12 +267,12 @@ class ScanFitter:
         params = [t['body_pose'], t['betas'], t['transl']] + ([t['global_orient']] if self.fit_global_orient else [])
         for p in params:
             p.requires_grad = True
-        sess = dict(t=t, cloud=cloud, vertex_weights=vw, keys_alive=(self.vertex_weights,),
+        sess = dict(t=t, cloud=cloud, normals_cloud=None, vertex_weights=vw, keys_alive=(self.vertex_weights,),
                     stage=SMPLifyDC._Stage(self, 'fit', params, iteration, {}))
         return key, sess
 
     def __call__(self, points, global_orient, counts=None, weights=None, body_pose=None, betas=None, transl=None,
-                 normals=None):
+                 normals=None, viewpoint=None):
         if points.dim() != 3 or points.shape[2] != 3 or points.shape[0] == 0 or points.shape[1] == 0:
             raise ValueError('ScanFitter: points must be [B,Q,3], got %s' % (tuple(points.shape),))
         batch, num_points = points.shape[0], points.shape[1]
@@ -268,6 +285,14 @@ class ScanFitter:
             raise ValueError('ScanFitter: normals need max_normal_angle (the fitter was created without it)')
         if normals is not None and tuple(normals.shape) != (batch, num_points, 3):
             raise ValueError('ScanFitter: normals has shape %s, expected %s' % (tuple(normals.shape), (batch, num_points, 3)))
+        if self.estimate_normals is not None and normals is not None:
+            raise ValueError('ScanFitter: normals were passed to a fitter that estimates them (estimate_normals=%d)'
+                             % self.estimate_normals)
+        if viewpoint is not None and self.estimate_normals is None:
+            raise ValueError('ScanFitter: viewpoint needs estimate_normals (the fitter was created without it)')
+        if viewpoint is not None and tuple(viewpoint.shape) != (batch, 3):
+            raise ValueError('ScanFitter: viewpoint has shape %s, expected %s' % (tuple(viewpoint.shape), (batch, 3)))
+        with_normals = normals is not None or self.estimate_normals is not None
         device = points.device
         if device.type != 'cuda':
             raise RuntimeError('ScanFitter runs on a HIP device (there is no host fallback); got tensors on %s' % device)
@@ -282,7 +307,7 @@ class ScanFitter:
             self.history = {'fit': []}
         # graph replays never run on the NULL stream (ops.py)
         with ops.off_default_stream(device) if on_gpu else contextlib.nullcontext():
-            key, sess = self._session(batch, num_points, counts is not None, weights is not None, device, normals is not None)
+            key, sess = self._session(batch, num_points, counts is not None, weights is not None, device, with_normals)
             t = sess['t']
             with torch.no_grad():
                 t['points'].copy_(points)
@@ -312,6 +337,16 @@ class ScanFitter:
                 if sess['cloud'] is not None:
                     sess['cloud'].rebuild(t['points'], t['counts'], t['weights'])
                     t['near'].fill_(-1)                   # no memory of another call's answers
+                if self.estimate_normals is not None:
+                    # the scan's normals from the scan itself, once per call: the loop is that of a fit given normals
+                    cloud = sess['cloud']
+                    if cloud is None:
+                        if sess['normals_cloud'] is None:
+                            sess['normals_cloud'] = ops.PointCloud(t['points'], t['counts'], t['weights'], self.resolution)
+                        else:
+                            sess['normals_cloud'].rebuild(t['points'], t['counts'], t['weights'])
+                        cloud = sess['normals_cloud']
+                    t['normals'].copy_(cloud.normals(k=self.estimate_normals, viewpoint=viewpoint).normal)
             captured = sess['stage'].run(self.num_iters, None, capture)
             # a captured loop is kept for the next call; a session that ran eagerly (or lost its capture) is dropped
             if not (captured and self.keep_sessions):
@@ -325,7 +360,7 @@ class ScanFitter:
                 hint = t['hint'] if self.use_hint else None
                 _, loss, near = ops.scan_fit(self.model, verts, t['transl'], t['points'], t['counts'], t['weights'], hint,
                                              self.rho, self.sigma, normals=t['normals'],
-                                             max_angle=self.max_normal_angle if normals is not None else None)
+                                             max_angle=self.max_normal_angle if with_normals else None)
                 vertices = verts + t['transl'][:, None]
                 self.model_to_scan_result = None
                 if sess['cloud'] is not None:

@@ -1685,6 +1685,26 @@ class NearestPoint(NamedTuple):
     index: torch.Tensor
 
 
+class KNearest(NamedTuple):
+    d2: torch.Tensor
+    index: torch.Tensor
+
+
+class PointNormals(NamedTuple):
+    normal: torch.Tensor
+    variation: torch.Tensor
+    count: torch.Tensor
+    cov: Optional[torch.Tensor]
+
+
+MAX_NEIGHBOURS = 32
+
+
+def _check_k(what, k):
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_NEIGHBOURS:
+        raise ValueError('%s: k must be an int in 1 .. %d, got %r' % (what, MAX_NEIGHBOURS, k))
+
+
 class CloudGrid(NamedTuple):
     """Host copies of a PointCloud's per-body headers: origin [B,3] float32, cell [B] float32, dims [B,3] int32."""
     origin: np.ndarray
@@ -1799,6 +1819,81 @@ class PointCloud:
         counts = None if counts is None else counts.to(torch.int32).contiguous()
         d2 = _CloudNearest.apply(queries, shift, self, counts, hint, tau, index)
         return NearestPoint(d2, index)
+
+    def _knn_args(self, what, queries, k, shift, counts, max_distance):
+        """The checks and conversions knn and normals share: (queries, shift, counts, tau) as the C ABI takes them."""
+        _check_k(what, k)
+        own = queries is None
+        if own:
+            queries = self.points
+        self._check_queries(what, queries, shift, None)
+        b = queries.shape[0]
+        if counts is not None and tuple(counts.shape) != (b,):
+            raise ValueError('%s: counts must be [%d], got %s' % (what, b, tuple(counts.shape)))
+        tau = _tau_of(what, max_distance)
+        _need_hip(what, counts)
+        qs = _f32(queries)
+        if own:
+            # the cloud's own points in the caller's order: an invalid point is no query (beyond counts: query_counts;
+            # weight 0: made non-finite, which the rule answers with the no-winner outputs)
+            if counts is None:
+                counts = self.counts
+            if self.weights is not None:
+                qs = torch.where((self.weights != 0)[:, :, None], qs, torch.full_like(qs, float('nan')))
+        counts = None if counts is None else counts.to(torch.int32).contiguous()
+        return qs, None if shift is None else _f32(shift), counts, tau
+
+    def knn(self, queries=None, k=8, shift=None, counts=None, max_distance=None) -> KNearest:
+        """For every real query ``queries[b,n] + shift[b]`` the k (1 .. 32) nearest valid points of body b's cloud in
+        ascending order of the packed key (d2, then index): ``KNearest(d2 [B,N,k], index [B,N,k] int32)``, the tail -1 /
+        +inf where fewer than k points are admissible.  ``queries=None``: the cloud's own points in the caller's order
+        (each valid point finds itself first, or its smallest-index duplicate; invalid points get -1 / +inf).  The bits
+        are those of a sorted float32 brute-force sweep (tuch_point_cloud_knn).  No gradients."""
+        qs, sh, counts, tau = self._knn_args('PointCloud.knn', queries, k, shift, counts, max_distance)
+        b, n = qs.shape[0], qs.shape[1]
+        d2 = torch.empty(b, n, k, dtype=torch.float32, device=qs.device)
+        index = torch.empty(b, n, k, dtype=torch.int32, device=qs.device)
+        with torch.cuda.device(qs.device):
+            _C.check(_C.lib().tuch_point_cloud_knn(
+                _C.ptr(self._ws), self._nbytes, _C.ptr(self.points), _C.ptr(self.counts), _C.ptr(self.weights), _C.ptr(qs),
+                _C.ptr(sh), _C.ptr(counts), tau, b, self.num_points, n, k, _C.ptr(d2), _C.ptr(index), _C.stream()))
+        return KNearest(d2, index)
+
+    def normals(self, queries=None, k=16, viewpoint=None, shift=None, counts=None, max_distance=None,
+                with_cov=False) -> PointNormals:
+        """PCA normals over the k nearest valid points of every query (tuch_point_cloud_normals; the rule, the error bound
+        and the zero rows are in include/tuch_amd.h): ``PointNormals(normal [B,N,3], variation [B,N], count [B,N] int32,
+        cov [B,N,6] or None)``.  ``viewpoint`` [B,3] or [B,N,3], the sensor's position in the frame of the shifted
+        queries, turns every normal towards it; without one the sign is canonical (the component of the largest
+        magnitude is positive).  A zero row means "unknown" (fewer than 3 neighbours, collinear, coincident or isotropic
+        ones) and is what scan_fit's ``normals`` treats as unconstrained.  ``queries=None``: the cloud's own points.
+        No gradients."""
+        what = 'PointCloud.normals'
+        _check_k(what, k)
+        n_of = self.num_points if queries is None else (queries.shape[1] if queries.dim() == 3 else -1)
+        layout = 0
+        if viewpoint is not None:
+            if tuple(viewpoint.shape) == (self.batch, 3):
+                layout = 1
+            elif tuple(viewpoint.shape) == (self.batch, n_of, 3):
+                layout = 2
+            else:
+                raise ValueError('%s: viewpoint must be [%d,3] or [%d,N,3], got %s'
+                                 % (what, self.batch, self.batch, tuple(viewpoint.shape)))
+        qs, sh, counts, tau = self._knn_args(what, queries, k, shift, counts, max_distance)
+        _need_hip(what, viewpoint)
+        view = None if viewpoint is None else _f32(viewpoint)
+        b, n = qs.shape[0], qs.shape[1]
+        normal = torch.empty(b, n, 3, dtype=torch.float32, device=qs.device)
+        variation = torch.empty(b, n, dtype=torch.float32, device=qs.device)
+        count = torch.empty(b, n, dtype=torch.int32, device=qs.device)
+        cov = torch.empty(b, n, 6, dtype=torch.float32, device=qs.device) if with_cov else None
+        with torch.cuda.device(qs.device):
+            _C.check(_C.lib().tuch_point_cloud_normals(
+                _C.ptr(self._ws), self._nbytes, _C.ptr(self.points), _C.ptr(self.counts), _C.ptr(self.weights), _C.ptr(qs),
+                _C.ptr(sh), _C.ptr(counts), tau, b, self.num_points, n, k, _C.ptr(view), layout, _C.ptr(normal),
+                _C.ptr(variation), _C.ptr(count), _C.ptr(cov), _C.stream()))
+        return PointNormals(normal, variation, count, cov)
 
     def grid(self) -> CloudGrid:
         """The headers the build wrote, as host arrays (synchronises; for tests and tools)."""

@@ -19,6 +19,7 @@ of the fit runs eagerly through the same runner.
 from __future__ import annotations
 
 import contextlib
+import gc
 import logging
 import os
 
@@ -152,11 +153,24 @@ class SMPLifyDC():
                     iterate(3, self._one)
                 torch.cuda.current_stream().wait_stream(side)
                 done = 3
+                # Python's cycle collector must not run inside the capture.  A fitter and its stages refer to each other, so a
+                # dropped fitter's sessions -- captured graphs and their memory pools -- die only when the collector
+                # finds them, and destroying a graph while a stream is capturing aborts the process (seen in the test
+                # suite: which allocation triggers a collection depends on everything that ran before).  Dead sessions
+                # are collected here, before the capture, and the collector rests until the capture has ended.  (The
+                # collector's switch is process-wide: two threads capturing at once may re-enable it early for each
+                # other, which is then no worse than before.)
+                gc.collect()
+                collecting = gc.isenabled()
+                gc.disable()
                 try:
                     graph = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(graph, capture_error_mode='thread_local'):
                         self._one()
                 except Exception as exc:
+                    if collecting:
+                        gc.enable()
+                        collecting = False
                     # a loop that cannot be captured still runs (eagerly), but never silently: TUCH_GRAPH_STRICT=1
                     # (set by the tests) turns this into an error
                     if owner.graph_strict:
@@ -167,6 +181,9 @@ class SMPLifyDC():
                     self.optimizer.zero_grad()       # a half-recorded fused update must not swallow the next step()
                     iterate(num_iters - done, self._one)
                     return False
+                finally:
+                    if collecting:
+                        gc.enable()
                 self.graph = graph
             iterate(num_iters - done, self.graph.replay)
             owner.graph_replayed[self.name] = num_iters - done
