@@ -278,14 +278,19 @@ TERM_TAU = 0.02
 
 @functools.lru_cache(maxsize=None)
 def term_case(name: str, rho: str, weighted: str = 'none', tau: bool = False, batch: int = 3, num_points: int = 257,
-              seed: int = 0):
+              seed: int = 0, num_verts: int = None):
     """dict(verts [B,V,3], transl, points, counts (ragged), weights=None, vw, rho, sigma, tau, scale, ref: term_statement
     in float64, bound [B]: 4 x the error of the float32 numpy restatement, floored as sc.term_case floors its bound).
-    weighted: 'none', 'V' or 'BV' (a quarter of the vertex weights is 0)."""
-    verts, faces = mesh_verts(name, batch, seed)
+    weighted: 'none', 'V' or 'BV' (a quarter of the vertex weights is 0).  num_verts: the mesh's vertices cycled / cut to
+    that many queries, 5 mm of noise on each (the clouds stay samples of the mesh itself)."""
+    mesh_v, faces = mesh_verts(name, batch, seed)
+    verts = mesh_v
+    if num_verts is not None:
+        noise = 5e-3 * np.random.default_rng(seed + 43).standard_normal((batch, num_verts, 3))
+        verts = (mesh_v[:, np.arange(num_verts) % mesh_v.shape[1]] + noise).astype(F32)
     rng = np.random.default_rng(seed + 41)
     transl = (0.1 * rng.standard_normal((batch, 3))).astype(F32)
-    points = np.stack([surface_samples(verts[b], faces, num_points, seed + 3 * b, noise=5e-3) + transl[b] for b in range(batch)])
+    points = np.stack([surface_samples(mesh_v[b], faces, num_points, seed + 3 * b, noise=5e-3) + transl[b] for b in range(batch)])
     points = points.astype(F32)
     counts = sc.ragged_counts(batch, num_points)
     num_verts = verts.shape[1]

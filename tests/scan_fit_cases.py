@@ -208,8 +208,9 @@ def term_numpy(points, verts, faces, transl, counts, weights, rho, sigma, dtype)
 
 
 def ragged_counts(batch, count):
-    """Every body another count: all, about a quarter, about half (0 and a value above Q have tests of their own)."""
-    return np.array([count, max(count // 4, 1), count // 2 + 1][:batch], np.int32)
+    """Every body another count: all, about a quarter, about half, and round again beyond three bodies (0 and a value above
+    Q have tests of their own)."""
+    return np.resize(np.array([count, max(count // 4, 1), count // 2 + 1], np.int32), batch)
 
 
 @functools.lru_cache(maxsize=None)

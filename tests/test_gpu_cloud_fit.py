@@ -373,6 +373,24 @@ def test_term_matches_float64(rho, weighted, tau):
         assert np.array_equal(got[key], again[key]), key
 
 
+def test_term_at_batch_65_with_two_chunks_matches_float64():
+    """65 bodies x 257 weighted vertices against clouds of 65 points: two workgroups per body (and two strides of the
+    normaliser's sum), and 4 x 65 = 260 (body, component) sums for the 256 threads of the workgroup that arrives last --
+    the second trip of its loop, which a batch of 3 never takes.  per_body and total by the rule of
+    test_term_matches_float64; the last body's sums, the ones of the second trip, have the bits of that body alone."""
+    c = cf.term_case('body122', 'distance', 'BV', False, batch=65, num_points=65, num_verts=257)
+    got, _ = _term(c)
+    err = np.abs(got['per'].astype(np.float64) - c['ref'][0])
+    print('cloud_fit batch 65: largest per-body error / bound', (err / c['bound']).max())
+    assert np.all(c['ref'][0] > 0)
+    assert np.all(err <= c['bound']), (err, c['bound'])
+    assert abs(got['total'] - c['ref'][1]) <= c['bound'].sum()
+    last = dict(c, **{k: c[k][64:] for k in ('verts', 'transl', 'points', 'counts', 'vw')})
+    alone, _ = _term(last)
+    for key in ('per', 'gt', 'gv'):
+        assert np.array_equal(got[key][64:], alone[key]), key
+
+
 @pytest.mark.parametrize('rho', sc.RHOS)
 def test_gradients_against_central_differences(rho):
     from tuch_amd import ops

@@ -187,6 +187,23 @@ def test_term_matches_float64(name, count, rho):
     assert total.item() == got['total'] and np.array_equal(per.cpu().numpy(), got['per'])
 
 
+def test_term_at_batch_65_with_two_chunks_matches_float64():
+    """65 bodies x 257 points: two workgroups per body, and 4 x 65 = 260 (body, component) sums for the 256 threads of the
+    workgroup that arrives last -- the second trip of its loop, which a batch of 3 never takes.  per_body and total by the
+    rule of test_term_matches_float64; the last body's sums, the ones of the second trip, have the bits of that body alone."""
+    c = sc.term_case('icosphere', 65, 257, 'distance')
+    m = model('icosphere')
+    got, _ = _term(m, c)
+    err = np.abs(got['per'].astype(np.float64) - c['ref'][0])
+    print('scan_fit batch 65: largest per-body error / bound', (err / c['bound']).max())
+    assert np.all(err <= c['bound']), (err, c['bound'])
+    assert abs(got['total'] - c['ref'][1]) <= c['bound'].sum()
+    last = dict(c, **{k: c[k][64:] for k in ('verts', 'points', 'transl', 'counts')})
+    alone, _ = _term(m, last)
+    for key in ('per', 'gt', 'gv', 'gp'):
+        assert np.array_equal(got[key][64:], alone[key]), key
+
+
 @pytest.mark.parametrize('rho', sc.RHOS)
 def test_term_weighted_matches_float64(rho):
     c = sc.term_case('icosphere', 3, 257, rho, weighted=True)

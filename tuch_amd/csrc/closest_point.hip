@@ -13,6 +13,8 @@
 //                           bound is within its current best (ballot); the lanes whose own bound admits it run the
 //                           exact test over its faces, every lane reading the same triangle (an LDS broadcast).  The
 //                           next admitted group's loads are issued before the current group's tests (two LDS buffers).
+// The adjoint (cp_bwd_kernel) scatters into the winning face's corner rows with fit_scatter_corners (fit_reduce.h: shared
+// with scan_fit.hip's term) and converts fixed-point sums with tuch_launch_fixed_to_float (common.h).
 //
 // The rule.  cp_eval below is THE squared distance of a (query, triangle) pair: one instruction sequence (contraction
 // off, every fused operation spelled out), a function of the six points' bits only.  The winner is the smallest packed
@@ -95,6 +97,7 @@
 //   The hint.  A hinted lane starts from its hint only if the face is in [0, F), admissible for the lane and at a finite
 // d2; then its key is one the unpruned sweep computes too, and the argument of the hinted start holds.  Any other hint
 // takes the unhinted path.
+#include "fit_reduce.h"
 #include "model.h"
 #include "workspace.h"
 
@@ -636,31 +639,13 @@ __global__ __launch_bounds__(256) void cp_bwd_kernel(const float* __restrict__ v
         gx = g2 * (points[o * 3] - cx);
         gy = g2 * (points[o * 3 + 1] - cy);
         gz = g2 * (points[o * 3 + 2] - cz);
-        if (grad_verts || grad_fixed)
-            for (int k = 0; k < 3; ++k) {
-                const size_t row = ((size_t)b * V + vi[k]) * 3;
-                if (kFixed) {
-                    fixed_add(grad_fixed + row, -w[k] * gx);
-                    fixed_add(grad_fixed + row + 1, -w[k] * gy);
-                    fixed_add(grad_fixed + row + 2, -w[k] * gz);
-                } else {
-                    atomicAdd(grad_verts + row, -w[k] * gx);
-                    atomicAdd(grad_verts + row + 1, -w[k] * gy);
-                    atomicAdd(grad_verts + row + 2, -w[k] * gz);
-                }
-            }
+        if (grad_verts || grad_fixed) fit_scatter_corners<kFixed>(grad_verts, grad_fixed, (size_t)b * V, vi, w, gx, gy, gz);
     }
     if (grad_points) {
         grad_points[o * 3] = gx;
         grad_points[o * 3 + 1] = gy;
         grad_points[o * 3 + 2] = gz;
     }
-}
-
-__global__ __launch_bounds__(256) void cp_fixed_to_float_kernel(const long long* __restrict__ fixed, float* __restrict__ out, size_t n)
-{
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) out[i] = fixed_value(fixed[i]);
 }
 
 }  // namespace
@@ -761,11 +746,8 @@ extern "C" int tuch_closest_point_bwd(const tuch_contact_model* m, const float* 
         hipLaunchKernelGGL(cp_bwd_kernel<true>, grid, dim3(256), 0, s, verts, points, face, bary, grad_d2,
                            (const int32_t*)m->faces, m->V, m->F, Q, grad_points, (float*)nullptr,
                            (long long*)grad_verts_fixed_zeroed);
-        if (grad_verts) {
-            const size_t n = (size_t)B * m->V * 3;
-            hipLaunchKernelGGL(cp_fixed_to_float_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s,
-                               (const long long*)grad_verts_fixed_zeroed, grad_verts, n);
-        }
+        if (grad_verts)
+            tuch_launch_fixed_to_float((const long long*)grad_verts_fixed_zeroed, grad_verts, (size_t)B * m->V * 3, s);
     } else {
         hipLaunchKernelGGL(cp_bwd_kernel<false>, grid, dim3(256), 0, s, verts, points, face, bary, grad_d2,
                            (const int32_t*)m->faces, m->V, m->F, Q, grad_points, grad_verts, (long long*)nullptr);

@@ -56,6 +56,14 @@ static __device__ __forceinline__ float wave_min_uniform(float v)
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
 
+// Sum over the 64 lanes, valid in lane 0; the order is fixed, so the result depends on nothing but the inputs.
+static __device__ __forceinline__ float wave_sum_lane0(float v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;
+}
+
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
 // Model constants: device memory, or host memory under TUCH_HOST_TABLES=1 (api.hip: sanitizer runs of the table builders)
@@ -95,6 +103,11 @@ static __device__ __forceinline__ void fixed_add(long long* acc, float x)
     atomicAdd((unsigned long long*)acc, (unsigned long long)__double2ll_rn((double)x * kFixedScale));
 }
 static __device__ __forceinline__ float fixed_value(long long acc) { return (float)((double)acc * (1.0 / kFixedScale)); }
+// out[i] = fixed_value(fixed[i]), and n 32-bit words of zeros (a float array, or 64-bit fixed-point sums as pairs of
+// words): one launch each, n > 0 (contact_terms.hip, beside tuch_fixed_to_float).  Kernels, not copies or memsets: a
+// captured loop then holds kernel nodes only.  The caller checks the launch.
+void tuch_launch_fixed_to_float(const long long* fixed, float* out, size_t n, hipStream_t stream);
+void tuch_launch_zero_words(void* out, size_t n, hipStream_t stream);
 
 // torch.optim.Adam's update of one element (no weight decay / amsgrad), shared by adam_kernel (adam.hip) and the body
 // model's last backward kernel (smpl_lbs.hip: PoseAdam) so that the two give the same BITS: every operation is spelled

@@ -49,8 +49,7 @@ __device__ __forceinline__ Term contact_term(float d, bool exterior, int mode, f
 
 __device__ __forceinline__ float block_sum(float v, float* smem)
 {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    v = wave_sum_lane0(v);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     if (lane == 0) smem[wave] = v;
     __syncthreads();
@@ -393,7 +392,23 @@ __global__ __launch_bounds__(256) void fixed_to_float_kernel(const long long* __
     if (i < n) out[i] = fixed_value(acc[i]);
 }
 
+__global__ __launch_bounds__(256) void zero_words_kernel(uint32_t* __restrict__ out, size_t n)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = 0u;
+}
+
 }  // namespace
+
+void tuch_launch_fixed_to_float(const long long* fixed, float* out, size_t n, hipStream_t stream)
+{
+    hipLaunchKernelGGL(fixed_to_float_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, fixed, out, n);
+}
+
+void tuch_launch_zero_words(void* out, size_t n, hipStream_t stream)
+{
+    hipLaunchKernelGGL(zero_words_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (uint32_t*)out, n);
+}
 
 extern "C" size_t tuch_smplify_stage2_fused_scratch_floats(int B) { return (size_t)(B > 0 ? B : 0) * kFusedSplits * 3; }
 
@@ -429,8 +444,7 @@ extern "C" int tuch_fixed_to_float(const void* fixed, size_t n, float* out, void
 {
     TUCH_REQUIRE(fixed && out, "tuch_fixed_to_float: null pointer");
     if (n == 0) return TUCH_OK;
-    hipLaunchKernelGGL(fixed_to_float_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const long long*)fixed, out, n);
+    tuch_launch_fixed_to_float((const long long*)fixed, out, n, (hipStream_t)stream);
     return tuch_check_launch("tuch_fixed_to_float");
 }
 
@@ -526,9 +540,7 @@ extern "C" int tuch_contact_terms_bwd_fixed(const float* points, const int32_t* 
     hipLaunchKernelGGL(contact_terms_bwd_kernel<true>, dim3(ceil_div(N, 256), B), dim3(256), 0,
                        (hipStream_t)stream, points, partner, exterior, grad_scale, N, mode, euclthres,
                        (float*)nullptr, (long long*)grad_fixed_zeroed);
-    const size_t n = (size_t)B * N * 3;
-    hipLaunchKernelGGL(fixed_to_float_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const long long*)grad_fixed_zeroed, grad_points, n);
+    tuch_launch_fixed_to_float((const long long*)grad_fixed_zeroed, grad_points, (size_t)B * N * 3, (hipStream_t)stream);
     return tuch_check_launch("tuch_contact_terms_bwd_fixed");
 }
 

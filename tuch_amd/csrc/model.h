@@ -118,8 +118,6 @@ extern "C" size_t tuch_closest_point_oriented_workspace_bytes(const tuch_contact
 int tuch_cp_search(const char* name, const tuch_contact_model* m, const float* verts, const float* points, const float* shift,
                    const float* normals, float max_angle_cos, const int32_t* counts, const int32_t* hint, int B, int Q,
                    float* d2, int32_t* face, float* bary, void* workspace, size_t workspace_bytes, void* stream);
-// rho of tuch_scan_fit_terms (scan_fit.hip), as include/tuch_amd.h numbers them
-enum { TUCH_SCAN_RHO_SQUARED = 0, TUCH_SCAN_RHO_DISTANCE = 1, TUCH_SCAN_RHO_GMOF = 2 };
 
 struct tuch_contact_model {
     tuch_tables tables;        // owns every device table below

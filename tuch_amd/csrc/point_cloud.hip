@@ -16,8 +16,8 @@
 // There is no gradient with respect to the points of the cloud: they are data.
 //
 // The structure (build: five launches, no host round trip, no allocation, capturable).
-//   pc_clear_kernel    the cell and block tables of every body <- 0 (a kernel, not a memset: a captured loop then holds
-//                      kernel nodes only)
+//   tuch_launch_zero_words (common.h)  the cell and block tables of every body <- 0 (a kernel, not a memset: a captured
+//                      loop then holds kernel nodes only)
 //   pc_header_kernel   one workgroup per body: box and number of the valid points -> header [16 words]: origin (the box's
 //                      low corner), cell edge = longest extent / resolution (isotropic; at least kPcMinCell, so a box
 //                      without extent is one cell), 1 / edge, dims_k = min(resolution, floor(extent_k / edge) + 1)
@@ -28,10 +28,12 @@
 //                      ends as the END of its cell: cell c is [table[c - 1], table[c]), cell 0 starts at 0).  The order
 //                      inside a cell depends on atomic arrival; by the key rule no output depends on it.
 //
-// The query (pc_search): one query per lane, 64 consecutive queries of one body per wavefront.  A lane walks the blocks in
-// Chebyshev rings around the block of its own (clamped) cell; a block is opened when it holds points and its bound admits
-// it, then each of its cells likewise, then pc_d2 on the cell's points.  The walk ends after ring r when the ring bound
-// (below) exceeds the lane's key, or when the grid is exhausted.
+// The query (pc_walk, ONE body of code for the one-key and the k-key query: what follows, and the margin below, is about
+// it): one query per lane, 64 consecutive queries of one body per wavefront.  A lane walks the blocks in Chebyshev rings
+// around the block of its own (clamped) cell; a block is opened when it holds points and its bound admits it, then each
+// of its cells likewise, then pc_d2 on the cell's points, which go to the lane's sink.  The walk ends after ring r when
+// the ring bound (below) exceeds the sink's bound -- the lane's key (PcBest) or its k-th key (PcList) -- or when the grid
+// is exhausted.
 //
 // Pruning margin.  Everything is measured in cells: t = fl(fl(x - origin) * inv) for a point s (t_s) and for the query
 // (t_q), the SAME two operations.  Undoing them, s - q = (t_s (1 + e_s) - t_q (1 + e_q)) / inv with |e| <= 2.1 u
@@ -56,15 +58,15 @@
 // sweep computes too, so it cannot undercut the sweep's minimum; it only shortens the walk.  Anything else takes the
 // unhinted path.  hint may alias the index output: a lane reads its own entry before it writes it.
 //
-// k nearest points and normals (tuch_point_cloud_knn / _normals; pc_knn_search, pc_knn_kernel, pc_normals_kernel).  The
+// k nearest points and normals (tuch_point_cloud_knn / _normals; PcList, pc_knn_kernel, pc_normals_kernel).  The
 // rule above, verbatim, for the k (1 .. 32) smallest keys of a query in ascending order: index [B,N,k], d2 [B,N,k]; with
 // fewer than k admissible points (finite d2, within tau) the tail is -1 / +inf; a non-finite query, an empty cloud or
 // an entry beyond query_counts gives all -1 / +inf.  A point that coincides with the query is an ordinary neighbour with
 // d2 = 0.  The outputs equal a sorted float32 brute-force sweep bit for bit, alone or in a batch, for any order of
 // queries or points, any resolution, eager or replayed.
-//   pc_knn_search walks the same Chebyshev rings with the same gap bounds and the same 2^-20 margin as pc_search.  The
-// pruning bound is the lane's k-th key so far; while its list is not full the bound is (limit, -1).  The derivation
-// above carries over unchanged: a cell, a block, a row, a slab or the rest of the grid is skipped only when its lower
+//   It is pc_walk with the list as its sink: the pruning bound is the lane's k-th key so far; while its list is not full
+// the bound is (limit, -1).  The derivation above holds for any such bound: a cell, a block, a row, a slab or the rest
+// of the grid is skipped only when its lower
 // bound exceeds the bound's d2, so no point whose key is below the bound is ever skipped, and the k smallest keys are
 // found whatever was visited in whatever order.  With no tau the ring test cannot end the walk before the list is full
 // (limit is then the largest finite float): the walk ends after a ring only once the list is full (or nothing beyond
@@ -89,27 +91,22 @@
 // The term (pc_fit_kernel; tuch_point_cloud_fit_terms): the query for q = verts[b,v] + transl[b], then per vertex
 // g_v = scale w_v rho'(d2_v) / sum w and grad_verts[b,v] = 2 g_v (q - s) written by the lane that owns the row (no
 // atomics); the per-body loss, the normaliser and grad_transl = sum_v grad_verts[b,v] cross to the workgroup that arrives
-// last (mesh_fit.hip's ticket scheme, here with a release fence / acquire fence pair) and are added in chunk order, the
-// total in a fixed tree: no float atomics, the same bits in either mode of tuch_set_deterministic and for a body alone or
-// in a batch.  A vertex of weight 0 is not computed from; one without winner contributes rho(tau^2) when tau is given and
+// last through fit_reduce_tail (fit_reduce.h: the hand-over all three fit terms use, drained write-through stores and no
+// fences, and its argument) and are added in chunk order, the total in a fixed tree: no float atomics, the same bits in
+// either mode of tuch_set_deterministic and for a body alone or in a batch.  The normaliser is fit_body_sum, rho is fit_rho.  A vertex of weight 0 is not computed from; one without winner contributes rho(tau^2) when tau is given and
 // the cloud is not empty, else 0, with a zero gradient row; a body with an empty cloud or without weight has loss 0.
+#include "fit_reduce.h"
 #include "workspace.h"
 #include <math.h>
 #include <string.h>
-
-#define TUCH_SCAN_RHO_SQUARED 0
-#define TUCH_SCAN_RHO_DISTANCE 1
-#define TUCH_SCAN_RHO_GMOF 2
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kWaves = kBlock / 64;
+constexpr int kBlock = kFitBlock;
 constexpr int kCtl = 64;                 // control words in front of the headers: [0] guard words found changed
 constexpr int kHead = 16;                // words per body header
-constexpr int kPart = 8;                 // floats per partial: sum w rho, grad_transl.xyz, sum w, 3 unused
 constexpr int kMaxRes = 256;
 constexpr float kPcMargin = 9.5367431640625e-7f;       // M = 2^-20
 constexpr float kPcMinCell = 1e-6f;
@@ -118,8 +115,6 @@ constexpr float kPcMaxD2 = 3.402823466e+38f;             // the largest finite d
 constexpr unsigned long long kPcNoKey = 0x7f800000ffffffffull;      // d2 = +inf, index = -1
 
 enum { H_OX = 0, H_OY, H_OZ, H_CELL, H_INV, H_DX, H_DY, H_DZ, H_N, H_RES };
-
-typedef __attribute__((address_space(1))) float gfloat;
 
 int g_pc_canary = 0;
 
@@ -150,7 +145,7 @@ PcScratch pc_scratch(int B, int N)
 {
     PcScratch l;
     size_t o = 0;
-    l.partial = tuch_ws_take(o, (size_t)B * ceil_div(N, kBlock) * kPart * sizeof(float));
+    l.partial = tuch_ws_take(o, (size_t)B * ceil_div(N, kBlock) * kFitPart * sizeof(float));
     l.total = o;
     return l;
 }
@@ -212,12 +207,6 @@ static __device__ __forceinline__ float pc_t(float x, float o, float inv) { retu
 static __device__ __forceinline__ int pc_axis_cell(float t, int d)
 {
     return pc_clampi((int)__builtin_fminf(__builtin_fmaxf(t, 0.0f), (float)(d - 1)), 0, d - 1);
-}
-
-__global__ __launch_bounds__(kBlock) void pc_clear_kernel(int32_t* __restrict__ tables, size_t n)
-{
-    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i < n) tables[i] = 0;
 }
 
 __global__ __launch_bounds__(kBlock) void pc_header_kernel(const float* __restrict__ points, const int32_t* __restrict__ counts,
@@ -366,14 +355,29 @@ static __device__ __forceinline__ bool pc_out(float sum, unsigned long long best
     return lb > __uint_as_float((uint32_t)(best >> 32)) && lb >= kPcNormal;
 }
 
-// The smallest key of query (qx, qy, qz), finite, against the cloud of body b; `best` arrives as the starting key (no
-// key: (limit bits, -1) with limit = tau^2 or FLT_MAX; or the hinted key).  A candidate needs d2 <= limit.
-static __device__ unsigned long long pc_search(const PcTables& w, int b, int Q, float qx, float qy, float qz, float limit,
-                                               unsigned long long best)
+// The sink of a one-key query: `best` arrives as the starting key (no key: (limit bits, -1) with limit = tau^2 or
+// FLT_MAX; or the hinted key) and ends as the smallest key.  A candidate needs d2 <= limit.
+struct PcBest {
+    unsigned long long best;
+    float limit;
+    __device__ __forceinline__ unsigned long long bound() const { return best; }
+    __device__ __forceinline__ void offer(float d2, unsigned long long key)
+    {
+        best = d2 <= limit && key < best ? key : best;         // (a select, not a branch around a store: the innermost loop)
+    }
+};
+
+// THE walk of the grid, for the finite query (qx, qy, qz) against the cloud of body b: the rings, gaps, slack and 2^-20
+// margin of the file header.  Everything is pruned against sink.bound(), a key that no candidate still wanted lies
+// above (PcBest: the best key so far; PcList below: the k-th), and every point of a cell that is opened goes to
+// sink.offer(d2, key).  The sink comes and goes by value: it lives in registers, and pc_nearest_kernel compiles to the
+// instructions it had when the walk was written out for the one key.
+template <typename Sink>
+static __device__ Sink pc_walk(const PcTables& w, int b, int Q, float qx, float qy, float qz, Sink sink)
 {
     const PcGrid g = pc_grid(w.head, b);
     const int n = pc_clampi(g.n, 0, Q);
-    if (n == 0) return best;
+    if (n == 0) return sink;
     const long long fine = (long long)g.res * g.res * g.res;
     const int cres = (g.res + 3) >> 2;
     const long long base = (long long)b * (fine + (long long)cres * cres * cres);
@@ -389,45 +393,43 @@ static __device__ unsigned long long pc_search(const PcTables& w, int b, int Q, 
     rmax = rmax > g.cdz - 1 - hz ? rmax : g.cdz - 1 - hz;
     for (int r = 0; r <= rmax; ++r) {
         // rings 0 .. r - 1 are done: every block left has an axis with g >= 4 (r - 1)
-        if (r > 1 && pc_out(pc_sq(g.cell, pc_gap(0.0f, 4 * (r - 1), 4 * (r - 1) + 1, slack)), best)) break;
+        if (r > 1 && pc_out(pc_sq(g.cell, pc_gap(0.0f, 4 * (r - 1), 4 * (r - 1) + 1, slack)), sink.bound())) break;
         const int z0 = hz - r < 0 ? 0 : hz - r, z1 = hz + r > g.cdz - 1 ? g.cdz - 1 : hz + r;
         const int y0 = hy - r < 0 ? 0 : hy - r, y1 = hy + r > g.cdy - 1 ? g.cdy - 1 : hy + r;
         const int x0 = hx - r < 0 ? 0 : hx - r, x1 = hx + r > g.cdx - 1 ? g.cdx - 1 : hx + r;
         for (int bz = z0; bz <= z1; ++bz) {
             const float lz = pc_sq(g.cell, pc_gap(tz, 4 * bz, 4 * bz + 4, slack));
-            if (pc_out(lz, best)) continue;                          // (one axis' share alone: the whole slab is out)
+            if (pc_out(lz, sink.bound())) continue;                          // (one axis' share alone: the whole slab is out)
             const bool zface = bz - hz == r || hz - bz == r;
             for (int by = y0; by <= y1; ++by) {
                 const float lyz = pc_add(pc_sq(g.cell, pc_gap(ty, 4 * by, 4 * by + 4, slack)), lz);
-                if (pc_out(lyz, best)) continue;
+                if (pc_out(lyz, sink.bound())) continue;
                 const bool face = zface || by - hy == r || hy - by == r;
                 // the shell of the ring: whole rows on its faces, else the two end blocks
                 const int step = face ? 1 : 2 * r;
                 for (int bx = face ? x0 : (hx - r >= 0 ? hx - r : hx + r); bx <= x1; bx += step) {
                     if (pc_table(w, base + fine + ((long long)bz * g.cdy + by) * g.cdx + bx) <= 0) continue;
                     // (the sum's order differs from a cell's below; both are bounds of their own)
-                    if (pc_out(pc_add(pc_sq(g.cell, pc_gap(tx, 4 * bx, 4 * bx + 4, slack)), lyz), best)) continue;
+                    if (pc_out(pc_add(pc_sq(g.cell, pc_gap(tx, 4 * bx, 4 * bx + 4, slack)), lyz), sink.bound())) continue;
                     const int cz1 = 4 * bz + 4 < g.dz ? 4 * bz + 4 : g.dz, cy1 = 4 * by + 4 < g.dy ? 4 * by + 4 : g.dy,
                               cx1 = 4 * bx + 4 < g.dx ? 4 * bx + 4 : g.dx;
                     for (int cz = 4 * bz; cz < cz1; ++cz) {
                         const float mz = pc_sq(g.cell, pc_gap(tz, cz, cz + 1, slack));
-                        if (pc_out(mz, best)) continue;
+                        if (pc_out(mz, sink.bound())) continue;
                         for (int cy = 4 * by; cy < cy1; ++cy) {
                             const float myz = pc_add(pc_sq(g.cell, pc_gap(ty, cy, cy + 1, slack)), mz);
-                            if (pc_out(myz, best)) continue;
+                            if (pc_out(myz, sink.bound())) continue;
                             const long long row = base + ((long long)cz * g.dy + cy) * g.dx;
                             for (int cx = 4 * bx; cx < cx1; ++cx) {
                                 const long long c = row + cx;
                                 const int end = pc_clampi(pc_table(w, c), 0, n);
                                 const int begin = c == base ? 0 : pc_clampi(pc_table(w, c - 1), 0, n);
                                 if (begin >= end) continue;
-                                if (pc_out(pc_add(pc_sq(g.cell, pc_gap(tx, cx, cx + 1, slack)), myz), best)) continue;
+                                if (pc_out(pc_add(pc_sq(g.cell, pc_gap(tx, cx, cx + 1, slack)), myz), sink.bound())) continue;
                                 for (int p = begin; p < end; ++p) {
                                     const float4 s = pts[p];
                                     const float d2 = pc_d2(qx, qy, qz, s.x, s.y, s.z);
-                                    const unsigned long long key =
-                                        ((unsigned long long)__float_as_uint(d2) << 32) | (uint32_t)__float_as_int(s.w);
-                                    if (d2 <= limit && key < best) best = key;
+                                    sink.offer(d2, ((unsigned long long)__float_as_uint(d2) << 32) | (uint32_t)__float_as_int(s.w));
                                 }
                             }
                         }
@@ -436,7 +438,7 @@ static __device__ unsigned long long pc_search(const PcTables& w, int b, int Q, 
             }
         }
     }
-    return best;
+    return sink;
 }
 
 // The whole query of one lane: the starting key, the hint, the search.  Returns the key; (uint32_t)key == ~0u: no winner.
@@ -445,14 +447,14 @@ static __device__ __forceinline__ unsigned long long pc_query(const PcTables& w,
                                                               const float* __restrict__ weights, int b, int Q, float qx,
                                                               float qy, float qz, int hint, float limit)
 {
-    unsigned long long best = ((unsigned long long)__float_as_uint(limit) << 32) | 0xffffffffull;
-    if (!pc_finite3(qx, qy, qz)) return best;
+    PcBest sink = {((unsigned long long)__float_as_uint(limit) << 32) | 0xffffffffull, limit};
+    if (!pc_finite3(qx, qy, qz)) return sink.best;
     float sx, sy, sz;
     if (hint >= 0 && hint < Q && pc_valid(points, counts, weights, b, Q, hint, sx, sy, sz)) {
         const float d2 = pc_d2(qx, qy, qz, sx, sy, sz);
-        if (d2 <= limit) best = ((unsigned long long)__float_as_uint(d2) << 32) | (uint32_t)hint;
+        if (d2 <= limit) sink.best = ((unsigned long long)__float_as_uint(d2) << 32) | (uint32_t)hint;
     }
-    return pc_search(w, b, Q, qx, qy, qz, limit, best);
+    return pc_walk(w, b, Q, qx, qy, qz, sink).best;
 }
 
 __global__ __launch_bounds__(kBlock) void pc_nearest_kernel(PcTables w, const float* __restrict__ points,
@@ -486,12 +488,15 @@ __global__ __launch_bounds__(kBlock) void pc_nearest_kernel(PcTables w, const fl
 // A lane's list: k keys in LDS, slot j of lane t at list[j * lanes + t] (the lanes of a wavefront are contiguous, so
 // every ds_read_b64 / ds_write_b64 is free of bank conflicts, whatever slot each lane is at: a row of slots is a multiple
 // of 256 bytes).  While the walk runs `n` slots are filled, in arrival order until n == k; from then on the k slots are
-// a binary max-heap (children of slot i at 2 i + 1 and 2 i + 2) whose root is `bound`, the lane's k-th key so far.
-// Until then bound is (limit bits, -1), above every admissible key.
+// a binary max-heap (children of slot i at 2 i + 1 and 2 i + 2) whose root is `root`, the lane's k-th key so far.
+// Until then root is (limit bits, -1), above every admissible key.  It is the other sink of pc_walk.
 struct PcList {
     unsigned long long* at;      // the lane's slot 0
     int lanes, k, n;
-    unsigned long long bound;
+    float limit;
+    unsigned long long root;
+    __device__ __forceinline__ unsigned long long bound() const { return root; }
+    __device__ __forceinline__ void offer(float d2, unsigned long long key);
 };
 
 // v into slot i of the max-heap of the first n slots: the larger child moves up until v is no smaller than both
@@ -512,17 +517,17 @@ static __device__ __forceinline__ void pc_list_sift(unsigned long long* at, int 
     at[(size_t)i * lanes] = v;
 }
 
-static __device__ __forceinline__ void pc_list_offer(PcList& l, float d2, float limit, unsigned long long key)
+__device__ __forceinline__ void PcList::offer(float d2, unsigned long long key)
 {
-    if (!(d2 <= limit) || key >= l.bound) return;
-    if (l.n < l.k) {
-        l.at[(size_t)l.n * l.lanes] = key;
-        if (++l.n < l.k) return;                               // not full: the bound stays at limit
-        for (int i = l.k / 2 - 1; i >= 0; --i) pc_list_sift(l.at, l.lanes, l.k, i, l.at[(size_t)i * l.lanes]);
+    if (!(d2 <= limit) || key >= root) return;
+    if (n < k) {
+        at[(size_t)n * lanes] = key;
+        if (++n < k) return;                                   // not full: the bound stays at limit
+        for (int i = k / 2 - 1; i >= 0; --i) pc_list_sift(at, lanes, k, i, at[(size_t)i * lanes]);
     } else {
-        pc_list_sift(l.at, l.lanes, l.k, 0, key);               // in place of the maximum
+        pc_list_sift(at, lanes, k, 0, key);                     // in place of the maximum
     }
-    l.bound = l.at[0];
+    root = at[0];
 }
 
 // the n keys of the list in ascending order, in place (heap sort: the root goes behind the shrinking heap)
@@ -534,73 +539,6 @@ static __device__ __forceinline__ void pc_list_sort(PcList& l)
         const unsigned long long v = l.at[(size_t)end * l.lanes];
         l.at[(size_t)end * l.lanes] = l.at[0];
         pc_list_sift(l.at, l.lanes, end, 0, v);
-    }
-}
-
-// pc_search with a list in place of the one key: the same rings, gaps, slack and 2^-20 margin, the same tests in the
-// same places, against l.bound.  Returns with the n <= k smallest admissible keys in the list, unsorted.
-static __device__ void pc_knn_search(const PcTables& w, int b, int Q, float qx, float qy, float qz, float limit, PcList& l)
-{
-    const PcGrid g = pc_grid(w.head, b);
-    const int n = pc_clampi(g.n, 0, Q);
-    if (n == 0) return;
-    const long long fine = (long long)g.res * g.res * g.res;
-    const int cres = (g.res + 3) >> 2;
-    const long long base = (long long)b * (fine + (long long)cres * cres * cres);
-    const float4* pts = w.sorted + (size_t)b * Q;
-    const float tx = pc_t(qx, g.ox, g.inv), ty = pc_t(qy, g.oy, g.inv), tz = pc_t(qz, g.oz, g.inv);
-    const float tmax = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(tx), __builtin_fabsf(ty)), __builtin_fabsf(tz));
-    const float slack = pc_mul(kPcMargin, pc_add(tmax, (float)(g.res + 2)));
-    const int hx = pc_axis_cell(tx, g.dx) >> 2, hy = pc_axis_cell(ty, g.dy) >> 2, hz = pc_axis_cell(tz, g.dz) >> 2;
-    int rmax = hx > g.cdx - 1 - hx ? hx : g.cdx - 1 - hx;
-    rmax = rmax > hy ? rmax : hy;
-    rmax = rmax > g.cdy - 1 - hy ? rmax : g.cdy - 1 - hy;
-    rmax = rmax > hz ? rmax : hz;
-    rmax = rmax > g.cdz - 1 - hz ? rmax : g.cdz - 1 - hz;
-    for (int r = 0; r <= rmax; ++r) {
-        if (r > 1 && pc_out(pc_sq(g.cell, pc_gap(0.0f, 4 * (r - 1), 4 * (r - 1) + 1, slack)), l.bound)) break;
-        const int z0 = hz - r < 0 ? 0 : hz - r, z1 = hz + r > g.cdz - 1 ? g.cdz - 1 : hz + r;
-        const int y0 = hy - r < 0 ? 0 : hy - r, y1 = hy + r > g.cdy - 1 ? g.cdy - 1 : hy + r;
-        const int x0 = hx - r < 0 ? 0 : hx - r, x1 = hx + r > g.cdx - 1 ? g.cdx - 1 : hx + r;
-        for (int bz = z0; bz <= z1; ++bz) {
-            const float lz = pc_sq(g.cell, pc_gap(tz, 4 * bz, 4 * bz + 4, slack));
-            if (pc_out(lz, l.bound)) continue;
-            const bool zface = bz - hz == r || hz - bz == r;
-            for (int by = y0; by <= y1; ++by) {
-                const float lyz = pc_add(pc_sq(g.cell, pc_gap(ty, 4 * by, 4 * by + 4, slack)), lz);
-                if (pc_out(lyz, l.bound)) continue;
-                const bool face = zface || by - hy == r || hy - by == r;
-                const int step = face ? 1 : 2 * r;
-                for (int bx = face ? x0 : (hx - r >= 0 ? hx - r : hx + r); bx <= x1; bx += step) {
-                    if (pc_table(w, base + fine + ((long long)bz * g.cdy + by) * g.cdx + bx) <= 0) continue;
-                    if (pc_out(pc_add(pc_sq(g.cell, pc_gap(tx, 4 * bx, 4 * bx + 4, slack)), lyz), l.bound)) continue;
-                    const int cz1 = 4 * bz + 4 < g.dz ? 4 * bz + 4 : g.dz, cy1 = 4 * by + 4 < g.dy ? 4 * by + 4 : g.dy,
-                              cx1 = 4 * bx + 4 < g.dx ? 4 * bx + 4 : g.dx;
-                    for (int cz = 4 * bz; cz < cz1; ++cz) {
-                        const float mz = pc_sq(g.cell, pc_gap(tz, cz, cz + 1, slack));
-                        if (pc_out(mz, l.bound)) continue;
-                        for (int cy = 4 * by; cy < cy1; ++cy) {
-                            const float myz = pc_add(pc_sq(g.cell, pc_gap(ty, cy, cy + 1, slack)), mz);
-                            if (pc_out(myz, l.bound)) continue;
-                            const long long row = base + ((long long)cz * g.dy + cy) * g.dx;
-                            for (int cx = 4 * bx; cx < cx1; ++cx) {
-                                const long long c = row + cx;
-                                const int end = pc_clampi(pc_table(w, c), 0, n);
-                                const int begin = c == base ? 0 : pc_clampi(pc_table(w, c - 1), 0, n);
-                                if (begin >= end) continue;
-                                if (pc_out(pc_add(pc_sq(g.cell, pc_gap(tx, cx, cx + 1, slack)), myz), l.bound)) continue;
-                                for (int p = begin; p < end; ++p) {
-                                    const float4 s = pts[p];
-                                    const float d2 = pc_d2(qx, qy, qz, s.x, s.y, s.z);
-                                    pc_list_offer(l, d2, limit,
-                                                  ((unsigned long long)__float_as_uint(d2) << 32) | (uint32_t)__float_as_int(s.w));
-                                }
-                            }
-                        }
-                    }
-                }
-            }
-        }
     }
 }
 
@@ -623,8 +561,9 @@ static __device__ __forceinline__ int pc_knn_lane(const PcTables& w, const float
     PcList l;
     l.at = list + lane;
     l.lanes = lanes; l.k = k; l.n = 0;
-    l.bound = ((unsigned long long)__float_as_uint(limit) << 32) | 0xffffffffull;
-    pc_knn_search(w, b, Q, qx, qy, qz, limit, l);
+    l.limit = limit;
+    l.root = ((unsigned long long)__float_as_uint(limit) << 32) | 0xffffffffull;
+    l = pc_walk(w, b, Q, qx, qy, qz, l);                      // the n <= k smallest admissible keys, unsorted
     pc_list_sort(l);
     return l.n;
 }
@@ -786,30 +725,6 @@ __global__ __launch_bounds__(kBlock) void pc_normals_kernel(PcTables w, const fl
 // ---------------------------------------------------------------------------------------------------------- the term
 #pragma clang fp contract(fast)
 
-// Sum over the 64 lanes, valid in lane 0, in a fixed order.
-static __device__ __forceinline__ float pc_wave_sum(float v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
-// rho(d2) and its derivative, as scan_fit.hip's ('distance' has derivative 0 at d2 = 0)
-static __device__ __forceinline__ void pc_rho(int rho, float sigma2, float d2, float& value, float& slope)
-{
-    if (rho == TUCH_SCAN_RHO_SQUARED) {
-        value = d2;
-        slope = 1.0f;
-    } else if (rho == TUCH_SCAN_RHO_DISTANCE) {
-        value = __builtin_sqrtf(d2);
-        slope = value > 0.0f ? 0.5f / value : 0.0f;
-    } else {
-        const float q = sigma2 / (sigma2 + d2);
-        value = q * d2;
-        slope = q * q;
-    }
-}
-
 // vertex weights: layout 0 none (ones), 1 [V], 2 [B,V]
 static __device__ __forceinline__ float pc_weight(const float* __restrict__ vw, int layout, int b, int V, int v)
 {
@@ -826,29 +741,11 @@ __global__ __launch_bounds__(kBlock) void pc_fit_kernel(PcTables w, const float*
                                                        float* __restrict__ total, float* __restrict__ grad_verts,
                                                        float* __restrict__ grad_transl)
 {
-    __shared__ float red[kWaves][4];
-    __shared__ float s_wsum;
-    __shared__ float tree[kBlock];
-    __shared__ bool last;
-    const int c = blockIdx.x, b = blockIdx.y, t = threadIdx.x, chunks = gridDim.x;
-    // the normaliser: this body's vertex weights in one fixed order (the same bits in every workgroup of the body)
+    __shared__ FitShared sh;
+    const int c = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
+    // the normaliser: this body's vertex weights
     float wsum = (float)V;
-    if (layout != 0) {
-        float acc = 0.0f;
-        for (int i = t; i < V; i += kBlock) acc += pc_weight(vw, layout, b, V, i);
-        acc = pc_wave_sum(acc);
-        if ((t & 63) == 0) red[t >> 6][0] = acc;
-        __syncthreads();
-        if (t == 0) {
-            float a = red[0][0];
-#pragma unroll
-            for (int j = 1; j < kWaves; ++j) a += red[j][0];
-            s_wsum = a;
-        }
-        __syncthreads();
-        wsum = s_wsum;
-        __syncthreads();                                      // (red is written again below)
-    }
+    if (layout != 0) wsum = fit_body_sum(sh, V, [&](int i) { return pc_weight(vw, layout, b, V, i); });
     const int cloud = pc_clampi((int)w.head[kCtl + (size_t)b * kHead + H_N], 0, Q);
     const int v = c * kBlock + t;
     float s = 0.0f, ex = 0.0f, ey = 0.0f, ez = 0.0f;
@@ -872,70 +769,20 @@ __global__ __launch_bounds__(kBlock) void pc_fit_kernel(PcTables w, const float*
         index_out[o] = idx;
         if (won) {
             float value, slope;
-            pc_rho(rho, sigma2, d2, value, slope);
+            fit_rho(rho, sigma2, d2, value, slope);
             s = wv * value;
             const float g2 = 2.0f * (scale * wv * slope / wsum);
             const float* p = points + ((size_t)b * Q + pc_clampi(idx, 0, Q - 1)) * 3;
             ex = g2 * (qx - p[0]); ey = g2 * (qy - p[1]); ez = g2 * (qz - p[2]);
         } else if (live && has_tau) {
             float value, slope;
-            pc_rho(rho, sigma2, limit, value, slope);
+            fit_rho(rho, sigma2, limit, value, slope);
             s = wv * value;
         }
         float* gv = grad_verts + o * 3;
         gv[0] = ex; gv[1] = ey; gv[2] = ez;
     }
-    float sx = pc_wave_sum(ex), sy = pc_wave_sum(ey), sz = pc_wave_sum(ez);
-    s = pc_wave_sum(s);
-    if ((t & 63) == 0) {
-        float* r = red[t >> 6];
-        r[0] = s; r[1] = sx; r[2] = sy; r[3] = sz;
-    }
-    __syncthreads();
-    if (t < 5) {
-        float acc = wsum;
-        if (t < 4) {
-            acc = red[0][t];
-#pragma unroll
-            for (int j = 1; j < kWaves; ++j) acc += red[j][t];
-        }
-        __hip_atomic_store((gfloat*)partial + ((size_t)b * chunks + c) * kPart + t, acc, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");    // the partial is visible before the ticket is taken
-    }
-    __syncthreads();
-    if (t == 0) {
-        last = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == chunks * B - 1;
-    }
-    __syncthreads();
-    if (!last) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    float mine = 0.0f;
-    for (int idx = t; idx < 4 * B; idx += kBlock) {           // (body, component); the stride keeps a thread on one component
-        const int body = idx >> 2, k = idx & 3;
-        const gfloat* p = (const gfloat*)partial + (size_t)body * chunks * kPart + k;
-        float acc = 0.0f;
-        for (int j = 0; j < chunks; ++j) acc += __hip_atomic_load(p + kPart * j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (k == 0) {
-            const float n = __hip_atomic_load((const gfloat*)partial + (size_t)body * chunks * kPart + 4, __ATOMIC_RELAXED,
-                                              __HIP_MEMORY_SCOPE_AGENT);
-            const float value = n != 0.0f ? scale * (acc / n) : 0.0f;
-            per_body[body] = value;
-            mine += value;
-        } else {
-            grad_transl[3 * body + k - 1] = acc;
-        }
-    }
-    tree[t] = mine;
-    __syncthreads();
-    for (int h = kBlock / 2; h > 0; h >>= 1) {
-        if (t < h) tree[t] += tree[t + h];
-        __syncthreads();
-    }
-    if (t == 0) {
-        total[0] = tree[0];
-        __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    fit_reduce_tail(sh, s, ex, ey, ez, wsum, scale, partial, ticket, B, per_body, total, grad_transl);
 }
 
 bool pc_sizes_ok(int B, int Q, int N)
@@ -999,7 +846,7 @@ extern "C" int tuch_point_cloud_build(const float* points, const int32_t* counts
     const size_t ints = (size_t)B * pc_table_ints(resolution);
     TUCH_REQUIRE((ints + kBlock - 1) / kBlock < (1ull << 31), "tuch_point_cloud_build: tables too large (B=%d resolution=%d)", B,
                  resolution);
-    hipLaunchKernelGGL(pc_clear_kernel, dim3((unsigned)((ints + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, tables, ints);
+    tuch_launch_zero_words(tables, ints, s);
     hipLaunchKernelGGL(pc_header_kernel, dim3(B), dim3(kBlock), 0, s, points, counts, weights, Q, resolution, head);
     const dim3 grid(ceil_div(Q, kBlock), B);
     hipLaunchKernelGGL(pc_file_kernel<false>, grid, dim3(kBlock), 0, s, points, counts, weights, Q, resolution,

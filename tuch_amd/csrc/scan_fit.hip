@@ -3,30 +3,30 @@
 // their total, and the unit gradients w.r.t. vertices, translation and points.
 //
 // Launches: the two of the closest-point search (closest_point.hip; the queries are points - transl, subtracted by the
-// search itself), scan_zero_kernel on the gradient accumulator (a kernel, not a memset: a captured loop then holds kernel
-// nodes only), scan_term_kernel, and in deterministic mode the conversion of the fixed-point sums: 4 or 5.
+// search itself), tuch_launch_zero_words on the gradient accumulator (a kernel, not a memset: a captured loop then holds
+// kernel nodes only), scan_term_kernel, and in deterministic mode tuch_launch_fixed_to_float on the fixed-point sums: 4
+// or 5.
 //
-//   scan_term_kernel   one point per thread, 256 per workgroup.  Every workgroup first adds up its body's weights in one
-//                      fixed order (the normaliser: the same bits in every workgroup of the body, alone or in a batch),
-//                      then g_q = w_q rho'(d2_q) / sum w and r = (p - t) - c with c = sum_k bary_k x_k:
-//                        grad_points = 2 g r,  rows of the winning face's corners += -2 g bary_k r  (64-bit fixed-point
-//                        integer atomics in deterministic mode, float atomics otherwise),  grad_transl = -sum_q 2 g r.
-//                      The per-body sums (loss, normaliser, grad_transl) cross to the workgroup that arrives last by
-//                      mesh_fit.hip's ticket scheme and are added in chunk order there, the total in a fixed tree: no
-//                      float atomics for them in either mode.
+//   scan_term_kernel   one point per thread, 256 per workgroup.  Every workgroup first adds up its body's weights
+//                      (fit_body_sum: the normaliser, the same bits in every workgroup of the body, alone or in a batch),
+//                      then g_q = w_q rho'(d2_q) / sum w (fit_rho) and r = (p - t) - c with c = sum_k bary_k x_k:
+//                        grad_points = 2 g r,  rows of the winning face's corners += -2 g bary_k r  (fit_scatter_corners:
+//                        64-bit fixed-point integer atomics in deterministic mode, float atomics otherwise),
+//                        grad_transl = -sum_q 2 g r.
+//                      The per-body sums (loss, normaliser, grad_transl) cross to the workgroup that arrives last through
+//                      fit_reduce_tail and are added in chunk order there, the total in a fixed tree: no float atomics
+//                      for them in either mode.  What is shared with the other fit terms is in fit_reduce.h; here are
+//                      the loads, the per-point arithmetic and the launcher.
 //
 // A point of weight 0 is not computed from (it may be non-finite); neither is one the search found no face for (a body
 // with non-finite vertices).  A body without weight (counts[b] = 0, or all weights 0) has loss 0 and zero gradient rows.
+#include "fit_reduce.h"
 #include "model.h"
 #include "workspace.h"
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kWaves = kBlock / 64;
-constexpr int kPart = 8;                 // floats per partial: sum w rho, -sum e.xyz, sum w, 3 unused
-
-typedef __attribute__((address_space(1))) float gfloat;
+constexpr int kBlock = kFitBlock;
 
 struct ScanLayout { size_t search, fixed, partial, total; };
 
@@ -38,36 +38,12 @@ ScanLayout scan_layout(const tuch_contact_model* m, int B, int Q, bool oriented)
     l.search = tuch_ws_take(o, oriented ? tuch_closest_point_oriented_workspace_bytes(m, B, Q)
                                         : tuch_closest_point_workspace_bytes(m, B, Q), false);
     l.fixed = tuch_ws_take(o, (size_t)B * m->V * 3 * sizeof(long long));
-    l.partial = tuch_ws_take(o, (size_t)B * ceil_div(Q, kBlock) * kPart * sizeof(float));
+    l.partial = tuch_ws_take(o, (size_t)B * ceil_div(Q, kBlock) * kFitPart * sizeof(float));
     l.total = o;
     return l;
 }
 
 static __device__ __forceinline__ int clamp_index(int i, int n) { return i < 0 ? 0 : (i >= n ? n - 1 : i); }
-
-// Sum over the 64 lanes, valid in lane 0, in a fixed order.
-static __device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
-// rho(d2) and its derivative.  'distance' has derivative 0 at d2 = 0 (vertex_fit's convention: torch.norm's subgradient).
-static __device__ __forceinline__ void scan_rho(int rho, float sigma2, float d2, float& value, float& slope)
-{
-    if (rho == TUCH_SCAN_RHO_SQUARED) {
-        value = d2;
-        slope = 1.0f;
-    } else if (rho == TUCH_SCAN_RHO_DISTANCE) {
-        value = __builtin_sqrtf(d2);
-        slope = value > 0.0f ? 0.5f / value : 0.0f;
-    } else {
-        const float q = sigma2 / (sigma2 + d2);
-        value = q * d2;
-        slope = q * q;
-    }
-}
 
 template <bool kFixed>
 __global__ __launch_bounds__(kBlock) void scan_term_kernel(
@@ -78,34 +54,16 @@ __global__ __launch_bounds__(kBlock) void scan_term_kernel(
     float* __restrict__ grad_points, float* __restrict__ grad_verts, long long* __restrict__ grad_fixed,
     float* __restrict__ grad_transl)
 {
-    __shared__ float red[kWaves][4];
-    __shared__ float s_wsum;
-    __shared__ float tree[kBlock];
-    __shared__ bool last;
-    const int c = blockIdx.x, b = blockIdx.y, t = threadIdx.x, chunks = gridDim.x;
+    __shared__ FitShared sh;
+    const int c = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
     int count = Q;
     if (counts) {
         count = counts[b];
         count = count < 0 ? 0 : (count > Q ? Q : count);
     }
-    // the normaliser: this body's weights in one fixed order
+    // the normaliser: this body's weights
     float wsum = (float)count;
-    if (weights) {
-        float acc = 0.0f;
-        for (int i = t; i < count; i += kBlock) acc += weights[(size_t)b * Q + i];
-        acc = wave_sum(acc);
-        if ((t & 63) == 0) red[t >> 6][0] = acc;
-        __syncthreads();
-        if (t == 0) {
-            float a = red[0][0];
-#pragma unroll
-            for (int j = 1; j < kWaves; ++j) a += red[j][0];
-            s_wsum = a;
-        }
-        __syncthreads();
-        wsum = s_wsum;
-        __syncthreads();                                      // (red is written again below)
-    }
+    if (weights) wsum = fit_body_sum(sh, count, [&](int i) { return weights[(size_t)b * Q + i]; });
     const int q = c * kBlock + t;
     float s = 0.0f, ex = 0.0f, ey = 0.0f, ez = 0.0f;
     if (q < count) {
@@ -114,7 +72,7 @@ __global__ __launch_bounds__(kBlock) void scan_term_kernel(
         const int f = face[o];
         if (w != 0.0f && wsum != 0.0f && f >= 0 && f < F) {
             float value, slope;
-            scan_rho(rho, sigma2, d2[o], value, slope);
+            fit_rho(rho, sigma2, d2[o], value, slope);
             s = w * value;
             const float g2 = 2.0f * (w * slope / wsum);
             const float bw[3] = {bary[o * 3], bary[o * 3 + 1], bary[o * 3 + 2]};
@@ -130,86 +88,14 @@ __global__ __launch_bounds__(kBlock) void scan_term_kernel(
             ex = g2 * ((points[o * 3] - transl[3 * b]) - cx);
             ey = g2 * ((points[o * 3 + 1] - transl[3 * b + 1]) - cy);
             ez = g2 * ((points[o * 3 + 2] - transl[3 * b + 2]) - cz);
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const size_t row = ((size_t)b * V + vi[k]) * 3;
-                if (kFixed) {
-                    fixed_add(grad_fixed + row, -bw[k] * ex);
-                    fixed_add(grad_fixed + row + 1, -bw[k] * ey);
-                    fixed_add(grad_fixed + row + 2, -bw[k] * ez);
-                } else {
-                    atomicAdd(grad_verts + row, -bw[k] * ex);
-                    atomicAdd(grad_verts + row + 1, -bw[k] * ey);
-                    atomicAdd(grad_verts + row + 2, -bw[k] * ez);
-                }
-            }
+            fit_scatter_corners<kFixed>(grad_verts, grad_fixed, (size_t)b * V, vi, bw, ex, ey, ez);
         }
     }
     if (grad_points && q < Q) {
         float* g = grad_points + ((size_t)b * Q + q) * 3;
         g[0] = ex; g[1] = ey; g[2] = ez;
     }
-    float sx = wave_sum(-ex), sy = wave_sum(-ey), sz = wave_sum(-ez);
-    s = wave_sum(s);
-    if ((t & 63) == 0) {
-        float* r = red[t >> 6];
-        r[0] = s; r[1] = sx; r[2] = sy; r[3] = sz;
-    }
-    __syncthreads();
-    if (t < 5) {
-        float acc = wsum;
-        if (t < 4) {
-            acc = red[0][t];
-#pragma unroll
-            for (int j = 1; j < kWaves; ++j) acc += red[j][t];
-        }
-        __hip_atomic_store((gfloat*)partial + ((size_t)b * chunks + c) * kPart + t, acc, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-    }
-    // as vertex_fit_kernel (mesh_fit.hip): wave 0 holds the storing lanes and the lane that takes the ticket; its
-    // write-through stores have left before the ticket is taken, and the partials are read by loads that bypass this
-    // CU's cache
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (t == 0) last = atomicAdd(ticket, 1) == chunks * B - 1;
-    __syncthreads();
-    if (!last) return;
-    float mine = 0.0f;
-    for (int idx = t; idx < 4 * B; idx += kBlock) {           // (body, component); the stride keeps a thread on one component
-        const int body = idx >> 2, k = idx & 3;
-        const gfloat* p = (const gfloat*)partial + (size_t)body * chunks * kPart + k;
-        float acc = 0.0f;
-        for (int j = 0; j < chunks; ++j) acc += __hip_atomic_load(p + kPart * j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (k == 0) {
-            const float n = __hip_atomic_load((const gfloat*)partial + (size_t)body * chunks * kPart + 4, __ATOMIC_RELAXED,
-                                              __HIP_MEMORY_SCOPE_AGENT);
-            const float v = n != 0.0f ? acc / n : 0.0f;
-            per_body[body] = v;
-            mine += v;
-        } else {
-            grad_transl[3 * body + k - 1] = acc;
-        }
-    }
-    tree[t] = mine;
-    __syncthreads();
-    for (int h = kBlock / 2; h > 0; h >>= 1) {
-        if (t < h) tree[t] += tree[t + h];
-        __syncthreads();
-    }
-    if (t == 0) { total[0] = tree[0]; *ticket = 0; }
-}
-
-// n 32-bit words of zeros (the float gradient, or the 64-bit fixed-point sums as pairs of words)
-__global__ __launch_bounds__(kBlock) void scan_zero_kernel(uint32_t* __restrict__ out, size_t n)
-{
-    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i < n) out[i] = 0u;
-}
-
-__global__ __launch_bounds__(kBlock) void scan_fixed_to_float_kernel(const long long* __restrict__ fixed, float* __restrict__ out,
-                                                                    size_t n)
-{
-    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i < n) out[i] = fixed_value(fixed[i]);
+    fit_reduce_tail(sh, s, -ex, -ey, -ez, wsum, 1.0f, partial, ticket, B, per_body, total, grad_transl);
 }
 
 }  // namespace
@@ -260,17 +146,14 @@ static int scan_fit_terms(const char* name, const tuch_contact_model* m, const f
     float* partial = (float*)((char*)workspace + l.partial);
     const bool det = tuch_deterministic() != 0;
     const size_t n = (size_t)B * m->V * 3;
-    const size_t words = det ? 2 * n : n;
-    hipLaunchKernelGGL(scan_zero_kernel, dim3((unsigned)((words + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
-                       det ? (uint32_t*)fixed : (uint32_t*)grad_verts, words);
+    tuch_launch_zero_words(det ? (void*)fixed : (void*)grad_verts, det ? 2 * n : n, s);
     const dim3 grid(ceil_div(Q, kBlock), B);
     const float sigma2 = sigma * sigma;
     if (det) {
         hipLaunchKernelGGL(scan_term_kernel<true>, grid, dim3(kBlock), 0, s, verts, transl, points, counts, weights,
                            (const float*)d2, (const int32_t*)face, (const float*)bary, (const int32_t*)m->faces, B, m->V, m->F,
                            Q, rho, sigma2, partial, ticket, per_body, total, grad_points, (float*)nullptr, fixed, grad_transl);
-        hipLaunchKernelGGL(scan_fixed_to_float_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
-                           (const long long*)fixed, grad_verts, n);
+        tuch_launch_fixed_to_float(fixed, grad_verts, n, s);
     } else {
         hipLaunchKernelGGL(scan_term_kernel<false>, grid, dim3(kBlock), 0, s, verts, transl, points, counts, weights,
                            (const float*)d2, (const int32_t*)face, (const float*)bary, (const int32_t*)m->faces, B, m->V, m->F,

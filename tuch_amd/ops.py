@@ -739,6 +739,22 @@ def fit_weights(weights, num_verts, device) -> FitWeights:
     return build()
 
 
+def _hand_over(ctx, g, num_inputs, expand=None):
+    """backward() of the fit terms (_VertexFit, _ScanFit, _CloudFit): the saved unit gradients (None where one was not
+    asked for), scaled unless the upstream gradient g is the cached unit seed of ops.backward_scalar, then expand(*grads)
+    where the inputs that get one are more than the saved tensors, each cast to its input's dtype (ctx.in_dtypes: the
+    leading inputs); None for every other input, and for all of them when g is None."""
+    if g is None:
+        return (None,) * num_inputs
+    grads = ctx.saved_tensors
+    if not backward_pass.is_unit_seed(g):
+        g = g.reshape(()).to(torch.float32)
+        grads = tuple(None if x is None else x * g for x in grads)
+    if expand is not None:
+        grads = expand(*grads)
+    return tuple(None if x is None else x.to(d) for x, d in zip(grads, ctx.in_dtypes)) + (None,) * (num_inputs - len(grads))
+
+
 class _VertexFit(torch.autograd.Function):
     """The data term of a fit to target meshes in correspondence (tuch/utils/smplxtosmpl_mtp.py:100-101, per body) as ONE
     launch: the bodies' losses, their total and the unit gradients w.r.t. vertices and translation (csrc/mesh_fit.hip:
@@ -768,14 +784,7 @@ class _VertexFit(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, g, _g_per_body):
-        if g is None:
-            return None, None, None, None, None
-        gv, gt = ctx.saved_tensors
-        if not backward_pass.is_unit_seed(g):
-            g = g.reshape(()).to(torch.float32)
-            gv, gt = gv * g, gt * g
-        dv, dt, dg = ctx.in_dtypes
-        return (gv.to(dv), gt.to(dt), (-gv).to(dg) if ctx.needs_input_grad[2] else None, None, None)
+        return _hand_over(ctx, g, 5, lambda gv, gt: (gv, gt, -gv if ctx.needs_input_grad[2] else None))
 
 
 def vertex_fit(verts, transl, target, weights=None):
@@ -1577,6 +1586,15 @@ class _ClosestPoint(torch.autograd.Function):
 SCAN_RHO = {'squared': 0, 'distance': 1, 'gmof': 2}
 
 
+def _rho_of(what, rho, sigma):
+    """(rho, sigma) as the C entry points of scan_fit and cloud_fit take them."""
+    if rho not in SCAN_RHO:
+        raise ValueError('%s: rho must be one of %s, got %r' % (what, sorted(SCAN_RHO), rho))
+    if rho == 'gmof' and not (sigma is not None and float(sigma) > 0.0):
+        raise ValueError("%s: rho='gmof' needs sigma > 0, got %r" % (what, sigma))
+    return SCAN_RHO[rho], float(sigma) if sigma is not None else 0.0
+
+
 class _ScanFit(torch.autograd.Function):
     """ops.scan_fit: the search, the term and the unit gradients in one C call (csrc/scan_fit.hip: tuch_scan_fit_terms).
     `face` [B,Q] int32 is written in place (it may be the hint tensor).  backward() only hands the gradients over (scaled
@@ -1596,21 +1614,18 @@ class _ScanFit(torch.autograd.Function):
         gv = torch.empty_like(v)
         gt = torch.empty(b, 3, dtype=torch.float32, device=dev)
         gp = torch.empty_like(pts) if ctx.needs_input_grad[2] else None
-        if normals is not None:
-            nbytes = L.tuch_scan_fit_oriented_workspace_bytes(model._handle, b, q)
-            ws = _workspace(nbytes, dev)
-            _C.check(L.tuch_scan_fit_terms_oriented(model._handle, _C.ptr(v), _C.ptr(tr), _C.ptr(pts), _C.ptr(normals), cos,
-                                                    _C.ptr(counts), _C.ptr(weights), _C.ptr(hint), b, q, rho, sigma, _C.ptr(d2),
-                                                    _C.ptr(face), _C.ptr(bary), _C.ptr(_ticket(dev)), _C.ptr(per_body),
-                                                    _C.ptr(out), _C.ptr(gv), _C.ptr(gt), _C.ptr(gp), _C.ptr(ws), nbytes,
-                                                    _C.stream()))
-        else:
-            nbytes = L.tuch_scan_fit_workspace_bytes(model._handle, b, q)
-            ws = _workspace(nbytes, dev)
-            _C.check(L.tuch_scan_fit_terms(model._handle, _C.ptr(v), _C.ptr(tr), _C.ptr(pts), _C.ptr(counts), _C.ptr(weights),
-                                           _C.ptr(hint), b, q, rho, sigma, _C.ptr(d2), _C.ptr(face), _C.ptr(bary),
-                                           _C.ptr(_ticket(dev)), _C.ptr(per_body), _C.ptr(out), _C.ptr(gv), _C.ptr(gt),
-                                           _C.ptr(gp), _C.ptr(ws), nbytes, _C.stream()))
+        # the oriented entry point takes (normals, cos) behind the points and is otherwise the plain one
+        oriented = normals is not None
+        sizer, entry = ((L.tuch_scan_fit_oriented_workspace_bytes, L.tuch_scan_fit_terms_oriented) if oriented else
+                        (L.tuch_scan_fit_workspace_bytes, L.tuch_scan_fit_terms))
+        nbytes = sizer(model._handle, b, q)
+        ws = _workspace(nbytes, dev)
+        args = [model._handle, _C.ptr(v), _C.ptr(tr), _C.ptr(pts), _C.ptr(counts), _C.ptr(weights), _C.ptr(hint), b, q, rho,
+                sigma, _C.ptr(d2), _C.ptr(face), _C.ptr(bary), _C.ptr(_ticket(dev)), _C.ptr(per_body), _C.ptr(out), _C.ptr(gv),
+                _C.ptr(gt), _C.ptr(gp), _C.ptr(ws), nbytes, _C.stream()]
+        if oriented:
+            args[4:4] = [_C.ptr(normals), cos]
+        _C.check(entry(*args))
         ctx.num_inputs = 10 if normals is None else 12
         ctx.save_for_backward(gv, gt, gp)
         ctx.in_dtypes = (verts.dtype, transl.dtype, points.dtype)
@@ -1621,14 +1636,7 @@ class _ScanFit(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, g, *_others):
-        if g is None:
-            return (None,) * ctx.num_inputs
-        gv, gt, gp = ctx.saved_tensors
-        if not backward_pass.is_unit_seed(g):
-            g = g.reshape(()).to(torch.float32)
-            gv, gt, gp = gv * g, gt * g, (gp * g if gp is not None else None)
-        dv, dt, dp = ctx.in_dtypes
-        return (gv.to(dv), gt.to(dt), gp.to(dp) if gp is not None else None) + (None,) * (ctx.num_inputs - 3)
+        return _hand_over(ctx, g, ctx.num_inputs)
 
 
 def scan_fit(model: ContactModel, verts, transl, points, counts=None, weights=None, hint=None, rho='distance', sigma=None,
@@ -1648,10 +1656,7 @@ def scan_fit(model: ContactModel, verts, transl, points, counts=None, weights=No
     one (tuch_scan_fit_terms_oriented); normals are not translated and get no gradient.  A real point without an
     admissible face (face = -1) adds 0 to the loss and to every gradient and keeps its weight in the normaliser.  Both or
     neither must be given; with neither the call is the plain one.  There is no host fallback."""
-    if rho not in SCAN_RHO:
-        raise ValueError('scan_fit: rho must be one of %s, got %r' % (sorted(SCAN_RHO), rho))
-    if rho == 'gmof' and not (sigma is not None and float(sigma) > 0.0):
-        raise ValueError("scan_fit: rho='gmof' needs sigma > 0, got %r" % (sigma,))
+    rho, sigma = _rho_of('scan_fit', rho, sigma)
     if verts.dim() != 3 or tuple(verts.shape[1:]) != (model.num_verts, 3):
         raise ValueError('scan_fit: verts must be [B,%d,3], got %s' % (model.num_verts, tuple(verts.shape)))
     b = verts.shape[0]
@@ -1675,8 +1680,7 @@ def scan_fit(model: ContactModel, verts, transl, points, counts=None, weights=No
     hint = _hint_of(hint, points, 'scan_fit')
     face = face_out if face_out is not None else torch.empty(b, q, dtype=torch.int32, device=points.device)
     extra = () if cos is None else (_f32(normals.detach()), cos)
-    total, per_body, d2, bary = _ScanFit.apply(verts, transl, points, model, counts, weights, hint, SCAN_RHO[rho],
-                                               float(sigma) if sigma is not None else 0.0, face, *extra)
+    total, per_body, d2, bary = _ScanFit.apply(verts, transl, points, model, counts, weights, hint, rho, sigma, face, *extra)
     return total, per_body, ClosestPoint(d2, face, bary)
 
 
@@ -1963,14 +1967,7 @@ class _CloudFit(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, g, *_others):
-        if g is None:
-            return (None,) * 11
-        gv, gt = ctx.saved_tensors
-        if not backward_pass.is_unit_seed(g):
-            g = g.reshape(()).to(torch.float32)
-            gv, gt = gv * g, gt * g
-        dv, dt = ctx.in_dtypes
-        return (gv.to(dv), gt.to(dt)) + (None,) * 9
+        return _hand_over(ctx, g, 11)
 
 
 def cloud_fit(cloud: PointCloud, verts, transl, vertex_weights=None, hint=None, rho='distance', sigma=None,
@@ -1986,10 +1983,7 @@ def cloud_fit(cloud: PointCloud, verts, transl, vertex_weights=None, hint=None, 
     There is no host fallback."""
     if not isinstance(cloud, PointCloud):
         raise ValueError('cloud_fit: cloud must be a PointCloud, got %r' % type(cloud).__name__)
-    if rho not in SCAN_RHO:
-        raise ValueError('cloud_fit: rho must be one of %s, got %r' % (sorted(SCAN_RHO), rho))
-    if rho == 'gmof' and not (sigma is not None and float(sigma) > 0.0):
-        raise ValueError("cloud_fit: rho='gmof' needs sigma > 0, got %r" % (sigma,))
+    rho, sigma = _rho_of('cloud_fit', rho, sigma)
     if transl is None or tuple(transl.shape) != (cloud.batch, 3):
         raise ValueError('cloud_fit: transl must be [%d,3], got %s'
                          % (cloud.batch, None if transl is None else tuple(transl.shape)))
@@ -2008,8 +2002,7 @@ def cloud_fit(cloud: PointCloud, verts, transl, vertex_weights=None, hint=None, 
     tau = _tau_of('cloud_fit', max_distance)
     _need_hip('cloud_fit', index_out)
     index = _index_out('cloud_fit', index_out, b, n, verts.device)
-    total, per_body, d2 = _CloudFit.apply(verts, transl, cloud, vw, layout, hint, SCAN_RHO[rho],
-                                          float(sigma) if sigma is not None else 0.0, tau, float(scale), index)
+    total, per_body, d2 = _CloudFit.apply(verts, transl, cloud, vw, layout, hint, rho, sigma, tau, float(scale), index)
     return total, per_body, NearestPoint(d2, index)
 
 
