@@ -606,6 +606,55 @@ int tuch_point_cloud_fit_terms(const void* workspace, size_t workspace_bytes, co
                                float* d2 /* [B,V] */, int32_t* index /* [B,V] */, int* ticket, float* per_body /* [B] */,
                                float* total /* [1] */, float* grad_verts /* [B,V,3] */, float* grad_transl /* [B,3] */,
                                void* scratch, size_t scratch_bytes, void* stream);
+/* The oriented query: tuch_point_cloud_nearest's rule over the ADMISSIBLE valid points.  normals [B,Q,3] belong to the
+ * points, in the caller's order; query_normals [B,N,3] to the queries (neither is translated by shift).  With
+ * c = max_angle_cos in [0, 1), c2 = c c formed once, for a query normal u and a point normal n, every operation rounded
+ * to float32 on its own:
+ *   uu = (ux ux + uy uy) + uz uz,  nn = (nx nx + ny ny) + nz nz,  s = (ux nx + uy ny) + uz nz,
+ *   admissible  <=>  s > 0  and  s s >= c2 (uu nn).
+ * A pair is unconstrained -- admissible -- when uu or nn is 0 or not finite: a missing normal, the zero rows of
+ * tuch_point_cloud_normals among them.  Valid points, q = x + shift, the squared distance, the packed key, max_distance,
+ * query_counts and the no-winner outputs (-1 / +inf) are tuch_point_cloud_nearest's; the winner is the smallest key over
+ * the admissible valid points; a hint seeds the search only if it names a valid, admissible point within the limit.
+ * The outputs equal a float32 brute-force sweep under this rule bit for bit: for any batch, order of queries or points,
+ * resolution and hint content, eager or replayed, with cones or with cones NULL.
+ *   cones: per-block normal cones that let a lane pass by a block of the grid none of whose points is admissible for
+ * its normal (they may only skip, never decide; csrc/point_cloud.hip has the derivation).  A caller-provided buffer of
+ * tuch_point_cloud_cones_bytes(B, resolution) bytes, filled by tuch_point_cloud_build_cones AFTER tuch_point_cloud_build
+ * from the same normals (one launch, capturable) and stale after the next build; NULL: no block is skipped. */
+size_t tuch_point_cloud_cones_bytes(int B, int resolution);
+int tuch_point_cloud_build_cones(const void* workspace, size_t workspace_bytes, const float* normals /* [B,Q,3] */, int B,
+                                 int Q, int resolution, void* cones, size_t cones_bytes, void* stream);
+int tuch_point_cloud_nearest_oriented(const void* workspace, size_t workspace_bytes, const float* points,
+                                      const int32_t* counts, const float* weights, const float* normals /* [B,Q,3] */,
+                                      const float* queries /* [B,N,3] */, const float* query_normals /* [B,N,3] */,
+                                      const float* shift, const int32_t* query_counts, const int32_t* hint,
+                                      float max_distance, float max_angle_cos, const void* cones /* or NULL */,
+                                      size_t cones_bytes, int B, int Q, int N, float* d2, int32_t* index, void* stream);
+/* The oriented term: tuch_point_cloud_fit_terms with the oriented query.  The lane that owns vertex v forms the vertex's
+ * normal itself, from the UNTRANSLATED verts, by tuch_vertex_normals' sequence (faces [F,3], vf_off [V+1], vf_ids [3F]
+ * as there; normalize = 0), so d2 / index have the bits of tuch_point_cloud_nearest_oriented called with
+ * tuch_vertex_normals' raw rows, and the term stays one launch.  The term, a vertex without winner, the fixed-order sums
+ * and the gradients are tuch_point_cloud_fit_terms'; normals only decide the match and get no gradient. */
+int tuch_point_cloud_fit_terms_oriented(const void* workspace, size_t workspace_bytes, const float* points,
+                                        const int32_t* counts, const float* weights, const float* normals /* [B,Q,3] */,
+                                        float max_angle_cos, const int32_t* faces, const int32_t* vf_off,
+                                        const int32_t* vf_ids, int F, const void* cones /* or NULL */, size_t cones_bytes,
+                                        const float* verts, const float* transl, const int32_t* hint, float max_distance,
+                                        int B, int Q, int V, const float* vertex_weights, int vertex_weight_layout, int rho,
+                                        float sigma, float scale, float* d2, int32_t* index, int* ticket, float* per_body,
+                                        float* total, float* grad_verts, float* grad_transl, void* scratch,
+                                        size_t scratch_bytes, void* stream);
+/* Posed vertex normals (csrc/vertex_normals.hip).  vf_off [V+1], vf_ids [3F]: the vertex -> faces lists of
+ * tuch_render_mesh (vertex v is a corner of the faces vf_ids[vf_off[v] .. vf_off[v+1]), ascending).  One fixed float32
+ * sequence, nothing fused: for vertex v, over its faces in that order, m = (b - a) x (c - a) exactly as
+ * tuch_closest_point_oriented forms it, u_v = ((0 + m_1) + m_2) + ... per component: the area-weighted normal,
+ * unnormalised.  normalize != 0: divided by sqrt(uu), uu = (ux ux + uy uy) + uz uz; a zero row where uu is 0 or not
+ * finite.  out [B,V,3], every row written by the lane that owns it: no atomics, the same bits for a vertex alone or in
+ * any batch, eager or replayed; table entries are clamped before they address anything; a body that holds NaN changes
+ * no other body's bits.  No gradients.  One launch; capturable. */
+int tuch_vertex_normals(const float* verts /* [B,V,3] */, const int32_t* faces /* [F,3] */, const int32_t* vf_off,
+                        const int32_t* vf_ids, int B, int V, int F, int normalize, float* out, void* stream);
 /* Host copies of the per-body headers the build wrote: origin_host [B,3], cell_host [B], dims_host [B,3].  Synchronises;
  * for tests and tools (a test can put points exactly on cell walls). */
 int tuch_point_cloud_grid(const void* workspace, int B, int resolution, float* origin_host, float* cell_host,

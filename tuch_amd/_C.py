@@ -139,6 +139,16 @@ _SIGNATURES = {
     'tuch_point_cloud_fit_scratch_bytes': (c_size_t, [c_int, c_int]),
     'tuch_point_cloud_fit_terms': (c_int, [c_void_p, c_size_t] + [c_void_p] * 6 + [c_float, c_int, c_int, c_int, c_void_p, c_int,
                                            c_int, c_float, c_float] + [c_void_p] * 8 + [c_size_t, c_void_p]),
+    'tuch_point_cloud_cones_bytes': (c_size_t, [c_int, c_int]),
+    'tuch_point_cloud_build_cones': (c_int, [c_void_p, c_size_t, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    'tuch_point_cloud_nearest_oriented': (c_int, [c_void_p, c_size_t] + [c_void_p] * 9 + [c_float, c_float, c_void_p, c_size_t,
+                                                  c_int, c_int, c_int] + [c_void_p] * 3),
+    'tuch_point_cloud_fit_terms_oriented': (c_int, [c_void_p, c_size_t] + [c_void_p] * 4 + [c_float] + [c_void_p] * 3
+                                            + [c_int, c_void_p, c_size_t] + [c_void_p] * 3 + [c_float, c_int, c_int, c_int,
+                                                                                           c_void_p, c_int, c_int, c_float,
+                                                                                           c_float] + [c_void_p] * 8
+                                            + [c_size_t, c_void_p]),
+    'tuch_vertex_normals': (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 2),
     'tuch_point_cloud_grid': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'tuch_point_cloud_set_canary': (c_int, [c_int]),
     'tuch_point_cloud_canary_hits': (c_int, [c_void_p, POINTER(c_int), c_int]),

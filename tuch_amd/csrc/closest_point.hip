@@ -97,6 +97,7 @@
 //   The hint.  A hinted lane starts from its hint only if the face is in [0, F), admissible for the lane and at a finite
 // d2; then its key is one the unpruned sweep computes too, and the argument of the hinted start holds.  Any other hint
 // takes the unhinted path.
+#include "face_normal.h"
 #include "fit_reduce.h"
 #include "model.h"
 #include "workspace.h"
@@ -108,11 +109,7 @@ constexpr int kCpTri = 9;                           // floats per staged triangl
 constexpr int kCpBox = 8;                           // floats per box
 constexpr float kCpMargin = 64.0f * 5.9604645e-8f;  // 64 * 2^-24, relative to far(g)
 constexpr float kCpDegenerate = 1e-8f;              // |ab x ac|^2 <= this * |ab|^2 |ac|^2: the triangle is its edges
-constexpr int kCpCone = 8;                          // floats per normal cone
-constexpr float kCpConeMargin = 256.0f * 5.9604645e-8f;   // 256 * 2^-24, absolute, on cosines (file header: the cones)
-constexpr float kCpSaneLo = 1e-30f, kCpSaneHi = 1e30f;    // |m|^2 of a face inside: its square root and unit normal are sound
-constexpr float kCpNormalLo = 1e-20f, kCpNormalHi = 1e20f; // |n|^2 inside: |A x n|^2 neither overflows nor underflows
-constexpr float kCpPairLo = 1e-24f, kCpPairHi = 1e24f;    // |m|^2 |n|^2 inside: no under- or overflow that matters in the rule
+// (kCpCone, kCpConeMargin and the sane ranges kCpSane*, kCpNormal*, kCpPair* of the cones: face_normal.h)
 constexpr unsigned long long kCpNoKey = 0x7f800000ffffffffull;     // d2 = +inf, face = -1
 
 struct CpLayout { size_t boxes, tris, cones, total; };
@@ -218,16 +215,7 @@ static __device__ __forceinline__ void cp_box(float px, float py, float pz, cons
     far = cp_dot(fx, fy, fz, fx, fy, fz);
 }
 
-// The face normal of the admissibility rule: m = (b - a) x (c - a), one subtraction per component, each component of the
-// product as (x y) - (z w), every operation rounded to float32 on its own (contraction is off here).
-static __device__ __forceinline__ void cp_face_normal(const float* __restrict__ t, float& mx, float& my, float& mz)
-{
-    const float e1x = t[3] - t[0], e1y = t[4] - t[1], e1z = t[5] - t[2];
-    const float e2x = t[6] - t[0], e2y = t[7] - t[1], e2z = t[8] - t[2];
-    mx = (e1y * e2z) - (e1z * e2y);
-    my = (e1z * e2x) - (e1x * e2z);
-    mz = (e1x * e2y) - (e1y * e2x);
-}
+// (cp_face_normal, the face normal of the admissibility rule, is in face_normal.h: the vertex normals sum it too)
 
 static __device__ __forceinline__ float cp_sq3(float x, float y, float z) { return (x * x + y * y) + z * z; }
 
@@ -243,23 +231,8 @@ static __device__ __forceinline__ bool cp_admissible(const float* __restrict__ t
 }
 #pragma clang fp contract(fast)
 
-// A group's normal cone against one lane's normal n with inv = 1 / |n|: 0 mixed, 1 wholly admissible, 2 wholly
-// inadmissible (file header: the cones).  cone = axis.xyz, cos beta, sin beta, usable (> 0), the smallest and the
-// largest |m|^2 of the group's faces
-static __device__ __forceinline__ int cp_cone_class(const float* __restrict__ cone, float nx, float ny, float nz, float inv, float c)
-{
-    const float ax = cone[0], ay = cone[1], az = cone[2], cb = cone[3], sb = cone[4];
-    const float ca = (ax * nx + ay * ny + az * nz) * inv;
-    const float wx = ay * nz - az * ny, wy = az * nx - ax * nz, wz = ax * ny - ay * nx;
-    const float sa = __builtin_sqrtf(wx * wx + wy * wy + wz * wz) * inv;
-    const float sum = ca * cb - sa * sb;            // cos(alpha + beta)
-    const float dif = ca * cb + sa * sb;            // cos(alpha - beta)
-    int cls = 0;
-    if (ca > 0.0f && cb > 0.0f && sum >= c + kCpConeMargin) cls = 1;
-    if (ca < cb - kCpConeMargin && dif <= c - kCpConeMargin) cls = 2;
-    const float nn = nx * nx + ny * ny + nz * nz;
-    return cone[5] > 0.0f && cone[6] * nn >= kCpPairLo && cone[7] * nn <= kCpPairHi ? cls : 0;
-}
+// (cp_cone_class, a cone against one lane's normal, is in face_normal.h with its constants: the point cloud's block
+// cones are classified by the same function)
 
 // what a lane of the oriented search knows of its normal: n and nn as the rule takes them, 1 / |n| for the cones
 struct CpNormal {

@@ -95,6 +95,46 @@
 // fences, and its argument) and are added in chunk order, the total in a fixed tree: no float atomics, the same bits in
 // either mode of tuch_set_deterministic and for a body alone or in a batch.  The normaliser is fit_body_sum, rho is fit_rho.  A vertex of weight 0 is not computed from; one without winner contributes rho(tau^2) when tau is given and
 // the cloud is not empty, else 0, with a zero gradient row; a body with an empty cloud or without weight has loss 0.
+//
+// The oriented query (tuch_point_cloud_nearest_oriented / _fit_terms_oriented / _build_cones; PcOriented,
+// pc_query_oriented, pc_cones_kernel).  Points carry normals n (caller's order, never filed), a query a normal u.
+// pc_admissible is THE admissibility of a pair, stated in include/tuch_amd.h: with uu = |u|^2, nn = |n|^2, s = u . n,
+// every operation rounded to float32 on its own,  admissible <=> s > 0 and s s >= c2 (uu nn),  c2 = c c; a pair whose
+// uu or nn is 0 or not finite is unconstrained.  It is a function of the pair's bits and c alone, so the admissible set
+// of a query never depends on cell, lane, batch or order, and the winner -- the smallest key over the admissible valid
+// points, pc_d2 and the key untouched -- is the full sweep's whatever is pruned conservatively.  The walk is pc_walk
+// with PcOriented as its sink: a candidate is asked the rule only when it would otherwise become the best (d2 <= limit
+// and key < best), so the bound is always the key of an admissible point (or the limit) and every argument of the
+// pruning margin above holds unchanged.  A hint seeds the bound only if it names a valid, admissible point within the
+// limit: then its key is one the sweep computes too.
+//   What it costs.  A lane whose admissible match is far away, or that has none, finds the key above every nearer
+// inadmissible point and gathers that point's normal (12 bytes at a random place) to refuse it; such lanes are a sixth
+// to a half of a body's vertices on a scan that sees one side.  The cones below take whole blocks off that path;
+// DESIGN.md section 3 has the measured times, which say that they are not enough.
+//   The cones.  pc_cones_kernel stores per (body, 4^3-cell block) closest_point.hip's cone record (face_normal.h) over
+// the normals of the points filed in the block: an axis A (the normalised mean of the unit normals n / |n|), cos beta
+// and sin beta of the normal that makes the largest angle beta with A, the smallest and largest nn, and a flag: usable
+// only if the block holds a point, every point's nn is in [kCpSaneLo, kCpSaneHi] -- so a block that holds ANY
+// unconstrained point (a zero or non-finite row) is never usable, never skipped -- and the mean has a direction.
+// Nothing in it depends on the queries.  With alpha the angle between A and u, every normal of the block makes an angle
+// of at least alpha - beta with u; cp_cone_class (the one function the face groups use) says "wholly inadmissible"
+//     if  cos alpha < cos beta - kCpConeMargin  (alpha > beta)  and  cos(alpha - beta) <= c - kCpConeMargin
+// (0 < alpha - beta <= 180 deg, where the cosine is monotone: alpha - beta > max_angle, no normal of the block is within
+// max_angle of u), and only for a lane with kCpNormalLo <= uu <= kCpNormalHi and kCpPairLo <= uu nn <= kCpPairHi for the
+// block's extreme nn; any other lane skips nothing.  The margin is closest_point.hip's, its derivation carries over
+// term by term with (m, n) read as (n, u): the rule is the same sequence of operations on a pair of vectors (there m is
+// computed, here n is given, which only removes an error source), so it decides "cos angle(n, u) >= c" with the
+// threshold moved by less than 8 u; A, n / |n| and u / |u| are unit vectors to 3 u each, cos alpha, sin alpha, cos beta,
+// sin beta (cross products, not sqrt(1 - cos^2)) within 10 u, cos(alpha - beta) within 43 u: 51 u against the margin's
+// 256 u.  (The axis is a MEAN, so its squared length is at most 1 however many points a block holds; which axis is
+// taken affects how often a block is skipped, never whether skipping is right: beta is measured against the axis
+// actually stored.)  A skipped block holds no admissible point for the lane, so no key of the admissible set is lost:
+// the cones only skip, they never decide, and the bits are those of the call with cones NULL.  The buffer starts with
+// a header (the resolution the cones were built at): a lane uses them only if that is the cloud's resolution and its
+// body's records lie inside the buffer.  They are stale after the next build.
+//   The oriented term (pc_fit_oriented_kernel, pc_fit_body<true>): the lane that owns vertex v forms u_v itself from the UNTRANSLATED verts by
+// vn_vertex_normal (face_normal.h; tuch_vertex_normals' raw row), then the oriented query; the epilogue is shared.
+#include "face_normal.h"
 #include "fit_reduce.h"
 #include "workspace.h"
 #include <math.h>
@@ -365,6 +405,53 @@ struct PcBest {
     {
         best = d2 <= limit && key < best ? key : best;         // (a select, not a branch around a store: the innermost loop)
     }
+    __device__ __forceinline__ bool skip_block(long long) const { return false; }
+};
+
+// THE admissibility of a (query normal u, point normal n) pair (file header: the oriented query): every operation
+// rounded on its own.  uu is the caller's (ux ux + uy uy) + uz uz, positive and finite; a point whose nn is 0 or not
+// finite has no normal and is admissible.
+static __device__ __forceinline__ bool pc_admissible(float ux, float uy, float uz, float uu, float nx, float ny, float nz,
+                                                     float c2)
+{
+    const float nn = pc_add(pc_add(pc_mul(nx, nx), pc_mul(ny, ny)), pc_mul(nz, nz));
+    if (!(nn > 0.0f && __builtin_isfinite(nn))) return true;
+    const float s = pc_add(pc_add(pc_mul(ux, nx), pc_mul(uy, ny)), pc_mul(uz, nz));
+    return s > 0.0f && pc_mul(s, s) >= pc_mul(c2, pc_mul(uu, nn));
+}
+
+// The sink of the oriented one-key query: PcBest with the pair rule asked of a candidate that would otherwise become
+// the best -- rare once the key has settled, so the gather from the caller-order normals stays out of the innermost
+// loop's common path -- and with the block cones (file header).  normals: the body's [Q][3]; cones: the body's records
+// or nullptr (none, or this lane may not use them).
+struct PcOriented {
+    unsigned long long best;
+    float limit;
+    const float* normals;
+    int Q;
+    float ux, uy, uz, uu, c2;
+    bool constrained;            // uu is positive and finite: the rule applies (otherwise every point is admissible)
+    const float* cones;
+    long long cone_cap;
+    float inv, c;                // 1 / |u| and the cosine, for the cones
+    __device__ __forceinline__ unsigned long long bound() const { return best; }
+    __device__ __forceinline__ bool admits(int index) const
+    {
+        if (!constrained) return true;
+        const float* n = normals + (size_t)pc_clampi(index, 0, Q - 1) * 3;
+        return pc_admissible(ux, uy, uz, uu, n[0], n[1], n[2], c2);
+    }
+    __device__ __forceinline__ void offer(float d2, unsigned long long key)
+    {
+        if (d2 <= limit && key < best && admits((int)(uint32_t)key)) best = key;
+    }
+    // may the lane pass block `block` of its body by?  Only a usable cone that is wholly inadmissible for u says so.
+    __device__ __forceinline__ bool skip_block(long long block) const
+    {
+        if (!cones) return false;
+        const long long at = block < 0 ? 0 : (block >= cone_cap ? cone_cap - 1 : block);
+        return cp_cone_class(cones + (size_t)at * kCpCone, ux, uy, uz, inv, c) == 2;
+    }
 };
 
 // THE walk of the grid, for the finite query (qx, qy, qz) against the cloud of body b: the rings, gaps, slack and 2^-20
@@ -411,6 +498,7 @@ static __device__ Sink pc_walk(const PcTables& w, int b, int Q, float qx, float 
                     if (pc_table(w, base + fine + ((long long)bz * g.cdy + by) * g.cdx + bx) <= 0) continue;
                     // (the sum's order differs from a cell's below; both are bounds of their own)
                     if (pc_out(pc_add(pc_sq(g.cell, pc_gap(tx, 4 * bx, 4 * bx + 4, slack)), lyz), sink.bound())) continue;
+                    if (sink.skip_block(((long long)bz * g.cdy + by) * g.cdx + bx)) continue;    // (the oriented sink's cones)
                     const int cz1 = 4 * bz + 4 < g.dz ? 4 * bz + 4 : g.dz, cy1 = 4 * by + 4 < g.dy ? 4 * by + 4 : g.dy,
                               cx1 = 4 * bx + 4 < g.dx ? 4 * bx + 4 : g.dx;
                     for (int cz = 4 * bz; cz < cz1; ++cz) {
@@ -484,6 +572,169 @@ __global__ __launch_bounds__(kBlock) void pc_nearest_kernel(PcTables w, const fl
     index_out[o] = won ? (int32_t)(uint32_t)best : -1;
 }
 
+// -------------------------------------------------------------------------------------------------- the oriented query
+// what the oriented kernels know of the cloud's normals
+struct PcOrient {
+    const float* normals;        // [B][Q][3], the caller's order
+    const uint32_t* cones;       // kCpCone header words ([0]: the resolution they were built at), then the records; or nullptr
+    long long cone_cap;          // records behind the header
+    float c, c2;                 // the cosine and its square
+};
+
+// The whole oriented query of one lane: pc_query with the query's normal u.  A hint seeds the key only if it names a
+// valid, admissible point within the limit.  The cones serve a lane only if they were built at the cloud's resolution,
+// lie wholly inside the buffer for its body, and uu is in the sane range (file header).
+static __device__ __forceinline__ unsigned long long pc_query_oriented(const PcTables& w, const PcOrient& o,
+                                                                       const float* __restrict__ points,
+                                                                       const int32_t* __restrict__ counts,
+                                                                       const float* __restrict__ weights, int b, int Q,
+                                                                       float qx, float qy, float qz, float ux, float uy,
+                                                                       float uz, int hint, float limit)
+{
+    PcOriented sink;
+    sink.best = ((unsigned long long)__float_as_uint(limit) << 32) | 0xffffffffull;
+    sink.limit = limit;
+    if (!pc_finite3(qx, qy, qz)) return sink.best;
+    sink.normals = o.normals + (size_t)b * Q * 3;
+    sink.Q = Q;
+    sink.ux = ux; sink.uy = uy; sink.uz = uz;
+    sink.uu = pc_add(pc_add(pc_mul(ux, ux), pc_mul(uy, uy)), pc_mul(uz, uz));
+    sink.c2 = o.c2; sink.c = o.c;
+    sink.constrained = sink.uu > 0.0f && __builtin_isfinite(sink.uu);
+    sink.cones = nullptr; sink.cone_cap = 1; sink.inv = 0.0f;
+    if (o.cones && sink.constrained && sink.uu >= kCpNormalLo && sink.uu <= kCpNormalHi) {
+        const int res = pc_clampi((int)w.head[kCtl + (size_t)b * kHead + H_RES], 1, kMaxRes), cres = (res + 3) >> 2;
+        const long long stride = (long long)cres * cres * cres;
+        if ((int)o.cones[0] == res && (b + 1) * stride <= o.cone_cap) {
+            sink.cones = (const float*)(o.cones + kCpCone) + (size_t)b * stride * kCpCone;
+            sink.cone_cap = stride;
+            sink.inv = 1.0f / __builtin_sqrtf(sink.uu);
+        }
+    }
+    float sx, sy, sz;
+    if (hint >= 0 && hint < Q && pc_valid(points, counts, weights, b, Q, hint, sx, sy, sz)) {
+        const float d2 = pc_d2(qx, qy, qz, sx, sy, sz);
+        if (d2 <= limit && sink.admits(hint)) sink.best = ((unsigned long long)__float_as_uint(d2) << 32) | (uint32_t)hint;
+    }
+    return pc_walk(w, b, Q, qx, qy, qz, sink).best;
+}
+
+__global__ __launch_bounds__(kBlock) void pc_nearest_oriented_kernel(PcTables w, PcOrient orient,
+                                                                    const float* __restrict__ points,
+                                                                    const int32_t* __restrict__ counts,
+                                                                    const float* __restrict__ weights,
+                                                                    const float* __restrict__ queries,
+                                                                    const float* __restrict__ query_normals,
+                                                                    const float* __restrict__ shift,
+                                                                    const int32_t* __restrict__ query_counts,
+                                                                    const int32_t* hint, float limit, int Q, int N,
+                                                                    float* __restrict__ d2_out, int32_t* index_out)
+{
+    const int b = blockIdx.y, i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= N) return;
+    const size_t o = (size_t)b * N + i;
+    int count = N;
+    if (query_counts) count = pc_clampi(query_counts[b], 0, N);
+    unsigned long long best = kPcNoKey;
+    if (i < count) {
+        const int h = hint ? hint[o] : -1;
+        float qx = queries[o * 3], qy = queries[o * 3 + 1], qz = queries[o * 3 + 2];
+        if (shift) {
+            qx = pc_add(qx, shift[3 * b]); qy = pc_add(qy, shift[3 * b + 1]); qz = pc_add(qz, shift[3 * b + 2]);
+        }
+        best = pc_query_oriented(w, orient, points, counts, weights, b, Q, qx, qy, qz, query_normals[o * 3],
+                                 query_normals[o * 3 + 1], query_normals[o * 3 + 2], h, limit);
+    }
+    const bool won = (uint32_t)best != 0xffffffffu;
+    d2_out[o] = won ? __uint_as_float((uint32_t)(best >> 32)) : __builtin_inff();
+    index_out[o] = won ? (int32_t)(uint32_t)best : -1;
+}
+
+// The cone of one 4^3-cell block of one body (file header: the cones): one wavefront per block, its lanes striding over
+// the block's points row by row (the four cells of a block's row are contiguous in the filed order).  The record is
+// closest_point.hip's: axis (the normalised mean of the unit normals), cos beta and sin beta of the normal farthest from
+// it, usable, the smallest and the largest nn.  Not usable -- never skipped -- when the block is empty, holds a point
+// whose nn is outside [kCpSaneLo, kCpSaneHi] (zero rows, the "unknown" normals, and non-finite ones among them), or
+// the mean has no direction.  Lane 0 of block 0 of body 0 writes the header.
+__global__ __launch_bounds__(64) void pc_cones_kernel(PcTables w, const float* __restrict__ normals, int Q, int R,
+                                                     uint32_t* __restrict__ cones)
+{
+    const int b = blockIdx.y, blk = blockIdx.x, lane = threadIdx.x;
+    const int cres = (R + 3) >> 2;
+    const long long stride = (long long)cres * cres * cres;
+    if (b == 0 && blk == 0 && lane < kCpCone) cones[lane] = lane == 0 ? (uint32_t)R : 0u;
+    float* rec = (float*)(cones + kCpCone) + ((size_t)b * stride + blk) * kCpCone;
+    const PcGrid g = pc_grid(w.head, b);
+    const int n = pc_clampi(g.n, 0, Q);
+    const long long fine = (long long)g.res * g.res * g.res;
+    const long long base = (long long)b * (fine + stride);
+    const bool live = g.res == R && blk < g.cdx * g.cdy * g.cdz;
+    const int count = live ? pc_clampi(pc_table(w, base + fine + blk), 0, n) : 0;
+    if (count <= 0) {
+        if (lane < kCpCone) rec[lane] = 0.0f;
+        return;
+    }
+    const int bx = blk % g.cdx, by = (blk / g.cdx) % g.cdy, bz = blk / (g.cdx * g.cdy);
+    const float4* pts = w.sorted + (size_t)b * Q;
+    const float* body = normals + (size_t)b * Q * 3;
+    const float inf = __builtin_inff();
+    float ax = 0.0f, ay = 0.0f, az = 0.0f, cb = 2.0f, sb = 0.0f, lo = inf, hi = 0.0f;
+    bool sane = true;
+    for (int pass = 0; pass < 2; ++pass) {
+        float sx = 0.0f, sy = 0.0f, sz = 0.0f;
+        for (int row = 0; row < 16; ++row) {
+            const int cz = 4 * bz + (row >> 2), cy = 4 * by + (row & 3);
+            if (cz >= g.dz || cy >= g.dy) continue;
+            const long long first = base + ((long long)cz * g.dy + cy) * g.dx + 4 * bx;
+            const int cx1 = 4 * bx + 4 < g.dx ? 4 * bx + 4 : g.dx;
+            const int begin = first == base ? 0 : pc_clampi(pc_table(w, first - 1), 0, n);
+            const int end = pc_clampi(pc_table(w, first + (cx1 - 4 * bx) - 1), 0, n);
+            for (int p = begin + lane; p < end; p += 64) {
+                const float* nm = body + (size_t)pc_clampi(__float_as_int(pts[p].w), 0, Q - 1) * 3;
+                const float nx = nm[0], ny = nm[1], nz = nm[2];
+                const float nn = (nx * nx + ny * ny) + nz * nz;
+                const bool ok = nn >= kCpSaneLo && nn <= kCpSaneHi;
+                const float inv = ok ? 1.0f / __builtin_sqrtf(nn) : 0.0f;
+                const float hx = nx * inv, hy = ny * inv, hz = nz * inv;
+                if (pass == 0) {
+                    sane = sane && ok;
+                    sx += hx; sy += hy; sz += hz;
+                    lo = __builtin_fminf(lo, ok ? nn : 0.0f); hi = __builtin_fmaxf(hi, ok ? nn : inf);
+                } else {
+                    const float wx = ay * hz - az * hy, wy = az * hx - ax * hz, wz = ax * hy - ay * hx;
+                    const float ca = (ax * hx + ay * hy) + az * hz;
+                    if (ca < cb) { cb = ca; sb = __builtin_sqrtf((wx * wx + wy * wy) + wz * wz); }
+                }
+            }
+        }
+        if (pass == 0) {
+            for (int d = 32; d > 0; d >>= 1) {
+                sx += __shfl_xor(sx, d, 64); sy += __shfl_xor(sy, d, 64); sz += __shfl_xor(sz, d, 64);
+                lo = __builtin_fminf(lo, __shfl_xor(lo, d, 64)); hi = __builtin_fmaxf(hi, __shfl_xor(hi, d, 64));
+            }
+            sx = __shfl(sx, 0, 64) / (float)count; sy = __shfl(sy, 0, 64) / (float)count; sz = __shfl(sz, 0, 64) / (float)count;
+            const float len2 = (sx * sx + sy * sy) + sz * sz;
+            const bool usable = __ballot(!sane) == 0ull && len2 >= 1e-6f && len2 <= 4.0f;
+            if (!usable) {                                       // (uniform: every lane holds the same sums)
+                if (lane < kCpCone) rec[lane] = 0.0f;
+                return;
+            }
+            const float il = 1.0f / __builtin_sqrtf(len2);
+            ax = sx * il; ay = sy * il; az = sz * il;
+        }
+    }
+    float least = cb;
+    for (int d = 32; d > 0; d >>= 1) least = __builtin_fminf(least, __shfl_xor(least, d, 64));
+    least = __shfl(least, 0, 64);
+    const unsigned long long who = __ballot(cb == least);
+    const float sine = __shfl(sb, who ? __ffsll((long long)who) - 1 : 0, 64);
+    if (lane == 0) {
+        rec[0] = ax; rec[1] = ay; rec[2] = az; rec[3] = least; rec[4] = sine;
+        rec[5] = least <= 1.5f ? 1.0f : 0.0f;                    // (no lane saw a point: the tables disagree, not usable)
+        rec[6] = lo; rec[7] = hi;
+    }
+}
+
 // ------------------------------------------------------------------------------------------- k nearest points, normals
 // A lane's list: k keys in LDS, slot j of lane t at list[j * lanes + t] (the lanes of a wavefront are contiguous, so
 // every ds_read_b64 / ds_write_b64 is free of bank conflicts, whatever slot each lane is at: a row of slots is a multiple
@@ -497,6 +748,7 @@ struct PcList {
     unsigned long long root;
     __device__ __forceinline__ unsigned long long bound() const { return root; }
     __device__ __forceinline__ void offer(float d2, unsigned long long key);
+    __device__ __forceinline__ bool skip_block(long long) const { return false; }
 };
 
 // v into slot i of the max-heap of the first n slots: the larger child moves up until v is no smaller than both
@@ -731,17 +983,28 @@ static __device__ __forceinline__ float pc_weight(const float* __restrict__ vw, 
     return layout == 0 ? 1.0f : vw[(layout == 2 ? (size_t)b * V : (size_t)0) + v];
 }
 
-__global__ __launch_bounds__(kBlock) void pc_fit_kernel(PcTables w, const float* __restrict__ points,
-                                                       const int32_t* __restrict__ counts, const float* __restrict__ weights,
-                                                       const float* __restrict__ verts, const float* __restrict__ transl,
-                                                       const int32_t* hint, float limit, int has_tau, int B, int Q, int V,
-                                                       const float* __restrict__ vw, int layout, int rho, float sigma2,
-                                                       float scale, float* __restrict__ d2_out, int32_t* index_out,
-                                                       float* partial, int* ticket, float* __restrict__ per_body,
-                                                       float* __restrict__ total, float* __restrict__ grad_verts,
-                                                       float* __restrict__ grad_transl)
+// the mesh of the oriented term: the lane that owns a vertex forms its normal itself (face_normal.h: vn_vertex_normal)
+struct PcMesh {
+    const int32_t* faces;        // [F][3]
+    const int32_t* vf_off;       // [V + 1]
+    const int32_t* vf_ids;       // [3 F]
+    int F;
+};
+
+// The term, for both kernels.  kOriented: the query is the oriented one, with the raw vertex normal of the UNTRANSLATED
+// verts (tuch_vertex_normals' row, normalize = 0); nothing else differs.
+template <bool kOriented>
+static __device__ __forceinline__ void pc_fit_body(FitShared& sh, const PcTables& w, const PcOrient& orient,
+                                                   const PcMesh& mesh, const float* __restrict__ points,
+                                                   const int32_t* __restrict__ counts, const float* __restrict__ weights,
+                                                   const float* __restrict__ verts, const float* __restrict__ transl,
+                                                   const int32_t* hint, float limit, int has_tau, int B, int Q, int V,
+                                                   const float* __restrict__ vw, int layout, int rho, float sigma2,
+                                                   float scale, float* __restrict__ d2_out, int32_t* index_out,
+                                                   float* partial, int* ticket, float* __restrict__ per_body,
+                                                   float* __restrict__ total, float* __restrict__ grad_verts,
+                                                   float* __restrict__ grad_transl)
 {
-    __shared__ FitShared sh;
     const int c = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
     // the normaliser: this body's vertex weights
     float wsum = (float)V;
@@ -760,7 +1023,13 @@ __global__ __launch_bounds__(kBlock) void pc_fit_kernel(PcTables w, const float*
             qx = pc_add(verts[o * 3], transl[3 * b]);
             qy = pc_add(verts[o * 3 + 1], transl[3 * b + 1]);
             qz = pc_add(verts[o * 3 + 2], transl[3 * b + 2]);
-            best = pc_query(w, points, counts, weights, b, Q, qx, qy, qz, h, limit);
+            if (kOriented) {
+                float ux, uy, uz;
+                vn_vertex_normal(verts + (size_t)b * V * 3, mesh.faces, mesh.vf_off, mesh.vf_ids, V, mesh.F, v, ux, uy, uz);
+                best = pc_query_oriented(w, orient, points, counts, weights, b, Q, qx, qy, qz, ux, uy, uz, h, limit);
+            } else {
+                best = pc_query(w, points, counts, weights, b, Q, qx, qy, qz, h, limit);
+            }
         }
         const bool won = (uint32_t)best != 0xffffffffu;
         const float d2 = won ? __uint_as_float((uint32_t)(best >> 32)) : __builtin_inff();
@@ -783,6 +1052,36 @@ __global__ __launch_bounds__(kBlock) void pc_fit_kernel(PcTables w, const float*
         gv[0] = ex; gv[1] = ey; gv[2] = ez;
     }
     fit_reduce_tail(sh, s, ex, ey, ez, wsum, scale, partial, ticket, B, per_body, total, grad_transl);
+}
+__global__ __launch_bounds__(kBlock) void pc_fit_kernel(PcTables w, const float* __restrict__ points,
+                                                       const int32_t* __restrict__ counts, const float* __restrict__ weights,
+                                                       const float* __restrict__ verts, const float* __restrict__ transl,
+                                                       const int32_t* hint, float limit, int has_tau, int B, int Q, int V,
+                                                       const float* __restrict__ vw, int layout, int rho, float sigma2,
+                                                       float scale, float* __restrict__ d2_out, int32_t* index_out,
+                                                       float* partial, int* ticket, float* __restrict__ per_body,
+                                                       float* __restrict__ total, float* __restrict__ grad_verts,
+                                                       float* __restrict__ grad_transl)
+{
+    __shared__ FitShared sh;
+    pc_fit_body<false>(sh, w, PcOrient{}, PcMesh{}, points, counts, weights, verts, transl, hint, limit, has_tau, B, Q, V, vw, layout,
+                       rho, sigma2, scale, d2_out, index_out, partial, ticket, per_body, total, grad_verts, grad_transl);
+}
+
+__global__ __launch_bounds__(kBlock) void pc_fit_oriented_kernel(PcTables w, PcOrient orient, PcMesh mesh,
+                                                       const float* __restrict__ points,
+                                                       const int32_t* __restrict__ counts, const float* __restrict__ weights,
+                                                       const float* __restrict__ verts, const float* __restrict__ transl,
+                                                       const int32_t* hint, float limit, int has_tau, int B, int Q, int V,
+                                                       const float* __restrict__ vw, int layout, int rho, float sigma2,
+                                                       float scale, float* __restrict__ d2_out, int32_t* index_out,
+                                                       float* partial, int* ticket, float* __restrict__ per_body,
+                                                       float* __restrict__ total, float* __restrict__ grad_verts,
+                                                       float* __restrict__ grad_transl)
+{
+    __shared__ FitShared sh;
+    pc_fit_body<true>(sh, w, orient, mesh, points, counts, weights, verts, transl, hint, limit, has_tau, B, Q, V, vw, layout,
+                      rho, sigma2, scale, d2_out, index_out, partial, ticket, per_body, total, grad_verts, grad_transl);
 }
 
 bool pc_sizes_ok(int B, int Q, int N)
@@ -977,6 +1276,125 @@ extern "C" int tuch_point_cloud_fit_terms(const void* workspace, size_t workspac
                        sigma * sigma, scale, d2, index, (float*)((char*)scratch + sl.partial), ticket, per_body, total,
                        grad_verts, grad_transl);
     return tuch_check_launch("tuch_point_cloud_fit_terms");
+}
+
+// ------------------------------------------------------------------------------------------ the oriented entry points
+namespace {
+
+size_t pc_cone_words(int B, int R)
+{
+    const size_t c = (size_t)((R + 3) >> 2);
+    return (size_t)kCpCone + (size_t)B * c * c * c * kCpCone;
+}
+
+// what the oriented launches take; cones NULL: none
+PcOrient pc_orient(const float* normals, float max_angle_cos, const void* cones, size_t cones_bytes)
+{
+    PcOrient o;
+    o.normals = normals;
+    o.cones = (const uint32_t*)cones;
+    o.cone_cap = cones && cones_bytes >= 2 * kCpCone * sizeof(float) ? (long long)(cones_bytes / (kCpCone * sizeof(float))) - 1 : 0;
+    if (o.cone_cap == 0) o.cones = nullptr;
+    o.c = fminf(fmaxf(max_angle_cos, 0.0f), 1.0f);
+    o.c2 = o.c * o.c;
+    return o;
+}
+
+}  // namespace
+
+extern "C" size_t tuch_point_cloud_cones_bytes(int B, int resolution)
+{
+    if (B <= 0 || resolution <= 0 || resolution > kMaxRes) return 0;
+    return pc_cone_words(B, resolution) * sizeof(float);
+}
+
+extern "C" int tuch_point_cloud_build_cones(const void* workspace, size_t workspace_bytes, const float* normals, int B, int Q,
+                                            int resolution, void* cones, size_t cones_bytes, void* stream)
+{
+    TUCH_REQUIRE(workspace && normals && cones, "tuch_point_cloud_build_cones: null pointer");
+    TUCH_REQUIRE(pc_sizes_ok(B, Q, 1) && resolution > 0 && resolution <= kMaxRes,
+                 "tuch_point_cloud_build_cones: bad sizes B=%d Q=%d resolution=%d (1 .. %d)", B, Q, resolution, kMaxRes);
+    tuch_ws_scope scope(g_pc_canary != 0);
+    const size_t need = pc_layout(B, Q, resolution).total, cone_need = tuch_point_cloud_cones_bytes(B, resolution);
+    if (workspace_bytes < need || cones_bytes < cone_need) {
+        tuch_set_error("tuch_point_cloud_build_cones: workspace %zu < %zu or cones %zu < %zu bytes", workspace_bytes, need,
+                       cones_bytes, cone_need);
+        return TUCH_ERR_WORKSPACE;
+    }
+    const int cres = (resolution + 3) >> 2;
+    hipLaunchKernelGGL(pc_cones_kernel, dim3(cres * cres * cres, B), dim3(64), 0, (hipStream_t)stream,
+                       pc_tables((void*)workspace, workspace_bytes, B, Q), normals, Q, resolution, (uint32_t*)cones);
+    return tuch_check_launch("tuch_point_cloud_build_cones");
+}
+
+extern "C" int tuch_point_cloud_nearest_oriented(const void* workspace, size_t workspace_bytes, const float* points,
+                                                 const int32_t* counts, const float* weights, const float* normals,
+                                                 const float* queries, const float* query_normals, const float* shift,
+                                                 const int32_t* query_counts, const int32_t* hint, float max_distance,
+                                                 float max_angle_cos, const void* cones, size_t cones_bytes, int B, int Q,
+                                                 int N, float* d2, int32_t* index, void* stream)
+{
+    TUCH_REQUIRE(workspace && points && normals && queries && query_normals && d2 && index,
+                 "tuch_point_cloud_nearest_oriented: null pointer");
+    TUCH_REQUIRE(pc_sizes_ok(B, Q, N), "tuch_point_cloud_nearest_oriented: bad sizes B=%d Q=%d N=%d", B, Q, N);
+    TUCH_REQUIRE(max_angle_cos >= 0.0f && max_angle_cos < 1.0f, "tuch_point_cloud_nearest_oriented: max_angle_cos %g (in [0, 1))",
+                 (double)max_angle_cos);
+    tuch_ws_scope scope(g_pc_canary != 0);
+    const size_t need = pc_layout(B, Q, 1).total;
+    if (workspace_bytes < need) {
+        tuch_set_error("tuch_point_cloud_nearest_oriented: workspace %zu < %zu bytes", workspace_bytes, need);
+        return TUCH_ERR_WORKSPACE;
+    }
+    const float limit = max_distance > 0.0f ? fminf(max_distance * max_distance, kPcMaxD2) : kPcMaxD2;
+    hipLaunchKernelGGL(pc_nearest_oriented_kernel, dim3(ceil_div(N, kBlock), B), dim3(kBlock), 0, (hipStream_t)stream,
+                       pc_tables((void*)workspace, workspace_bytes, B, Q), pc_orient(normals, max_angle_cos, cones, cones_bytes),
+                       points, counts, weights, queries, query_normals, shift, query_counts, hint, limit, Q, N, d2, index);
+    return tuch_check_launch("tuch_point_cloud_nearest_oriented");
+}
+
+extern "C" int tuch_point_cloud_fit_terms_oriented(const void* workspace, size_t workspace_bytes, const float* points,
+                                                   const int32_t* counts, const float* weights, const float* normals,
+                                                   float max_angle_cos, const int32_t* faces, const int32_t* vf_off,
+                                                   const int32_t* vf_ids, int F, const void* cones, size_t cones_bytes,
+                                                   const float* verts, const float* transl, const int32_t* hint,
+                                                   float max_distance, int B, int Q, int V, const float* vertex_weights,
+                                                   int vertex_weight_layout, int rho, float sigma, float scale, float* d2,
+                                                   int32_t* index, int* ticket, float* per_body, float* total,
+                                                   float* grad_verts, float* grad_transl, void* scratch, size_t scratch_bytes,
+                                                   void* stream)
+{
+    TUCH_REQUIRE(workspace && points && normals && faces && vf_off && vf_ids && verts && transl && d2 && index && ticket &&
+                     per_body && total && grad_verts && grad_transl && scratch,
+                 "tuch_point_cloud_fit_terms_oriented: null pointer");
+    TUCH_REQUIRE(pc_sizes_ok(B, Q, V) && F > 0 && (long long)F * 3 < (1ll << 31),
+                 "tuch_point_cloud_fit_terms_oriented: bad sizes B=%d Q=%d V=%d F=%d", B, Q, V, F);
+    TUCH_REQUIRE(max_angle_cos >= 0.0f && max_angle_cos < 1.0f,
+                 "tuch_point_cloud_fit_terms_oriented: max_angle_cos %g (in [0, 1))", (double)max_angle_cos);
+    TUCH_REQUIRE(vertex_weight_layout >= 0 && vertex_weight_layout <= 2 && (vertex_weight_layout == 0 || vertex_weights),
+                 "tuch_point_cloud_fit_terms_oriented: vertex weight layout %d (0 none, 1 [V], 2 [B,V]) with weights %p",
+                 vertex_weight_layout, (const void*)vertex_weights);
+    TUCH_REQUIRE(rho == TUCH_SCAN_RHO_SQUARED || rho == TUCH_SCAN_RHO_DISTANCE || (rho == TUCH_SCAN_RHO_GMOF && sigma > 0.0f),
+                 "tuch_point_cloud_fit_terms_oriented: rho %d (0 squared, 1 distance, 2 gmof with sigma > 0; sigma = %g)", rho,
+                 (double)sigma);
+    tuch_ws_scope scope(g_pc_canary != 0);
+    const size_t need = pc_layout(B, Q, 1).total;
+    const PcScratch sl = scope.record(0, [&] { return pc_scratch(B, V); });
+    if (workspace_bytes < need || scratch_bytes < sl.total) {
+        tuch_set_error("tuch_point_cloud_fit_terms_oriented: workspace %zu < %zu or scratch %zu < %zu bytes", workspace_bytes,
+                       need, scratch_bytes, sl.total);
+        return TUCH_ERR_WORKSPACE;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const PcTables w = pc_tables((void*)workspace, workspace_bytes, B, Q);
+    scope.arm(scratch, (int32_t*)w.head, s);
+    const float limit = max_distance > 0.0f ? fminf(max_distance * max_distance, kPcMaxD2) : kPcMaxD2;
+    const PcMesh mesh = {faces, vf_off, vf_ids, F};
+    hipLaunchKernelGGL(pc_fit_oriented_kernel, dim3(ceil_div(V, kBlock), B), dim3(kBlock), 0, s, w,
+                       pc_orient(normals, max_angle_cos, cones, cones_bytes), mesh, points, counts, weights, verts, transl,
+                       hint, limit, max_distance > 0.0f ? 1 : 0, B, Q, V, vertex_weights, vertex_weight_layout, rho,
+                       sigma * sigma, scale, d2, index, (float*)((char*)scratch + sl.partial), ticket, per_body, total,
+                       grad_verts, grad_transl);
+    return tuch_check_launch("tuch_point_cloud_fit_terms_oriented");
 }
 
 extern "C" int tuch_point_cloud_grid(const void* workspace, int B, int resolution, float* origin_host, float* cell_host,

@@ -325,6 +325,51 @@ def vertex_face_table(faces, num_verts: int) -> Tuple[np.ndarray, np.ndarray]:
     return off.astype(np.int32), np.ascontiguousarray(face[order], dtype=np.int32)
 
 
+class VertexNormalTable(NamedTuple):
+    """What tuch_vertex_normals and the oriented cloud term read of a mesh: int32 device tensors faces [F,3] and the
+    vertex -> faces lists (off [V+1], ids [3F]) of vertex_face_table."""
+    faces: torch.Tensor
+    off: torch.Tensor
+    ids: torch.Tensor
+
+
+def vertex_normal_table(faces, num_verts: int, device) -> VertexNormalTable:
+    """faces [F,3] (array or tensor) -> the VertexNormalTable of the mesh on ``device``."""
+    faces = faces.detach().cpu().numpy() if torch.is_tensor(faces) else np.asarray(faces)
+    off, ids = vertex_face_table(faces, num_verts)
+    up = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32), device=device)
+    return VertexNormalTable(up(faces), up(off), up(ids))
+
+
+def _check_normal_table(what, table, num_verts, device):
+    if not isinstance(table, VertexNormalTable):
+        raise ValueError('%s: the table must be a VertexNormalTable (ops.vertex_normal_table), got %r'
+                         % (what, type(table).__name__))
+    if table.off.numel() != num_verts + 1 or table.ids.numel() != 3 * table.faces.shape[0]:
+        raise ValueError('%s: the table is for %d vertices and %d faces (%d entries), the vertices are %d'
+                         % (what, table.off.numel() - 1, table.faces.shape[0], table.ids.numel(), num_verts))
+    if table.faces.device != device:
+        raise RuntimeError('%s: the table is on %s, the vertices on %s' % (what, table.faces.device, device))
+
+
+def vertex_normals(verts: torch.Tensor, table: VertexNormalTable, normalize: bool = False) -> torch.Tensor:
+    """Posed vertex normals [B,V,3] (tuch_vertex_normals; the rule is in include/tuch_amd.h): the sum of the normals
+    (b - a) x (c - a) of every vertex's faces in ascending face order -- the area-weighted normal -- as one fixed
+    float32 sequence; ``normalize`` makes them unit vectors, with a zero row where the sum is 0 or not finite.  The same
+    bits for a vertex alone or in any batch.  No gradients; there is no host fallback."""
+    if verts.dim() != 3 or verts.shape[2] != 3 or verts.shape[0] == 0 or verts.shape[1] == 0:
+        raise ValueError('vertex_normals: verts must be [B,V,3] with B, V > 0, got %s' % (tuple(verts.shape),))
+    _need_hip('vertex_normals', verts)
+    _check_normal_table('vertex_normals', table, verts.shape[1], verts.device)
+    v = _f32(verts.detach())
+    b, n, _ = v.shape
+    out = torch.empty_like(v)
+    with torch.cuda.device(v.device):
+        _C.check(_C.lib().tuch_vertex_normals(_C.ptr(v), _C.ptr(table.faces), _C.ptr(table.off), _C.ptr(table.ids), b, n,
+                                              int(table.faces.shape[0]), int(bool(normalize)), _C.ptr(out), _C.stream()))
+    return out
+
+
 def render_mesh(verts: torch.Tensor, faces_i32: torch.Tensor, vface, cam_t: torch.Tensor, view_rot: torch.Tensor,
                 focal: float, cx: float, cy: float, height: int, width: int, colors: Optional[torch.Tensor] = None,
                 background: Optional[torch.Tensor] = None, background_views: int = 0) -> dict:
@@ -1728,14 +1773,22 @@ class _CloudNearest(torch.autograd.Function):
     use cloud_fit, whose gradients come out of the kernel)."""
 
     @staticmethod
-    def forward(ctx, queries, shift, cloud, counts, hint, tau, index):
+    def forward(ctx, queries, shift, cloud, counts, hint, tau, index, query_normals=None, cos=None):
         qs = _f32(queries)
         sh = None if shift is None else _f32(shift)
         b, n, _ = qs.shape
         d2 = torch.empty(b, n, dtype=torch.float32, device=qs.device)
-        _C.check(_C.lib().tuch_point_cloud_nearest(
-            _C.ptr(cloud._ws), cloud._nbytes, _C.ptr(cloud.points), _C.ptr(cloud.counts), _C.ptr(cloud.weights), _C.ptr(qs),
-            _C.ptr(sh), _C.ptr(counts), _C.ptr(hint), tau, b, cloud.num_points, n, _C.ptr(d2), _C.ptr(index), _C.stream()))
+        if query_normals is not None:              # the oriented query: the same call with the normals, the cosine, the cones
+            _C.check(_C.lib().tuch_point_cloud_nearest_oriented(
+                _C.ptr(cloud._ws), cloud._nbytes, _C.ptr(cloud.points), _C.ptr(cloud.counts), _C.ptr(cloud.weights),
+                _C.ptr(cloud.point_normals), _C.ptr(qs), _C.ptr(query_normals), _C.ptr(sh), _C.ptr(counts), _C.ptr(hint), tau,
+                cos, _C.ptr(cloud._cones), cloud._cones_bytes(), b, cloud.num_points, n, _C.ptr(d2), _C.ptr(index),
+                _C.stream()))
+        else:
+            _C.check(_C.lib().tuch_point_cloud_nearest(
+                _C.ptr(cloud._ws), cloud._nbytes, _C.ptr(cloud.points), _C.ptr(cloud.counts), _C.ptr(cloud.weights),
+                _C.ptr(qs), _C.ptr(sh), _C.ptr(counts), _C.ptr(hint), tau, b, cloud.num_points, n, _C.ptr(d2), _C.ptr(index),
+                _C.stream()))
         ctx.save_for_backward(qs, sh, index)
         ctx.cloud_points = cloud.points
         ctx.in_dtypes = (queries.dtype, None if shift is None else shift.dtype)
@@ -1752,7 +1805,8 @@ class _CloudNearest(torch.autograd.Function):
         gq = torch.where(won[:, :, None], 2.0 * g.to(torch.float32)[:, :, None] * (q - s), zero)
         dq, ds = ctx.in_dtypes
         return (gq.to(dq) if ctx.needs_input_grad[0] else None,
-                gq.sum(1).to(ds) if sh is not None and ctx.needs_input_grad[1] else None, None, None, None, None, None)
+                gq.sum(1).to(ds) if sh is not None and ctx.needs_input_grad[1] else None) + (None,) * (
+                    len(ctx.needs_input_grad) - 2)
 
 
 class PointCloud:
@@ -1790,10 +1844,48 @@ class PointCloud:
             self._ws = torch.zeros(max(int(nbytes), 1), dtype=torch.uint8, device=points.device)
             self._nbytes = nbytes
         self.batch, self.num_points = b, q
+        # a rebuild leaves the cloud unoriented (the cones would be stale): call orient() again; the cone buffer is kept
+        self.point_normals = None
+        self._cones = None
         with torch.cuda.device(points.device):
             _C.check(L.tuch_point_cloud_build(_C.ptr(self.points), _C.ptr(self.counts), _C.ptr(self.weights), b, q,
                                               self.resolution, _C.ptr(self._ws), nbytes, _C.stream()))
         return self
+
+    def orient(self, normals, cones=True):
+        """Give the cloud its points' normals [B,Q,3], in the points' order (kept by reference like the points; zero or
+        non-finite rows mean "unknown"), for ``nearest(query_normals=, max_angle=)`` and ``cloud_fit(max_angle=)``.
+        ``cones``: also build the per-block normal cones that let a query pass by blocks of the grid without an
+        admissible point (tuch_point_cloud_build_cones, one launch, capturable; they change no bit of any result).
+        ``rebuild()`` drops both: call ``orient`` again after it."""
+        if not torch.is_tensor(normals) or tuple(normals.shape) != (self.batch, self.num_points, 3):
+            raise ValueError('PointCloud.orient: normals must be [%d,%d,3], got %s'
+                             % (self.batch, self.num_points, tuple(normals.shape) if torch.is_tensor(normals) else type(normals)))
+        _need_hip('PointCloud.orient', normals)
+        if normals.device != self.points.device:
+            raise RuntimeError('PointCloud.orient: normals on %s, the cloud on %s' % (normals.device, self.points.device))
+        self.point_normals = _f32(normals.detach())
+        self._cones = None
+        if cones:
+            L = _C.lib()
+            nbytes = int(L.tuch_point_cloud_cones_bytes(self.batch, self.resolution))
+            buf = getattr(self, '_cone_buffer', None)
+            if buf is None or buf.numel() != nbytes or buf.device != self.points.device:
+                buf = self._cone_buffer = torch.zeros(nbytes, dtype=torch.uint8, device=self.points.device)
+            with torch.cuda.device(self.points.device):
+                _C.check(L.tuch_point_cloud_build_cones(_C.ptr(self._ws), self._nbytes, _C.ptr(self.point_normals), self.batch,
+                                                        self.num_points, self.resolution, _C.ptr(buf), nbytes, _C.stream()))
+            self._cones = buf
+        return self
+
+    def _cones_bytes(self) -> int:
+        return 0 if self._cones is None else int(self._cones.numel())
+
+    def _oriented_cos(self, what, max_angle) -> float:
+        """The float32 cosine the oriented C entry points take (as _max_angle_cos); the cloud must be oriented."""
+        if self.point_normals is None:
+            raise ValueError('%s: max_angle needs an oriented cloud (PointCloud.orient; rebuild() drops the normals)' % what)
+        return _max_angle_cos(self.point_normals, max_angle, self.points, what)
 
     def _check_queries(self, what, queries, shift, hint, name='queries'):
         if queries.dim() != 3 or queries.shape[0] != self.batch or queries.shape[2] != 3 or queries.shape[1] == 0:
@@ -1807,21 +1899,37 @@ class PointCloud:
                                  or not hint.is_contiguous()):
             raise ValueError('%s: hint must be a contiguous int32 %s tensor' % (what, tuple(queries.shape[:2])))
 
-    def nearest(self, queries, shift=None, counts=None, hint=None, max_distance=None, index_out=None) -> NearestPoint:
+    def nearest(self, queries, shift=None, counts=None, hint=None, max_distance=None, index_out=None, query_normals=None,
+                max_angle=None) -> NearestPoint:
         """For every real query ``queries[b,n] + shift[b]`` the nearest valid point of body b's cloud:
         ``NearestPoint(d2 [B,N], index [B,N] int32)``; no winner: index -1, d2 +inf.  counts [B]: real queries per body;
         hint [B,N] int32: a guess per query that changes no bit of any result (it may be ``index_out``, the tensor the
         indices are written to); max_distance tau > 0: only points with d2 <= f32(tau)^2 can win.  d2 is differentiable
-        w.r.t. queries and shift with the index held fixed."""
-        self._check_queries('PointCloud.nearest', queries, shift, hint)
+        w.r.t. queries and shift with the index held fixed.
+        query_normals [B,N,3] with max_angle in degrees, in (0, 90], on an oriented cloud (``orient``): the nearest valid
+        point whose normal is within the angle of the query's (tuch_point_cloud_nearest_oriented; a query or a point
+        whose normal is a zero or non-finite row is unconstrained; normals are not shifted and get no gradient).  Both
+        or neither must be given; with neither the call is the plain one."""
+        what = 'PointCloud.nearest'
+        self._check_queries(what, queries, shift, hint)
         b, n = queries.shape[0], queries.shape[1]
         if counts is not None and tuple(counts.shape) != (b,):
             raise ValueError('PointCloud.nearest: counts must be [%d], got %s' % (b, tuple(counts.shape)))
-        tau = _tau_of('PointCloud.nearest', max_distance)
-        _need_hip('PointCloud.nearest', counts, index_out)
-        index = _index_out('PointCloud.nearest', index_out, b, n, queries.device)
+        tau = _tau_of(what, max_distance)
+        _need_hip(what, counts, index_out)
+        extra = ()
+        if query_normals is not None or max_angle is not None:
+            if query_normals is None or max_angle is None:
+                raise ValueError('%s: query_normals and max_angle go together' % what)
+            if not torch.is_tensor(query_normals) or tuple(query_normals.shape) != (b, n, 3):
+                raise ValueError('%s: query_normals must be [%d,%d,3], got %s'
+                                 % (what, b, n, tuple(query_normals.shape) if torch.is_tensor(query_normals) else
+                                    type(query_normals)))
+            _need_hip(what, query_normals)
+            extra = (_f32(query_normals.detach()), self._oriented_cos(what, max_angle))
+        index = _index_out(what, index_out, b, n, queries.device)
         counts = None if counts is None else counts.to(torch.int32).contiguous()
-        d2 = _CloudNearest.apply(queries, shift, self, counts, hint, tau, index)
+        d2 = _CloudNearest.apply(queries, shift, self, counts, hint, tau, index, *extra)
         return NearestPoint(d2, index)
 
     def _knn_args(self, what, queries, k, shift, counts, max_distance):
@@ -1941,7 +2049,7 @@ class _CloudFit(torch.autograd.Function):
     _ScanFit's."""
 
     @staticmethod
-    def forward(ctx, verts, transl, cloud, vw, layout, hint, rho, sigma, tau, scale, index):
+    def forward(ctx, verts, transl, cloud, vw, layout, hint, rho, sigma, tau, scale, index, cos=None, table=None):
         v, tr = _f32(verts), _f32(transl)
         b, n, _ = v.shape
         dev = v.device
@@ -1953,11 +2061,18 @@ class _CloudFit(torch.autograd.Function):
         gt = torch.empty(b, 3, dtype=torch.float32, device=dev)
         nbytes = L.tuch_point_cloud_fit_scratch_bytes(b, n)
         scratch = _workspace(nbytes, dev)
-        _C.check(L.tuch_point_cloud_fit_terms(
-            _C.ptr(cloud._ws), cloud._nbytes, _C.ptr(cloud.points), _C.ptr(cloud.counts), _C.ptr(cloud.weights), _C.ptr(v),
-            _C.ptr(tr), _C.ptr(hint), tau, b, cloud.num_points, n, _C.ptr(vw), layout, rho, sigma, scale, _C.ptr(d2),
-            _C.ptr(index), _C.ptr(_ticket(dev)), _C.ptr(per_body), _C.ptr(out), _C.ptr(gv), _C.ptr(gt), _C.ptr(scratch),
-            nbytes, _C.stream()))
+        args = [_C.ptr(cloud._ws), cloud._nbytes, _C.ptr(cloud.points), _C.ptr(cloud.counts), _C.ptr(cloud.weights), _C.ptr(v),
+                _C.ptr(tr), _C.ptr(hint), tau, b, cloud.num_points, n, _C.ptr(vw), layout, rho, sigma, scale, _C.ptr(d2),
+                _C.ptr(index), _C.ptr(_ticket(dev)), _C.ptr(per_body), _C.ptr(out), _C.ptr(gv), _C.ptr(gt), _C.ptr(scratch),
+                nbytes, _C.stream()]
+        entry = L.tuch_point_cloud_fit_terms
+        if cos is not None:
+            # the oriented entry point takes the normals, the cosine, the mesh and the cones behind the cloud's triple
+            args[5:5] = [_C.ptr(cloud.point_normals), cos, _C.ptr(table.faces), _C.ptr(table.off), _C.ptr(table.ids),
+                         int(table.faces.shape[0]), _C.ptr(cloud._cones), cloud._cones_bytes()]
+            entry = L.tuch_point_cloud_fit_terms_oriented
+        _C.check(entry(*args))
+        ctx.num_inputs = 11 if cos is None else 13
         ctx.save_for_backward(gv, gt)
         ctx.in_dtypes = (verts.dtype, transl.dtype)
         ctx.mark_non_differentiable(per_body, d2)
@@ -1967,11 +2082,11 @@ class _CloudFit(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, g, *_others):
-        return _hand_over(ctx, g, 11)
+        return _hand_over(ctx, g, ctx.num_inputs)
 
 
 def cloud_fit(cloud: PointCloud, verts, transl, vertex_weights=None, hint=None, rho='distance', sigma=None,
-              max_distance=None, scale=1.0, index_out=None):
+              max_distance=None, scale=1.0, index_out=None, max_angle=None, normal_table=None):
     """Model -> scan data term of a two-sided fit: ``(total, per_body, NearestPoint)``.  The queries are ``verts[b,v] +
     transl[b]`` against ``cloud``; the NearestPoint has the bits of ``cloud.nearest(verts, transl, hint=hint,
     max_distance=max_distance)`` (a vertex of weight 0 is not computed from: -1 / +inf).  per_body[b] = scale sum_v w_v
@@ -1980,6 +2095,12 @@ def cloud_fit(cloud: PointCloud, verts, transl, vertex_weights=None, hint=None, 
     their sum over the bodies, differentiable w.r.t. verts and transl with the nearest point held fixed (there is no
     gradient w.r.t. the cloud's points: they are data).  Every sum is fixed-order: the same bits on every call, in
     either mode of ``deterministic()``, for a body alone or in a batch.  hint / index_out as in ``PointCloud.nearest``.
+    max_angle (degrees, in (0, 90]) with normal_table (``vertex_normal_table`` of the mesh the vertices belong to), on an
+    oriented cloud: a vertex is matched only to points whose normal is within the angle of the vertex's own
+    (tuch_point_cloud_fit_terms_oriented, still one launch: the kernel forms the posed vertex normals itself).  The
+    NearestPoint then has the bits of ``cloud.nearest(verts, transl, ..., query_normals=vertex_normals(verts,
+    normal_table), max_angle=max_angle)``; a vertex without an admissible point is one without winner (index -1).
+    Normals only decide the match: they get no gradient.  Both or neither must be given.
     There is no host fallback."""
     if not isinstance(cloud, PointCloud):
         raise ValueError('cloud_fit: cloud must be a PointCloud, got %r' % type(cloud).__name__)
@@ -2002,7 +2123,13 @@ def cloud_fit(cloud: PointCloud, verts, transl, vertex_weights=None, hint=None, 
     tau = _tau_of('cloud_fit', max_distance)
     _need_hip('cloud_fit', index_out)
     index = _index_out('cloud_fit', index_out, b, n, verts.device)
-    total, per_body, d2 = _CloudFit.apply(verts, transl, cloud, vw, layout, hint, rho, sigma, tau, float(scale), index)
+    extra = ()
+    if max_angle is not None or normal_table is not None:
+        if max_angle is None or normal_table is None:
+            raise ValueError('cloud_fit: max_angle and normal_table go together')
+        _check_normal_table('cloud_fit', normal_table, n, verts.device)
+        extra = (cloud._oriented_cos('cloud_fit', max_angle), normal_table)
+    total, per_body, d2 = _CloudFit.apply(verts, transl, cloud, vw, layout, hint, rho, sigma, tau, float(scale), index, *extra)
     return total, per_body, NearestPoint(d2, index)
 
 
