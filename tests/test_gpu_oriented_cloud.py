@@ -404,6 +404,48 @@ def test_equal_bits_twice_alone_and_in_both_modes():
     assert int(ops._ticket(torch.device(DEV)).item()) == 0
 
 
+def test_unconstrained_oriented_calls_have_the_plain_calls_bits():
+    """There is one query path: with all-zero query normals (nearest) or all-zero point normals (the term) every pair is
+    unconstrained and the oriented entry points return the plain ones' tensors, torch.equal.  Batch 2, 257 points with
+    ragged counts, 257 queries, resolution 8: several 4^3 blocks, a partial last workgroup, a wavefront boundary.  (That
+    the reference agrees is tests/test_oriented_cloud_host.py's.)"""
+    from tuch_amd import ops
+    c = oc.cloud_case('body122', 2, 257, 257, ('true',))
+    counts = np.array([257, 130], np.int32)
+    queries, shift, zeros = _dev(c['queries']), _dev(c['shift']), torch.zeros(2, 257, 3, device=DEV)
+    for cones in (True, False):
+        cloud = _cloud(c['points'], c['normals'], counts, None, 8, cones)
+        assert (cloud._cones is not None) == cones
+        answers = cloud.nearest(queries, shift).index
+        assert (answers >= 0).all()
+        for hint in (None, answers):
+            for tau in (None, 0.03):
+                plain = cloud.nearest(queries, shift, hint=hint, max_distance=tau)
+                got = cloud.nearest(queries, shift, hint=hint, max_distance=tau, query_normals=zeros, max_angle=60.0)
+                assert torch.equal(got.d2, plain.d2) and torch.equal(got.index, plain.index), (cones, hint is None, tau)
+                if tau is not None:                              # the limit is exercised
+                    assert (plain.index < 0).any() and (plain.index >= 0).any()
+    t = oc.term_case('body122', 'gmof', 'BV', True)
+    cloud = _cloud(t['points'], np.zeros_like(t['normals']), t['counts'], t['weights'])
+    table = ops.vertex_normal_table(t['faces'], t['verts'].shape[1], DEV)
+    for mode in (True, False):
+        for tau in (None, t['tau']):
+            with ops.deterministic_mode(mode):
+                out = []
+                for extra in ({}, dict(max_angle=60.0, normal_table=table)):
+                    v, tr = _dev(t['verts'], requires_grad=True), _dev(t['transl'], requires_grad=True)
+                    total, per, near = ops.cloud_fit(cloud, v, tr, _dev(t['vw']), None, t['rho'], t['sigma'], tau, t['scale'],
+                                                     **extra)
+                    ops.backward_scalar(total)
+                    out.append(dict(total=total.detach(), per_body=per, d2=near.d2, index=near.index, grad_verts=v.grad,
+                                    grad_transl=tr.grad))
+            for key in out[0]:
+                assert torch.equal(out[0][key], out[1][key]), (key, mode, tau)
+            assert (out[0]['index'] >= 0).any() and out[0]['grad_verts'].abs().sum() > 0
+            if tau is not None:
+                assert (out[0]['index'] < 0).any()
+
+
 def test_term_workspace_guards_and_capture():
     from tuch_amd import ops
     c = oc.term_case('body122', 'distance', 'V', True)

@@ -94,6 +94,16 @@ def test_brute_force_without_normals_is_the_unoriented_sweep():
     assert np.array_equal(got[0].view(np.uint32), want[0].view(np.uint32)) and np.array_equal(got[1], want[1])
     away = oc.brute_force_batch(c['queries'], c['query_normals'], c['points'], c['normals'], oc.cos32(60.0), shift=c['shift'])
     assert (away[1] != want[1]).any() and (away[0] >= want[0]).all()
+    # the case of the device's one-path test (tests/test_gpu_oriented_cloud.py): an unconstrained oriented call, by zero
+    # query normals or by zero point normals, is the plain call in the reference alone
+    c = oc.cloud_case('body122', 2, 257, 257, ('true',))
+    counts = np.array([257, 130], np.int32)
+    for tau in (None, 0.03):
+        want = cf.brute_force_batch(c['queries'], c['points'], counts, shift=c['shift'], tau=tau)
+        for qn, pn in ((np.zeros_like(c['query_normals']), c['normals']), (c['query_normals'], np.zeros_like(c['normals']))):
+            got = oc.brute_force_batch(c['queries'], qn, c['points'], pn, oc.cos32(60.0), counts, shift=c['shift'], tau=tau)
+            assert np.array_equal(got[0].view(np.uint32), want[0].view(np.uint32)) and np.array_equal(got[1], want[1])
+        assert (want[1] >= 0).any() and ((want[1] < 0).any() if tau else (want[1] >= 0).all())
 
 
 def test_what_it_is_for_on_the_cpu():

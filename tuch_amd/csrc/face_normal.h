@@ -1,6 +1,6 @@
 // The face normal of the admissibility rules and the vertex normal summed from it: one copy of each fixed float32
 // sequence for cp_admissible and the cones (closest_point.hip), vertex_normals_kernel (vertex_normals.hip) and
-// pc_fit_oriented_kernel (point_cloud.hip).  Contraction is switched off inside each body, so the sequences are the same
+// pc_fit_kernel<true> (point_cloud.hip).  Contraction is switched off inside each body, so the sequences are the same
 // whatever mode the including file is in.
 #pragma once
 #include "common.h"

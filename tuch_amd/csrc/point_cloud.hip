@@ -28,12 +28,24 @@
 //                      ends as the END of its cell: cell c is [table[c - 1], table[c]), cell 0 starts at 0).  The order
 //                      inside a cell depends on atomic arrival; by the key rule no output depends on it.
 //
-// The query (pc_walk, ONE body of code for the one-key and the k-key query: what follows, and the margin below, is about
-// it): one query per lane, 64 consecutive queries of one body per wavefront.  A lane walks the blocks in Chebyshev rings
-// around the block of its own (clamped) cell; a block is opened when it holds points and its bound admits it, then each
-// of its cells likewise, then pc_d2 on the cell's points, which go to the lane's sink.  The walk ends after ring r when
-// the ring bound (below) exceeds the sink's bound -- the lane's key (PcBest) or its k-th key (PcList) -- or when the grid
-// is exhausted.
+// The query.  There is ONE of each piece, and a form of the query is a choice of sink:
+//   pc_walk<Sink>       the walk of the grid (what follows, and the margin below, is about it): one query per lane, 64
+//                       consecutive queries of one body per wavefront.  A lane walks the blocks in Chebyshev rings
+//                       around the block of its own (clamped) cell; a block is opened when it holds points, its bound
+//                       admits it and the sink does not pass it by, then each of its cells likewise, then pc_d2 on the
+//                       cell's points, which go to the lane's sink.  The walk ends after ring r when the ring bound
+//                       (below) exceeds the sink's bound, or when the grid is exhausted.
+//   PcBest              the sink of the plain one-key query: the lane's key and the limit
+//   PcOriented          the sink of the oriented one-key query: PcBest that asks a candidate the pair rule (below)
+//   PcList              the sink of the k-key query: the lane's k smallest keys, its bound the k-th (below)
+//   pc_query<kOriented> a lane's whole one-key query: the starting key (limit, -1), the finite check, the hint, the
+//                       walk.  kOriented chooses the sink and nothing else.
+//   pc_nearest_kernel<kOriented>, pc_fit_kernel<kOriented>   the query for an entry of `queries` and for a vertex with
+//                       the term as its epilogue; the <false> instantiations do not read what only the oriented sink
+//                       needs, and each entry point pair has one launcher (pc_nearest, pc_fit_terms: normals == nullptr
+//                       is the plain form).
+// Keys are made and read by pc_key / pc_won / pc_key_d2 / pc_key_index alone; pc_entries and pc_entry say which
+// entries of a body are queries and what the query of an entry is.
 //
 // Pruning margin.  Everything is measured in cells: t = fl(fl(x - origin) * inv) for a point s (t_s) and for the query
 // (t_q), the SAME two operations.  Undoing them, s - q = (t_s (1 + e_s) - t_q (1 + e_q)) / inv with |e| <= 2.1 u
@@ -50,13 +62,15 @@
 // <= sum e_k^2 (1 - 12 u) is therefore <= the computed d2 of every point of the cell, and a cell, a block (c .. c + 4) or
 // the rest of the grid (ring r done: every unvisited block has an axis with g >= 4 r) is skipped only when lb > the lane's
 // bound -- and lb >= kPcNormal, where float32 products have their relative accuracy.  A slab or a row of blocks or cells
-// is skipped by the same test on one or two axes' shares alone (a sum of fewer non-negative terms, rounded: not larger).  A query outside the grid needs
-// nothing special (t_q is not clamped for the bound); one whose t_q overflows has slack +inf, l = 0 and prunes nothing.
+// is skipped by the same test on one or two axes' shares alone (a sum of fewer non-negative terms, rounded: not
+// larger).  A query outside the grid needs nothing special (t_q is not clamped for the bound); one whose t_q overflows
+// has slack +inf, l = 0 and prunes nothing.
 //
 // The hint.  hint[b,n] in [0, Q) that names a valid point (checked on the caller's arrays before anything else is
-// addressed) whose d2 is finite and within tau enters as an ordinary key -- the exact d2 to that point, which the full
-// sweep computes too, so it cannot undercut the sweep's minimum; it only shortens the walk.  Anything else takes the
-// unhinted path.  hint may alias the index output: a lane reads its own entry before it writes it.
+// addressed) whose d2 is finite and within tau, and which the sink admits, enters as an ordinary key -- the exact d2 to
+// that point, which the full sweep computes too, so it cannot undercut the sweep's minimum; it only shortens the walk.
+// Anything else takes the unhinted path.  hint may alias the index output: a lane reads its own entry before it writes
+// it.
 //
 // k nearest points and normals (tuch_point_cloud_knn / _normals; PcList, pc_knn_kernel, pc_normals_kernel).  The
 // rule above, verbatim, for the k (1 .. 32) smallest keys of a query in ascending order: index [B,N,k], d2 [B,N,k]; with
@@ -66,11 +80,10 @@
 // queries or points, any resolution, eager or replayed.
 //   It is pc_walk with the list as its sink: the pruning bound is the lane's k-th key so far; while its list is not full
 // the bound is (limit, -1).  The derivation above holds for any such bound: a cell, a block, a row, a slab or the rest
-// of the grid is skipped only when its lower
-// bound exceeds the bound's d2, so no point whose key is below the bound is ever skipped, and the k smallest keys are
-// found whatever was visited in whatever order.  With no tau the ring test cannot end the walk before the list is full
-// (limit is then the largest finite float): the walk ends after a ring only once the list is full (or nothing beyond
-// the ring is within tau), or when the grid is exhausted.
+// of the grid is skipped only when its lower bound exceeds the bound's d2, so no point whose key is below the bound is
+// ever skipped, and the k smallest keys are found whatever was visited in whatever order.  With no tau the ring test
+// cannot end the walk before the list is full (limit is then the largest finite float): the walk ends after a ring
+// only once the list is full (or nothing beyond the ring is within tau), or when the grid is exhausted.
 //   The list needs dynamic indexing, so it lives in LDS, not in registers: [k][lanes] 64-bit keys (PcList).  It fills in
 // arrival order; once full it is a binary max-heap whose root, the bound, is kept in a register.  An accepted candidate
 // takes the root's place and sifts down (at most 2 log2 k reads; accepts become rare once the list has warmed up); after
@@ -90,23 +103,28 @@
 //
 // The term (pc_fit_kernel; tuch_point_cloud_fit_terms): the query for q = verts[b,v] + transl[b], then per vertex
 // g_v = scale w_v rho'(d2_v) / sum w and grad_verts[b,v] = 2 g_v (q - s) written by the lane that owns the row (no
-// atomics); the per-body loss, the normaliser and grad_transl = sum_v grad_verts[b,v] cross to the workgroup that arrives
-// last through fit_reduce_tail (fit_reduce.h: the hand-over all three fit terms use, drained write-through stores and no
-// fences, and its argument) and are added in chunk order, the total in a fixed tree: no float atomics, the same bits in
-// either mode of tuch_set_deterministic and for a body alone or in a batch.  The normaliser is fit_body_sum, rho is fit_rho.  A vertex of weight 0 is not computed from; one without winner contributes rho(tau^2) when tau is given and
-// the cloud is not empty, else 0, with a zero gradient row; a body with an empty cloud or without weight has loss 0.
+// atomics); the per-body loss, the normaliser and grad_transl = sum_v grad_verts[b,v] cross to the workgroup that
+// arrives last through fit_reduce_tail (fit_reduce.h: the hand-over all three fit terms use, drained write-through
+// stores and no fences, and its argument) and are added in chunk order, the total in a fixed tree: no float atomics,
+// the same bits in either mode of tuch_set_deterministic and for a body alone or in a batch.  The normaliser is
+// fit_body_sum, rho is fit_rho.  A vertex of weight 0 is not computed from; one without winner contributes rho(tau^2)
+// when tau is given and the cloud is not empty, else 0, with a zero gradient row; a body with an empty cloud or without
+// weight has loss 0.
 //
-// The oriented query (tuch_point_cloud_nearest_oriented / _fit_terms_oriented / _build_cones; PcOriented,
-// pc_query_oriented, pc_cones_kernel).  Points carry normals n (caller's order, never filed), a query a normal u.
-// pc_admissible is THE admissibility of a pair, stated in include/tuch_amd.h: with uu = |u|^2, nn = |n|^2, s = u . n,
-// every operation rounded to float32 on its own,  admissible <=> s > 0 and s s >= c2 (uu nn),  c2 = c c; a pair whose
-// uu or nn is 0 or not finite is unconstrained.  It is a function of the pair's bits and c alone, so the admissible set
-// of a query never depends on cell, lane, batch or order, and the winner -- the smallest key over the admissible valid
-// points, pc_d2 and the key untouched -- is the full sweep's whatever is pruned conservatively.  The walk is pc_walk
-// with PcOriented as its sink: a candidate is asked the rule only when it would otherwise become the best (d2 <= limit
-// and key < best), so the bound is always the key of an admissible point (or the limit) and every argument of the
-// pruning margin above holds unchanged.  A hint seeds the bound only if it names a valid, admissible point within the
-// limit: then its key is one the sweep computes too.
+// The oriented query (tuch_point_cloud_nearest_oriented / _fit_terms_oriented / _build_cones) is the query above with
+// another sink, PcOriented: the same key, pc_d2, walk, margin, hint and outputs, over the ADMISSIBLE valid points only.
+// Points carry normals n (caller's order, never filed), a query a normal u: an entry of query_normals, or, in the
+// term, what the lane that owns vertex v forms itself from the UNTRANSLATED verts by vn_vertex_normal (face_normal.h;
+// tuch_vertex_normals' raw row).  pc_admissible is THE admissibility of a pair, stated in include/tuch_amd.h: with
+// uu = |u|^2, nn = |n|^2, s = u . n, every operation rounded to float32 on its own,
+//     admissible <=> s > 0 and s s >= c2 (uu nn),  c2 = c c;
+// a pair whose uu or nn is 0 or not finite is unconstrained, so a call whose query normals or point normals are all
+// zero has the plain call's bits.  The rule is a function of the pair's bits and c alone, so the admissible set of a
+// query never depends on cell, lane, batch or order, and the winner -- the smallest key over the admissible valid
+// points -- is the full sweep's whatever is pruned conservatively.  The sink asks a candidate the rule only when it
+// would otherwise become the best (d2 <= limit and key < best), so its bound is always the key of an admissible point
+// (or the limit) and every argument of the pruning margin above holds unchanged.  Likewise the hint: it seeds the
+// bound only if the sink admits it, and then its key is one the sweep computes too.
 //   What it costs.  A lane whose admissible match is far away, or that has none, finds the key above every nearer
 // inadmissible point and gathers that point's normal (12 bytes at a random place) to refuse it; such lanes are a sixth
 // to a half of a body's vertices on a scan that sees one side.  The cones below take whole blocks off that path;
@@ -132,13 +150,12 @@
 // the cones only skip, they never decide, and the bits are those of the call with cones NULL.  The buffer starts with
 // a header (the resolution the cones were built at): a lane uses them only if that is the cloud's resolution and its
 // body's records lie inside the buffer.  They are stale after the next build.
-//   The oriented term (pc_fit_oriented_kernel, pc_fit_body<true>): the lane that owns vertex v forms u_v itself from the UNTRANSLATED verts by
-// vn_vertex_normal (face_normal.h; tuch_vertex_normals' raw row), then the oriented query; the epilogue is shared.
 #include "face_normal.h"
 #include "fit_reduce.h"
 #include "workspace.h"
 #include <math.h>
 #include <string.h>
+#include <type_traits>
 
 #pragma clang fp contract(off)
 
@@ -209,6 +226,15 @@ static __device__ __forceinline__ float pc_d2(float qx, float qy, float qz, floa
     return pc_add(pc_add(pc_mul(dx, dx), pc_mul(dy, dy)), pc_mul(dz, dz));
 }
 
+// THE key of a (d2, index) pair: the smaller key is the nearer point, among equal d2 bits the smaller index.  A key whose
+// index is -1 names no point (the starting key, kPcNoKey): the query has not won.
+static __device__ __forceinline__ unsigned long long pc_key(float d2, int index)
+{
+    return ((unsigned long long)__float_as_uint(d2) << 32) | (uint32_t)index;
+}
+static __device__ __forceinline__ float pc_key_d2(unsigned long long key) { return __uint_as_float((uint32_t)(key >> 32)); }
+static __device__ __forceinline__ int pc_key_index(unsigned long long key) { return (int32_t)(uint32_t)key; }
+static __device__ __forceinline__ bool pc_won(unsigned long long key) { return (uint32_t)key != 0xffffffffu; }
 // is point i of body b in the cloud?  (its coordinates only where it may be)
 static __device__ __forceinline__ bool pc_valid(const float* __restrict__ points, const int32_t* __restrict__ counts,
                                                 const float* __restrict__ weights, int b, int Q, int i, float& x, float& y,
@@ -221,6 +247,23 @@ static __device__ __forceinline__ bool pc_valid(const float* __restrict__ points
     if (weights && weights[o] == 0.0f) return false;
     x = points[o * 3]; y = points[o * 3 + 1]; z = points[o * 3 + 2];
     return pc_finite3(x, y, z);
+}
+
+// Entry i of body b of queries [B][N][3] as a query.  pc_entries: how many entries of the body are queries (the rest
+// have no winner and are not read); pc_entry: q = x + shift[b], one add per component (no shift: the bits of x).
+static __device__ __forceinline__ int pc_entries(const int32_t* __restrict__ query_counts, int b, int N)
+{
+    return query_counts ? pc_clampi(query_counts[b], 0, N) : N;
+}
+template <bool kShifted = false>
+static __device__ __forceinline__ void pc_entry(const float* __restrict__ queries, const float* __restrict__ shift, int b, int N,
+                                                int i, float& qx, float& qy, float& qz)
+{
+    const size_t o = (size_t)b * N + i;
+    qx = queries[o * 3]; qy = queries[o * 3 + 1]; qz = queries[o * 3 + 2];
+    if (kShifted || shift) {
+        qx = pc_add(qx, shift[3 * b]); qy = pc_add(qy, shift[3 * b + 1]); qz = pc_add(qz, shift[3 * b + 2]);
+    }
 }
 
 struct PcGrid {
@@ -392,7 +435,7 @@ static __device__ __forceinline__ float pc_sq(float cell, float l)
 static __device__ __forceinline__ bool pc_out(float sum, unsigned long long best)
 {
     const float lb = pc_mul(sum, 1.0f - kPcMargin);
-    return lb > __uint_as_float((uint32_t)(best >> 32)) && lb >= kPcNormal;
+    return lb > pc_key_d2(best) && lb >= kPcNormal;
 }
 
 // The sink of a one-key query: `best` arrives as the starting key (no key: (limit bits, -1) with limit = tau^2 or
@@ -406,6 +449,15 @@ struct PcBest {
         best = d2 <= limit && key < best ? key : best;         // (a select, not a branch around a store: the innermost loop)
     }
     __device__ __forceinline__ bool skip_block(long long) const { return false; }
+    __device__ __forceinline__ bool admits(int) const { return true; }
+};
+
+// what the oriented query knows of the cloud's normals
+struct PcOrient {
+    const float* normals;        // [B][Q][3], the caller's order
+    const uint32_t* cones;       // kCpCone header words ([0]: the resolution they were built at), then the records; or nullptr
+    long long cone_cap;          // records behind the header
+    float c, c2;                 // the cosine and its square
 };
 
 // THE admissibility of a (query normal u, point normal n) pair (file header: the oriented query): every operation
@@ -434,6 +486,28 @@ struct PcOriented {
     const float* cones;
     long long cone_cap;
     float inv, c;                // 1 / |u| and the cosine, for the cones
+    // Everything but the key and the limit, for the query normal u of a lane of body b.  The cones serve the lane only
+    // if they were built at the cloud's resolution, lie wholly inside the buffer for its body, and uu is in the sane
+    // range (file header).
+    __device__ __forceinline__ void orient(const PcTables& w, const PcOrient& o, int b, int Q_, float ux_, float uy_, float uz_)
+    {
+        normals = o.normals + (size_t)b * Q_ * 3;
+        Q = Q_;
+        ux = ux_; uy = uy_; uz = uz_;
+        uu = pc_add(pc_add(pc_mul(ux, ux), pc_mul(uy, uy)), pc_mul(uz, uz));
+        c2 = o.c2; c = o.c;
+        constrained = uu > 0.0f && __builtin_isfinite(uu);
+        cones = nullptr; cone_cap = 1; inv = 0.0f;
+        if (o.cones && constrained && uu >= kCpNormalLo && uu <= kCpNormalHi) {
+            const int res = pc_clampi((int)w.head[kCtl + (size_t)b * kHead + H_RES], 1, kMaxRes), cres = (res + 3) >> 2;
+            const long long stride = (long long)cres * cres * cres;
+            if ((int)o.cones[0] == res && (b + 1) * stride <= o.cone_cap) {
+                cones = (const float*)(o.cones + kCpCone) + (size_t)b * stride * kCpCone;
+                cone_cap = stride;
+                inv = 1.0f / __builtin_sqrtf(uu);
+            }
+        }
+    }
     __device__ __forceinline__ unsigned long long bound() const { return best; }
     __device__ __forceinline__ bool admits(int index) const
     {
@@ -443,7 +517,7 @@ struct PcOriented {
     }
     __device__ __forceinline__ void offer(float d2, unsigned long long key)
     {
-        if (d2 <= limit && key < best && admits((int)(uint32_t)key)) best = key;
+        if (d2 <= limit && key < best && admits(pc_key_index(key))) best = key;
     }
     // may the lane pass block `block` of its body by?  Only a usable cone that is wholly inadmissible for u says so.
     __device__ __forceinline__ bool skip_block(long long block) const
@@ -457,8 +531,8 @@ struct PcOriented {
 // THE walk of the grid, for the finite query (qx, qy, qz) against the cloud of body b: the rings, gaps, slack and 2^-20
 // margin of the file header.  Everything is pruned against sink.bound(), a key that no candidate still wanted lies
 // above (PcBest: the best key so far; PcList below: the k-th), and every point of a cell that is opened goes to
-// sink.offer(d2, key).  The sink comes and goes by value: it lives in registers, and pc_nearest_kernel compiles to the
-// instructions it had when the walk was written out for the one key.
+// sink.offer(d2, key).  The sink comes and goes by value: it lives in registers, and pc_nearest_kernel<false> compiles
+// to the instructions it had when the walk was written out for the one key.
 template <typename Sink>
 static __device__ Sink pc_walk(const PcTables& w, int b, int Q, float qx, float qy, float qz, Sink sink)
 {
@@ -517,7 +591,7 @@ static __device__ Sink pc_walk(const PcTables& w, int b, int Q, float qx, float 
                                 for (int p = begin; p < end; ++p) {
                                     const float4 s = pts[p];
                                     const float d2 = pc_d2(qx, qy, qz, s.x, s.y, s.z);
-                                    sink.offer(d2, ((unsigned long long)__float_as_uint(d2) << 32) | (uint32_t)__float_as_int(s.w));
+                                    sink.offer(d2, pc_key(d2, __float_as_int(s.w)));
                                 }
                             }
                         }
@@ -529,26 +603,38 @@ static __device__ Sink pc_walk(const PcTables& w, int b, int Q, float qx, float 
     return sink;
 }
 
-// The whole query of one lane: the starting key, the hint, the search.  Returns the key; (uint32_t)key == ~0u: no winner.
-static __device__ __forceinline__ unsigned long long pc_query(const PcTables& w, const float* __restrict__ points,
+// The whole query of one lane, plain or oriented: the starting key, the hint, the search.  Returns the key; !pc_won(key):
+// no winner.  kOriented only chooses the sink (PcOriented, set up for the query normal u) and with it what the hint is
+// asked besides validity and the limit: PcBest admits every point.  The plain form reads neither `o` nor u.
+template <bool kOriented>
+static __device__ __forceinline__ unsigned long long pc_query(const PcTables& w, const PcOrient& o,
+                                                              const float* __restrict__ points,
                                                               const int32_t* __restrict__ counts,
                                                               const float* __restrict__ weights, int b, int Q, float qx,
-                                                              float qy, float qz, int hint, float limit)
+                                                              float qy, float qz, float ux, float uy, float uz, int hint,
+                                                              float limit)
 {
-    PcBest sink = {((unsigned long long)__float_as_uint(limit) << 32) | 0xffffffffull, limit};
+    std::conditional_t<kOriented, PcOriented, PcBest> sink;
+    sink.best = pc_key(limit, -1);
+    sink.limit = limit;
     if (!pc_finite3(qx, qy, qz)) return sink.best;
+    if constexpr (kOriented) sink.orient(w, o, b, Q, ux, uy, uz);
     float sx, sy, sz;
     if (hint >= 0 && hint < Q && pc_valid(points, counts, weights, b, Q, hint, sx, sy, sz)) {
         const float d2 = pc_d2(qx, qy, qz, sx, sy, sz);
-        if (d2 <= limit) sink.best = ((unsigned long long)__float_as_uint(d2) << 32) | (uint32_t)hint;
+        if (d2 <= limit && sink.admits(hint)) sink.best = pc_key(d2, hint);
     }
     return pc_walk(w, b, Q, qx, qy, qz, sink).best;
 }
 
-__global__ __launch_bounds__(kBlock) void pc_nearest_kernel(PcTables w, const float* __restrict__ points,
+// tuch_point_cloud_nearest (kOriented = false: orient and query_normals are not read) and _nearest_oriented
+template <bool kOriented>
+__global__ __launch_bounds__(kBlock) void pc_nearest_kernel(PcTables w, PcOrient orient, const float* __restrict__ points,
                                                            const int32_t* __restrict__ counts,
                                                            const float* __restrict__ weights,
-                                                           const float* __restrict__ queries, const float* __restrict__ shift,
+                                                           const float* __restrict__ queries,
+                                                           const float* __restrict__ query_normals,
+                                                           const float* __restrict__ shift,
                                                            const int32_t* __restrict__ query_counts, const int32_t* hint,
                                                            float limit, int Q, int N, float* __restrict__ d2_out,
                                                            int32_t* index_out)
@@ -556,100 +642,20 @@ __global__ __launch_bounds__(kBlock) void pc_nearest_kernel(PcTables w, const fl
     const int b = blockIdx.y, i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= N) return;
     const size_t o = (size_t)b * N + i;
-    int count = N;
-    if (query_counts) count = pc_clampi(query_counts[b], 0, N);
     unsigned long long best = kPcNoKey;
-    if (i < count) {
+    if (i < pc_entries(query_counts, b, N)) {
         const int h = hint ? hint[o] : -1;
-        float qx = queries[o * 3], qy = queries[o * 3 + 1], qz = queries[o * 3 + 2];
-        if (shift) {
-            qx = pc_add(qx, shift[3 * b]); qy = pc_add(qy, shift[3 * b + 1]); qz = pc_add(qz, shift[3 * b + 2]);
-        }
-        best = pc_query(w, points, counts, weights, b, Q, qx, qy, qz, h, limit);
+        float qx, qy, qz, ux = 0.0f, uy = 0.0f, uz = 0.0f;
+        pc_entry(queries, shift, b, N, i, qx, qy, qz);
+        if constexpr (kOriented) { ux = query_normals[o * 3]; uy = query_normals[o * 3 + 1]; uz = query_normals[o * 3 + 2]; }
+        best = pc_query<kOriented>(w, orient, points, counts, weights, b, Q, qx, qy, qz, ux, uy, uz, h, limit);
     }
-    const bool won = (uint32_t)best != 0xffffffffu;
-    d2_out[o] = won ? __uint_as_float((uint32_t)(best >> 32)) : __builtin_inff();
-    index_out[o] = won ? (int32_t)(uint32_t)best : -1;
+    const bool won = pc_won(best);
+    d2_out[o] = won ? pc_key_d2(best) : __builtin_inff();
+    index_out[o] = won ? pc_key_index(best) : -1;
 }
 
-// -------------------------------------------------------------------------------------------------- the oriented query
-// what the oriented kernels know of the cloud's normals
-struct PcOrient {
-    const float* normals;        // [B][Q][3], the caller's order
-    const uint32_t* cones;       // kCpCone header words ([0]: the resolution they were built at), then the records; or nullptr
-    long long cone_cap;          // records behind the header
-    float c, c2;                 // the cosine and its square
-};
-
-// The whole oriented query of one lane: pc_query with the query's normal u.  A hint seeds the key only if it names a
-// valid, admissible point within the limit.  The cones serve a lane only if they were built at the cloud's resolution,
-// lie wholly inside the buffer for its body, and uu is in the sane range (file header).
-static __device__ __forceinline__ unsigned long long pc_query_oriented(const PcTables& w, const PcOrient& o,
-                                                                       const float* __restrict__ points,
-                                                                       const int32_t* __restrict__ counts,
-                                                                       const float* __restrict__ weights, int b, int Q,
-                                                                       float qx, float qy, float qz, float ux, float uy,
-                                                                       float uz, int hint, float limit)
-{
-    PcOriented sink;
-    sink.best = ((unsigned long long)__float_as_uint(limit) << 32) | 0xffffffffull;
-    sink.limit = limit;
-    if (!pc_finite3(qx, qy, qz)) return sink.best;
-    sink.normals = o.normals + (size_t)b * Q * 3;
-    sink.Q = Q;
-    sink.ux = ux; sink.uy = uy; sink.uz = uz;
-    sink.uu = pc_add(pc_add(pc_mul(ux, ux), pc_mul(uy, uy)), pc_mul(uz, uz));
-    sink.c2 = o.c2; sink.c = o.c;
-    sink.constrained = sink.uu > 0.0f && __builtin_isfinite(sink.uu);
-    sink.cones = nullptr; sink.cone_cap = 1; sink.inv = 0.0f;
-    if (o.cones && sink.constrained && sink.uu >= kCpNormalLo && sink.uu <= kCpNormalHi) {
-        const int res = pc_clampi((int)w.head[kCtl + (size_t)b * kHead + H_RES], 1, kMaxRes), cres = (res + 3) >> 2;
-        const long long stride = (long long)cres * cres * cres;
-        if ((int)o.cones[0] == res && (b + 1) * stride <= o.cone_cap) {
-            sink.cones = (const float*)(o.cones + kCpCone) + (size_t)b * stride * kCpCone;
-            sink.cone_cap = stride;
-            sink.inv = 1.0f / __builtin_sqrtf(sink.uu);
-        }
-    }
-    float sx, sy, sz;
-    if (hint >= 0 && hint < Q && pc_valid(points, counts, weights, b, Q, hint, sx, sy, sz)) {
-        const float d2 = pc_d2(qx, qy, qz, sx, sy, sz);
-        if (d2 <= limit && sink.admits(hint)) sink.best = ((unsigned long long)__float_as_uint(d2) << 32) | (uint32_t)hint;
-    }
-    return pc_walk(w, b, Q, qx, qy, qz, sink).best;
-}
-
-__global__ __launch_bounds__(kBlock) void pc_nearest_oriented_kernel(PcTables w, PcOrient orient,
-                                                                    const float* __restrict__ points,
-                                                                    const int32_t* __restrict__ counts,
-                                                                    const float* __restrict__ weights,
-                                                                    const float* __restrict__ queries,
-                                                                    const float* __restrict__ query_normals,
-                                                                    const float* __restrict__ shift,
-                                                                    const int32_t* __restrict__ query_counts,
-                                                                    const int32_t* hint, float limit, int Q, int N,
-                                                                    float* __restrict__ d2_out, int32_t* index_out)
-{
-    const int b = blockIdx.y, i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= N) return;
-    const size_t o = (size_t)b * N + i;
-    int count = N;
-    if (query_counts) count = pc_clampi(query_counts[b], 0, N);
-    unsigned long long best = kPcNoKey;
-    if (i < count) {
-        const int h = hint ? hint[o] : -1;
-        float qx = queries[o * 3], qy = queries[o * 3 + 1], qz = queries[o * 3 + 2];
-        if (shift) {
-            qx = pc_add(qx, shift[3 * b]); qy = pc_add(qy, shift[3 * b + 1]); qz = pc_add(qz, shift[3 * b + 2]);
-        }
-        best = pc_query_oriented(w, orient, points, counts, weights, b, Q, qx, qy, qz, query_normals[o * 3],
-                                 query_normals[o * 3 + 1], query_normals[o * 3 + 2], h, limit);
-    }
-    const bool won = (uint32_t)best != 0xffffffffu;
-    d2_out[o] = won ? __uint_as_float((uint32_t)(best >> 32)) : __builtin_inff();
-    index_out[o] = won ? (int32_t)(uint32_t)best : -1;
-}
-
+// ----------------------------------------------------------------------------------------------------------- the cones
 // The cone of one 4^3-cell block of one body (file header: the cones): one wavefront per block, its lanes striding over
 // the block's points row by row (the four cells of a block's row are contiguous in the filed order).  The record is
 // closest_point.hip's: axis (the normalised mean of the unit normals), cos beta and sin beta of the normal farthest from
@@ -801,20 +807,14 @@ static __device__ __forceinline__ int pc_knn_lane(const PcTables& w, const float
                                                   float limit, int b, int Q, int N, int i, int k, unsigned long long* list,
                                                   int lanes, int lane, float& qx, float& qy, float& qz)
 {
-    int count = N;
-    if (query_counts) count = pc_clampi(query_counts[b], 0, N);
-    if (i >= count) return 0;
-    const size_t o = (size_t)b * N + i;
-    qx = queries[o * 3]; qy = queries[o * 3 + 1]; qz = queries[o * 3 + 2];
-    if (shift) {
-        qx = pc_add(qx, shift[3 * b]); qy = pc_add(qy, shift[3 * b + 1]); qz = pc_add(qz, shift[3 * b + 2]);
-    }
+    if (i >= pc_entries(query_counts, b, N)) return 0;
+    pc_entry(queries, shift, b, N, i, qx, qy, qz);
     if (!pc_finite3(qx, qy, qz)) return 0;
     PcList l;
     l.at = list + lane;
     l.lanes = lanes; l.k = k; l.n = 0;
     l.limit = limit;
-    l.root = ((unsigned long long)__float_as_uint(limit) << 32) | 0xffffffffull;
+    l.root = pc_key(limit, -1);
     l = pc_walk(w, b, Q, qx, qy, qz, l);                      // the n <= k smallest admissible keys, unsorted
     pc_list_sort(l);
     return l.n;
@@ -833,10 +833,10 @@ __global__ __launch_bounds__(kBlock) void pc_knn_kernel(PcTables w, const float*
     float qx, qy, qz;
     const int n = pc_knn_lane(w, queries, shift, query_counts, limit, b, Q, N, i, k, pc_keys, lanes, lane, qx, qy, qz);
     const size_t o = ((size_t)b * N + i) * k;
-    for (int j = 0; j < k; ++j) {
+    for (int j = 0; j < k; ++j) {                               // (a slot below n holds a point's key; kPcNoKey is +inf, -1)
         const unsigned long long key = j < n ? pc_keys[(size_t)j * lanes + lane] : kPcNoKey;
-        d2_out[o + j] = j < n ? __uint_as_float((uint32_t)(key >> 32)) : __builtin_inff();
-        index_out[o + j] = j < n ? (int32_t)(uint32_t)key : -1;
+        d2_out[o + j] = pc_key_d2(key);
+        index_out[o + j] = pc_key_index(key);
     }
 }
 
@@ -910,14 +910,14 @@ __global__ __launch_bounds__(kBlock) void pc_normals_kernel(PcTables w, const fl
     // the mean of d_j = s_j - q, in key order
     float mx = 0.0f, my = 0.0f, mz = 0.0f;
     for (int j = 0; j < n; ++j) {
-        const float* s = body + (size_t)pc_clampi((int)(uint32_t)pc_keys[(size_t)j * lanes + lane], 0, Q - 1) * 3;
+        const float* s = body + (size_t)pc_clampi(pc_key_index(pc_keys[(size_t)j * lanes + lane]), 0, Q - 1) * 3;
         const float dx = pc_sub(s[0], qx), dy = pc_sub(s[1], qy), dz = pc_sub(s[2], qz);
         mx = j == 0 ? dx : pc_add(mx, dx); my = j == 0 ? dy : pc_add(my, dy); mz = j == 0 ? dz : pc_add(mz, dz);
     }
     if (n > 0) { mx = mx / (float)n; my = my / (float)n; mz = mz / (float)n; }
     float cxx = 0.0f, cxy = 0.0f, cxz = 0.0f, cyy = 0.0f, cyz = 0.0f, czz = 0.0f;
     for (int j = 0; j < n; ++j) {
-        const float* s = body + (size_t)pc_clampi((int)(uint32_t)pc_keys[(size_t)j * lanes + lane], 0, Q - 1) * 3;
+        const float* s = body + (size_t)pc_clampi(pc_key_index(pc_keys[(size_t)j * lanes + lane]), 0, Q - 1) * 3;
         const float ex = pc_sub(pc_sub(s[0], qx), mx), ey = pc_sub(pc_sub(s[1], qy), my), ez = pc_sub(pc_sub(s[2], qz), mz);
         cxx = pc_add(cxx, pc_mul(ex, ex)); cxy = pc_add(cxy, pc_mul(ex, ey)); cxz = pc_add(cxz, pc_mul(ex, ez));
         cyy = pc_add(cyy, pc_mul(ey, ey)); cyz = pc_add(cyz, pc_mul(ey, ez)); czz = pc_add(czz, pc_mul(ez, ez));
@@ -991,20 +991,24 @@ struct PcMesh {
     int F;
 };
 
-// The term, for both kernels.  kOriented: the query is the oriented one, with the raw vertex normal of the UNTRANSLATED
-// verts (tuch_vertex_normals' row, normalize = 0); nothing else differs.
+// The term (tuch_point_cloud_fit_terms; kOriented: _fit_terms_oriented).  kOriented: the query is the oriented one, with
+// the raw vertex normal of the UNTRANSLATED verts (tuch_vertex_normals' row, normalize = 0); nothing else differs, and
+// the plain form reads neither orient nor mesh.  (The arguments stay a list: as one struct by value they are all loaded
+// at entry, and this kernel, which is at its SGPR limit, then spills them to VGPR lanes and reloads them inside the
+// walk -- 81 v_readlane against 19, docs/HISTORY.md section 13.)
 template <bool kOriented>
-static __device__ __forceinline__ void pc_fit_body(FitShared& sh, const PcTables& w, const PcOrient& orient,
-                                                   const PcMesh& mesh, const float* __restrict__ points,
-                                                   const int32_t* __restrict__ counts, const float* __restrict__ weights,
-                                                   const float* __restrict__ verts, const float* __restrict__ transl,
-                                                   const int32_t* hint, float limit, int has_tau, int B, int Q, int V,
-                                                   const float* __restrict__ vw, int layout, int rho, float sigma2,
-                                                   float scale, float* __restrict__ d2_out, int32_t* index_out,
-                                                   float* partial, int* ticket, float* __restrict__ per_body,
-                                                   float* __restrict__ total, float* __restrict__ grad_verts,
-                                                   float* __restrict__ grad_transl)
+__global__ __launch_bounds__(kBlock) void pc_fit_kernel(PcTables w, PcOrient orient, PcMesh mesh,
+                                                       const float* __restrict__ points,
+                                                       const int32_t* __restrict__ counts, const float* __restrict__ weights,
+                                                       const float* __restrict__ verts, const float* __restrict__ transl,
+                                                       const int32_t* hint, float limit, int has_tau, int B, int Q, int V,
+                                                       const float* __restrict__ vw, int layout, int rho, float sigma2,
+                                                       float scale, float* __restrict__ d2_out, int32_t* index_out,
+                                                       float* partial, int* ticket, float* __restrict__ per_body,
+                                                       float* __restrict__ total, float* __restrict__ grad_verts,
+                                                       float* __restrict__ grad_transl)
 {
+    __shared__ FitShared sh;
     const int c = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
     // the normaliser: this body's vertex weights
     float wsum = (float)V;
@@ -1020,20 +1024,15 @@ static __device__ __forceinline__ void pc_fit_body(FitShared& sh, const PcTables
         const bool live = wv != 0.0f && wsum != 0.0f && cloud > 0;
         const int h = hint ? hint[o] : -1;
         if (live) {
-            qx = pc_add(verts[o * 3], transl[3 * b]);
-            qy = pc_add(verts[o * 3 + 1], transl[3 * b + 1]);
-            qz = pc_add(verts[o * 3 + 2], transl[3 * b + 2]);
-            if (kOriented) {
-                float ux, uy, uz;
+            pc_entry<true>(verts, transl, b, V, v, qx, qy, qz);
+            float ux = 0.0f, uy = 0.0f, uz = 0.0f;
+            if constexpr (kOriented)
                 vn_vertex_normal(verts + (size_t)b * V * 3, mesh.faces, mesh.vf_off, mesh.vf_ids, V, mesh.F, v, ux, uy, uz);
-                best = pc_query_oriented(w, orient, points, counts, weights, b, Q, qx, qy, qz, ux, uy, uz, h, limit);
-            } else {
-                best = pc_query(w, points, counts, weights, b, Q, qx, qy, qz, h, limit);
-            }
+            best = pc_query<kOriented>(w, orient, points, counts, weights, b, Q, qx, qy, qz, ux, uy, uz, h, limit);
         }
-        const bool won = (uint32_t)best != 0xffffffffu;
-        const float d2 = won ? __uint_as_float((uint32_t)(best >> 32)) : __builtin_inff();
-        const int idx = won ? (int32_t)(uint32_t)best : -1;
+        const bool won = pc_won(best);
+        const float d2 = won ? pc_key_d2(best) : __builtin_inff();
+        const int idx = won ? pc_key_index(best) : -1;
         d2_out[o] = d2;
         index_out[o] = idx;
         if (won) {
@@ -1053,36 +1052,6 @@ static __device__ __forceinline__ void pc_fit_body(FitShared& sh, const PcTables
     }
     fit_reduce_tail(sh, s, ex, ey, ez, wsum, scale, partial, ticket, B, per_body, total, grad_transl);
 }
-__global__ __launch_bounds__(kBlock) void pc_fit_kernel(PcTables w, const float* __restrict__ points,
-                                                       const int32_t* __restrict__ counts, const float* __restrict__ weights,
-                                                       const float* __restrict__ verts, const float* __restrict__ transl,
-                                                       const int32_t* hint, float limit, int has_tau, int B, int Q, int V,
-                                                       const float* __restrict__ vw, int layout, int rho, float sigma2,
-                                                       float scale, float* __restrict__ d2_out, int32_t* index_out,
-                                                       float* partial, int* ticket, float* __restrict__ per_body,
-                                                       float* __restrict__ total, float* __restrict__ grad_verts,
-                                                       float* __restrict__ grad_transl)
-{
-    __shared__ FitShared sh;
-    pc_fit_body<false>(sh, w, PcOrient{}, PcMesh{}, points, counts, weights, verts, transl, hint, limit, has_tau, B, Q, V, vw, layout,
-                       rho, sigma2, scale, d2_out, index_out, partial, ticket, per_body, total, grad_verts, grad_transl);
-}
-
-__global__ __launch_bounds__(kBlock) void pc_fit_oriented_kernel(PcTables w, PcOrient orient, PcMesh mesh,
-                                                       const float* __restrict__ points,
-                                                       const int32_t* __restrict__ counts, const float* __restrict__ weights,
-                                                       const float* __restrict__ verts, const float* __restrict__ transl,
-                                                       const int32_t* hint, float limit, int has_tau, int B, int Q, int V,
-                                                       const float* __restrict__ vw, int layout, int rho, float sigma2,
-                                                       float scale, float* __restrict__ d2_out, int32_t* index_out,
-                                                       float* partial, int* ticket, float* __restrict__ per_body,
-                                                       float* __restrict__ total, float* __restrict__ grad_verts,
-                                                       float* __restrict__ grad_transl)
-{
-    __shared__ FitShared sh;
-    pc_fit_body<true>(sh, w, orient, mesh, points, counts, weights, verts, transl, hint, limit, has_tau, B, Q, V, vw, layout,
-                      rho, sigma2, scale, d2_out, index_out, partial, ticket, per_body, total, grad_verts, grad_transl);
-}
 
 bool pc_sizes_ok(int B, int Q, int N)
 {
@@ -1099,6 +1068,93 @@ PcTables pc_tables(void* workspace, size_t bytes, int B, int Q)
     w.tables = (const int32_t*)((char*)workspace + l.tables);
     w.cap = (long long)((bytes - l.tables) / sizeof(int32_t));
     return w;
+}
+
+// the limit of a query: f32(tau) f32(tau), or the largest finite d2 (max_distance <= 0: none)
+float pc_limit(float max_distance) { return max_distance > 0.0f ? fminf(max_distance * max_distance, kPcMaxD2) : kPcMaxD2; }
+
+// Every entry point that queries: the workspace holds the regions a query addresses by themselves, the term's scratch
+// (scratch_need != 0) its partials.  Called inside the entry point's tuch_ws_scope, which stays alive up to the launch:
+// the layout, like pc_tables' after it, is the guarded one under the canary option.
+int pc_workspace_check(const char* name, size_t workspace_bytes, int B, int Q, size_t scratch_bytes = 0, size_t scratch_need = 0)
+{
+    const size_t need = pc_layout(B, Q, 1).total;
+    if (workspace_bytes >= need && scratch_bytes >= scratch_need) return TUCH_OK;
+    if (scratch_need)
+        tuch_set_error("%s: workspace %zu < %zu or scratch %zu < %zu bytes", name, workspace_bytes, need, scratch_bytes,
+                       scratch_need);
+    else
+        tuch_set_error("%s: workspace %zu < %zu bytes", name, workspace_bytes, need);
+    return TUCH_ERR_WORKSPACE;
+}
+
+size_t pc_cone_words(int B, int R)
+{
+    const size_t c = (size_t)((R + 3) >> 2);
+    return (size_t)kCpCone + (size_t)B * c * c * c * kCpCone;
+}
+
+// what the oriented launches take; cones NULL: none
+PcOrient pc_orient(const float* normals, float max_angle_cos, const void* cones, size_t cones_bytes)
+{
+    PcOrient o;
+    o.normals = normals;
+    o.cones = (const uint32_t*)cones;
+    o.cone_cap = cones && cones_bytes >= 2 * kCpCone * sizeof(float) ? (long long)(cones_bytes / (kCpCone * sizeof(float))) - 1 : 0;
+    if (o.cone_cap == 0) o.cones = nullptr;
+    o.c = fminf(fmaxf(max_angle_cos, 0.0f), 1.0f);
+    o.c2 = o.c * o.c;
+    return o;
+}
+
+// both nearest entry points: `name` is the one the errors speak of; normals == nullptr is tuch_point_cloud_nearest
+int pc_nearest(const char* name, const void* workspace, size_t workspace_bytes, const float* points, const int32_t* counts,
+               const float* weights, const float* normals, const float* queries, const float* query_normals, const float* shift,
+               const int32_t* query_counts, const int32_t* hint, float max_distance, float max_angle_cos, const void* cones,
+               size_t cones_bytes, int B, int Q, int N, float* d2, int32_t* index, void* stream)
+{
+    TUCH_REQUIRE(workspace && points && queries && d2 && index, "%s: null pointer", name);
+    TUCH_REQUIRE(pc_sizes_ok(B, Q, N), "%s: bad sizes B=%d Q=%d N=%d", name, B, Q, N);
+    tuch_ws_scope scope(g_pc_canary != 0);
+    const int rc = pc_workspace_check(name, workspace_bytes, B, Q);
+    if (rc != TUCH_OK) return rc;
+    hipLaunchKernelGGL(normals ? pc_nearest_kernel<true> : pc_nearest_kernel<false>, dim3(ceil_div(N, kBlock), B), dim3(kBlock), 0,
+                       (hipStream_t)stream, pc_tables((void*)workspace, workspace_bytes, B, Q),
+                       pc_orient(normals, max_angle_cos, cones, cones_bytes), points, counts, weights, queries, query_normals,
+                       shift, query_counts, hint, pc_limit(max_distance), Q, N, d2, index);
+    return tuch_check_launch(name);
+}
+
+// both term entry points: normals == nullptr is tuch_point_cloud_fit_terms (no mesh, no cones)
+int pc_fit_terms(const char* name, const void* workspace, size_t workspace_bytes, const float* points, const int32_t* counts,
+                 const float* weights, const float* normals, float max_angle_cos, const PcMesh& mesh, const void* cones,
+                 size_t cones_bytes, const float* verts, const float* transl, const int32_t* hint, float max_distance, int B, int Q,
+                 int V, const float* vertex_weights, int vertex_weight_layout, int rho, float sigma, float scale, float* d2,
+                 int32_t* index, int* ticket, float* per_body, float* total, float* grad_verts, float* grad_transl, void* scratch,
+                 size_t scratch_bytes, void* stream)
+{
+    TUCH_REQUIRE(workspace && points && verts && transl && d2 && index && ticket && per_body && total && grad_verts &&
+                     grad_transl && scratch,
+                 "%s: null pointer", name);
+    TUCH_REQUIRE(pc_sizes_ok(B, Q, V), "%s: bad sizes B=%d Q=%d V=%d", name, B, Q, V);
+    TUCH_REQUIRE(vertex_weight_layout >= 0 && vertex_weight_layout <= 2 && (vertex_weight_layout == 0 || vertex_weights),
+                 "%s: vertex weight layout %d (0 none, 1 [V], 2 [B,V]) with weights %p", name, vertex_weight_layout,
+                 (const void*)vertex_weights);
+    TUCH_REQUIRE(rho == TUCH_SCAN_RHO_SQUARED || rho == TUCH_SCAN_RHO_DISTANCE || (rho == TUCH_SCAN_RHO_GMOF && sigma > 0.0f),
+                 "%s: rho %d (0 squared, 1 distance, 2 gmof with sigma > 0; sigma = %g)", name, rho, (double)sigma);
+    tuch_ws_scope scope(g_pc_canary != 0);
+    const PcScratch sl = scope.record(0, [&] { return pc_scratch(B, V); });
+    const int rc = pc_workspace_check(name, workspace_bytes, B, Q, scratch_bytes, sl.total);
+    if (rc != TUCH_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const PcTables w = pc_tables((void*)workspace, workspace_bytes, B, Q);
+    scope.arm(scratch, (int32_t*)w.head, s);
+    hipLaunchKernelGGL(normals ? pc_fit_kernel<true> : pc_fit_kernel<false>, dim3(ceil_div(V, kBlock), B), dim3(kBlock), 0, s, w,
+                       pc_orient(normals, max_angle_cos, cones, cones_bytes), mesh, points, counts, weights, verts, transl, hint,
+                       pc_limit(max_distance), max_distance > 0.0f ? 1 : 0, B, Q, V, vertex_weights, vertex_weight_layout, rho,
+                       sigma * sigma, scale, d2, index, (float*)((char*)scratch + sl.partial), ticket, per_body, total,
+                       grad_verts, grad_transl);
+    return tuch_check_launch(name);
 }
 
 }  // namespace
@@ -1161,19 +1217,8 @@ extern "C" int tuch_point_cloud_nearest(const void* workspace, size_t workspace_
                                         const float* shift, const int32_t* query_counts, const int32_t* hint,
                                         float max_distance, int B, int Q, int N, float* d2, int32_t* index, void* stream)
 {
-    TUCH_REQUIRE(workspace && points && queries && d2 && index, "tuch_point_cloud_nearest: null pointer");
-    TUCH_REQUIRE(pc_sizes_ok(B, Q, N), "tuch_point_cloud_nearest: bad sizes B=%d Q=%d N=%d", B, Q, N);
-    tuch_ws_scope scope(g_pc_canary != 0);
-    const size_t need = pc_layout(B, Q, 1).total;
-    if (workspace_bytes < need) {
-        tuch_set_error("tuch_point_cloud_nearest: workspace %zu < %zu bytes", workspace_bytes, need);
-        return TUCH_ERR_WORKSPACE;
-    }
-    const float limit = max_distance > 0.0f ? fminf(max_distance * max_distance, kPcMaxD2) : kPcMaxD2;
-    hipLaunchKernelGGL(pc_nearest_kernel, dim3(ceil_div(N, kBlock), B), dim3(kBlock), 0, (hipStream_t)stream,
-                       pc_tables((void*)workspace, workspace_bytes, B, Q), points, counts, weights, queries, shift,
-                       query_counts, hint, limit, Q, N, d2, index);
-    return tuch_check_launch("tuch_point_cloud_nearest");
+    return pc_nearest("tuch_point_cloud_nearest", workspace, workspace_bytes, points, counts, weights, nullptr, queries, nullptr,
+                      shift, query_counts, hint, max_distance, 0.0f, nullptr, 0, B, Q, N, d2, index, stream);
 }
 
 namespace {
@@ -1182,18 +1227,11 @@ namespace {
 // bytes) never exceeds 32 KiB and five workgroups fit into a CU's 160 KiB of LDS -- 20 wavefronts at k <= 16, 10 beyond.
 int pc_knn_lanes(int k) { return k > 16 ? kBlock / 2 : kBlock; }
 
-// (called inside the entry point's tuch_ws_scope: the layout, like pc_tables' after it, is the guarded one under the
-// canary option)
-int pc_knn_check(const char* what, const void* workspace, size_t workspace_bytes, int B, int Q, int N, int k)
+int pc_knn_check(const char* name, size_t workspace_bytes, int B, int Q, int N, int k)
 {
-    TUCH_REQUIRE(pc_sizes_ok(B, Q, N) && (long long)B * N * k < (1ll << 31), "%s: bad sizes B=%d Q=%d N=%d k=%d", what, B, Q, N,
+    TUCH_REQUIRE(pc_sizes_ok(B, Q, N) && (long long)B * N * k < (1ll << 31), "%s: bad sizes B=%d Q=%d N=%d k=%d", name, B, Q, N,
                  k);
-    const size_t need = pc_layout(B, Q, 1).total;
-    if (workspace_bytes < need) {
-        tuch_set_error("%s: workspace %zu < %zu bytes", what, workspace_bytes, need);
-        return TUCH_ERR_WORKSPACE;
-    }
-    return TUCH_OK;
+    return pc_workspace_check(name, workspace_bytes, B, Q);
 }
 
 }  // namespace
@@ -1206,14 +1244,13 @@ extern "C" int tuch_point_cloud_knn(const void* workspace, size_t workspace_byte
     TUCH_REQUIRE(workspace && points && queries && d2 && index, "tuch_point_cloud_knn: null pointer");
     TUCH_REQUIRE(k >= 1 && k <= 32, "tuch_point_cloud_knn: k = %d (1 .. 32)", k);
     tuch_ws_scope scope(g_pc_canary != 0);                     // alive up to the launch: pc_tables lays the regions out in it
-    const int rc = pc_knn_check("tuch_point_cloud_knn", workspace, workspace_bytes, B, Q, N, k);
+    const int rc = pc_knn_check("tuch_point_cloud_knn", workspace_bytes, B, Q, N, k);
     if (rc != TUCH_OK) return rc;
     (void)counts; (void)weights;        // (the build filed the valid points; the ABI keeps the triple together)
-    const float limit = max_distance > 0.0f ? fminf(max_distance * max_distance, kPcMaxD2) : kPcMaxD2;
     const int lanes = pc_knn_lanes(k);
     hipLaunchKernelGGL(pc_knn_kernel, dim3(ceil_div(N, lanes), B), dim3(lanes), (size_t)k * lanes * sizeof(unsigned long long),
                        (hipStream_t)stream, pc_tables((void*)workspace, workspace_bytes, B, Q), queries, shift, query_counts,
-                       limit, Q, N, k, d2, index);
+                       pc_limit(max_distance), Q, N, k, d2, index);
     return tuch_check_launch("tuch_point_cloud_knn");
 }
 
@@ -1229,15 +1266,14 @@ extern "C" int tuch_point_cloud_normals(const void* workspace, size_t workspace_
                  "tuch_point_cloud_normals: viewpoint layout %d (0 none, 1 [B,3], 2 [B,N,3]) with viewpoint %p", viewpoint_layout,
                  (const void*)viewpoint);
     tuch_ws_scope scope(g_pc_canary != 0);
-    const int rc = pc_knn_check("tuch_point_cloud_normals", workspace, workspace_bytes, B, Q, N, k);
+    const int rc = pc_knn_check("tuch_point_cloud_normals", workspace_bytes, B, Q, N, k);
     if (rc != TUCH_OK) return rc;
     (void)counts; (void)weights;
-    const float limit = max_distance > 0.0f ? fminf(max_distance * max_distance, kPcMaxD2) : kPcMaxD2;
     const int lanes = pc_knn_lanes(k);
     hipLaunchKernelGGL(pc_normals_kernel, dim3(ceil_div(N, lanes), B), dim3(lanes),
                        (size_t)k * lanes * sizeof(unsigned long long), (hipStream_t)stream,
-                       pc_tables((void*)workspace, workspace_bytes, B, Q), points, queries, shift, query_counts, limit, Q, N, k,
-                       viewpoint, viewpoint_layout, normals, variation, count, cov);
+                       pc_tables((void*)workspace, workspace_bytes, B, Q), points, queries, shift, query_counts,
+                       pc_limit(max_distance), Q, N, k, viewpoint, viewpoint_layout, normals, variation, count, cov);
     return tuch_check_launch("tuch_point_cloud_normals");
 }
 
@@ -1249,59 +1285,12 @@ extern "C" int tuch_point_cloud_fit_terms(const void* workspace, size_t workspac
                                           float* grad_verts, float* grad_transl, void* scratch, size_t scratch_bytes,
                                           void* stream)
 {
-    TUCH_REQUIRE(workspace && points && verts && transl && d2 && index && ticket && per_body && total && grad_verts &&
-                     grad_transl && scratch,
-                 "tuch_point_cloud_fit_terms: null pointer");
-    TUCH_REQUIRE(pc_sizes_ok(B, Q, V), "tuch_point_cloud_fit_terms: bad sizes B=%d Q=%d V=%d", B, Q, V);
-    TUCH_REQUIRE(vertex_weight_layout >= 0 && vertex_weight_layout <= 2 && (vertex_weight_layout == 0 || vertex_weights),
-                 "tuch_point_cloud_fit_terms: vertex weight layout %d (0 none, 1 [V], 2 [B,V]) with weights %p",
-                 vertex_weight_layout, (const void*)vertex_weights);
-    TUCH_REQUIRE(rho == TUCH_SCAN_RHO_SQUARED || rho == TUCH_SCAN_RHO_DISTANCE || (rho == TUCH_SCAN_RHO_GMOF && sigma > 0.0f),
-                 "tuch_point_cloud_fit_terms: rho %d (0 squared, 1 distance, 2 gmof with sigma > 0; sigma = %g)", rho,
-                 (double)sigma);
-    tuch_ws_scope scope(g_pc_canary != 0);
-    const size_t need = pc_layout(B, Q, 1).total;
-    const PcScratch sl = scope.record(0, [&] { return pc_scratch(B, V); });
-    if (workspace_bytes < need || scratch_bytes < sl.total) {
-        tuch_set_error("tuch_point_cloud_fit_terms: workspace %zu < %zu or scratch %zu < %zu bytes", workspace_bytes, need,
-                       scratch_bytes, sl.total);
-        return TUCH_ERR_WORKSPACE;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    const PcTables w = pc_tables((void*)workspace, workspace_bytes, B, Q);
-    scope.arm(scratch, (int32_t*)w.head, s);
-    const float limit = max_distance > 0.0f ? fminf(max_distance * max_distance, kPcMaxD2) : kPcMaxD2;
-    hipLaunchKernelGGL(pc_fit_kernel, dim3(ceil_div(V, kBlock), B), dim3(kBlock), 0, s, w, points, counts, weights, verts,
-                       transl, hint, limit, max_distance > 0.0f ? 1 : 0, B, Q, V, vertex_weights, vertex_weight_layout, rho,
-                       sigma * sigma, scale, d2, index, (float*)((char*)scratch + sl.partial), ticket, per_body, total,
-                       grad_verts, grad_transl);
-    return tuch_check_launch("tuch_point_cloud_fit_terms");
+    return pc_fit_terms("tuch_point_cloud_fit_terms", workspace, workspace_bytes, points, counts, weights, nullptr, 0.0f, PcMesh{},
+                        nullptr, 0, verts, transl, hint, max_distance, B, Q, V, vertex_weights, vertex_weight_layout, rho, sigma,
+                        scale, d2, index, ticket, per_body, total, grad_verts, grad_transl, scratch, scratch_bytes, stream);
 }
 
 // ------------------------------------------------------------------------------------------ the oriented entry points
-namespace {
-
-size_t pc_cone_words(int B, int R)
-{
-    const size_t c = (size_t)((R + 3) >> 2);
-    return (size_t)kCpCone + (size_t)B * c * c * c * kCpCone;
-}
-
-// what the oriented launches take; cones NULL: none
-PcOrient pc_orient(const float* normals, float max_angle_cos, const void* cones, size_t cones_bytes)
-{
-    PcOrient o;
-    o.normals = normals;
-    o.cones = (const uint32_t*)cones;
-    o.cone_cap = cones && cones_bytes >= 2 * kCpCone * sizeof(float) ? (long long)(cones_bytes / (kCpCone * sizeof(float))) - 1 : 0;
-    if (o.cone_cap == 0) o.cones = nullptr;
-    o.c = fminf(fmaxf(max_angle_cos, 0.0f), 1.0f);
-    o.c2 = o.c * o.c;
-    return o;
-}
-
-}  // namespace
-
 extern "C" size_t tuch_point_cloud_cones_bytes(int B, int resolution)
 {
     if (B <= 0 || resolution <= 0 || resolution > kMaxRes) return 0;
@@ -1334,22 +1323,12 @@ extern "C" int tuch_point_cloud_nearest_oriented(const void* workspace, size_t w
                                                  float max_angle_cos, const void* cones, size_t cones_bytes, int B, int Q,
                                                  int N, float* d2, int32_t* index, void* stream)
 {
-    TUCH_REQUIRE(workspace && points && normals && queries && query_normals && d2 && index,
-                 "tuch_point_cloud_nearest_oriented: null pointer");
-    TUCH_REQUIRE(pc_sizes_ok(B, Q, N), "tuch_point_cloud_nearest_oriented: bad sizes B=%d Q=%d N=%d", B, Q, N);
+    TUCH_REQUIRE(normals && query_normals, "tuch_point_cloud_nearest_oriented: null pointer");
     TUCH_REQUIRE(max_angle_cos >= 0.0f && max_angle_cos < 1.0f, "tuch_point_cloud_nearest_oriented: max_angle_cos %g (in [0, 1))",
                  (double)max_angle_cos);
-    tuch_ws_scope scope(g_pc_canary != 0);
-    const size_t need = pc_layout(B, Q, 1).total;
-    if (workspace_bytes < need) {
-        tuch_set_error("tuch_point_cloud_nearest_oriented: workspace %zu < %zu bytes", workspace_bytes, need);
-        return TUCH_ERR_WORKSPACE;
-    }
-    const float limit = max_distance > 0.0f ? fminf(max_distance * max_distance, kPcMaxD2) : kPcMaxD2;
-    hipLaunchKernelGGL(pc_nearest_oriented_kernel, dim3(ceil_div(N, kBlock), B), dim3(kBlock), 0, (hipStream_t)stream,
-                       pc_tables((void*)workspace, workspace_bytes, B, Q), pc_orient(normals, max_angle_cos, cones, cones_bytes),
-                       points, counts, weights, queries, query_normals, shift, query_counts, hint, limit, Q, N, d2, index);
-    return tuch_check_launch("tuch_point_cloud_nearest_oriented");
+    return pc_nearest("tuch_point_cloud_nearest_oriented", workspace, workspace_bytes, points, counts, weights, normals, queries,
+                      query_normals, shift, query_counts, hint, max_distance, max_angle_cos, cones, cones_bytes, B, Q, N, d2,
+                      index, stream);
 }
 
 extern "C" int tuch_point_cloud_fit_terms_oriented(const void* workspace, size_t workspace_bytes, const float* points,
@@ -1363,38 +1342,15 @@ extern "C" int tuch_point_cloud_fit_terms_oriented(const void* workspace, size_t
                                                    float* grad_verts, float* grad_transl, void* scratch, size_t scratch_bytes,
                                                    void* stream)
 {
-    TUCH_REQUIRE(workspace && points && normals && faces && vf_off && vf_ids && verts && transl && d2 && index && ticket &&
-                     per_body && total && grad_verts && grad_transl && scratch,
-                 "tuch_point_cloud_fit_terms_oriented: null pointer");
+    TUCH_REQUIRE(normals && faces && vf_off && vf_ids, "tuch_point_cloud_fit_terms_oriented: null pointer");
     TUCH_REQUIRE(pc_sizes_ok(B, Q, V) && F > 0 && (long long)F * 3 < (1ll << 31),
                  "tuch_point_cloud_fit_terms_oriented: bad sizes B=%d Q=%d V=%d F=%d", B, Q, V, F);
     TUCH_REQUIRE(max_angle_cos >= 0.0f && max_angle_cos < 1.0f,
                  "tuch_point_cloud_fit_terms_oriented: max_angle_cos %g (in [0, 1))", (double)max_angle_cos);
-    TUCH_REQUIRE(vertex_weight_layout >= 0 && vertex_weight_layout <= 2 && (vertex_weight_layout == 0 || vertex_weights),
-                 "tuch_point_cloud_fit_terms_oriented: vertex weight layout %d (0 none, 1 [V], 2 [B,V]) with weights %p",
-                 vertex_weight_layout, (const void*)vertex_weights);
-    TUCH_REQUIRE(rho == TUCH_SCAN_RHO_SQUARED || rho == TUCH_SCAN_RHO_DISTANCE || (rho == TUCH_SCAN_RHO_GMOF && sigma > 0.0f),
-                 "tuch_point_cloud_fit_terms_oriented: rho %d (0 squared, 1 distance, 2 gmof with sigma > 0; sigma = %g)", rho,
-                 (double)sigma);
-    tuch_ws_scope scope(g_pc_canary != 0);
-    const size_t need = pc_layout(B, Q, 1).total;
-    const PcScratch sl = scope.record(0, [&] { return pc_scratch(B, V); });
-    if (workspace_bytes < need || scratch_bytes < sl.total) {
-        tuch_set_error("tuch_point_cloud_fit_terms_oriented: workspace %zu < %zu or scratch %zu < %zu bytes", workspace_bytes,
-                       need, scratch_bytes, sl.total);
-        return TUCH_ERR_WORKSPACE;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    const PcTables w = pc_tables((void*)workspace, workspace_bytes, B, Q);
-    scope.arm(scratch, (int32_t*)w.head, s);
-    const float limit = max_distance > 0.0f ? fminf(max_distance * max_distance, kPcMaxD2) : kPcMaxD2;
-    const PcMesh mesh = {faces, vf_off, vf_ids, F};
-    hipLaunchKernelGGL(pc_fit_oriented_kernel, dim3(ceil_div(V, kBlock), B), dim3(kBlock), 0, s, w,
-                       pc_orient(normals, max_angle_cos, cones, cones_bytes), mesh, points, counts, weights, verts, transl,
-                       hint, limit, max_distance > 0.0f ? 1 : 0, B, Q, V, vertex_weights, vertex_weight_layout, rho,
-                       sigma * sigma, scale, d2, index, (float*)((char*)scratch + sl.partial), ticket, per_body, total,
-                       grad_verts, grad_transl);
-    return tuch_check_launch("tuch_point_cloud_fit_terms_oriented");
+    return pc_fit_terms("tuch_point_cloud_fit_terms_oriented", workspace, workspace_bytes, points, counts, weights, normals,
+                        max_angle_cos, PcMesh{faces, vf_off, vf_ids, F}, cones, cones_bytes, verts, transl, hint, max_distance, B,
+                        Q, V, vertex_weights, vertex_weight_layout, rho, sigma, scale, d2, index, ticket, per_body, total,
+                        grad_verts, grad_transl, scratch, scratch_bytes, stream);
 }
 
 extern "C" int tuch_point_cloud_grid(const void* workspace, int B, int resolution, float* origin_host, float* cell_host,

@@ -12,7 +12,7 @@
 //
 // Cost.  A vertex of a closed triangle mesh has six faces on average: 6 x 9 floats gathered from rows its neighbours
 // read too (SMPL: 83 KB of vertices per body, resident in L2), 3 floats written.  The launch is bound by its latency
-// at SMPL's size (B x 6890 lanes); pc_fit_oriented_kernel (point_cloud.hip) calls vn_vertex_normal itself and needs no
+// at SMPL's size (B x 6890 lanes); pc_fit_kernel<true> (point_cloud.hip) calls vn_vertex_normal itself and needs no
 // launch of this kernel.
 #include "face_normal.h"
 
