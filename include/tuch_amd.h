@@ -261,7 +261,10 @@ void tuch_contact_model_destroy(tuch_contact_model* model);
  * seg_splits, seg_fused, seg_assist (fixed at create), hd_search, hd_search_waves, hd_overlap, canary.  (Deterministic mode is process-wide: tuch_set_deterministic.)  The environment variables TUCH_<NAME> are read ONCE, by
  * tuch_contact_model_create; afterwards only set_option changes a model's switches -- no hot call looks at the
  * environment, so a captured hipGraph cannot depend on it.  (The workspace sizes depend on ray_pair_cap and canary:
- * query *_workspace_bytes again after changing them.) */
+ * query *_workspace_bytes again after changing them.)
+ * hd_search_waves (wavefronts per block of 64 columns in the matrix-core search of the HD branch) has three forms, 4, 2
+ * and 1; any other value is accepted and mapped silently: >= 4 runs the form with 4, 2 or 3 the form with 2, anything
+ * below 2 (0 and negative values included) the form with 1.  get_option returns the value as it was set. */
 int tuch_contact_model_set_option(tuch_contact_model* model, const char* name, int value);
 int tuch_contact_model_get_option(const tuch_contact_model* model, const char* name, int* value);
 /* Option canary = 1 (debug): every region of every workspace of the model's hot calls (nearest-vertex search, inside

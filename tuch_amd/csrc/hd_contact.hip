@@ -213,8 +213,13 @@ struct Term { float value, dd; };
 __device__ __forceinline__ Term contact_term(float d, bool exterior)
 {
     const float weight = exterior ? 0.005f : 1.0f, scale = exterior ? 0.005f : 0.04f;
-    const float th = tanhf(d / scale);
-    Term t = {weight * th * th, 2.0f * weight * th * (1.0f - th * th) / scale};
+    const float x = d / scale;
+    const float th = tanhf(x);
+    // d tanh^2 = 2 th sech^2 with sech^2 = 4 e / (1 + e)^2, e = exp(-2x) -- not 1 - th * th: for a saturated term (x > 6)
+    // that difference is a small multiple of 2^-23, the slope comes out quantised (off by up to its own size), and a vertex
+    // that supports hundreds of HD points adds hundreds of those errors up (the forward value does not use it)
+    const float e = expf(-2.0f * x), sech2 = 4.0f * e / ((1.0f + e) * (1.0f + e));
+    Term t = {weight * th * th, 2.0f * weight * th * sech2 / scale};
     return t;
 }
 
