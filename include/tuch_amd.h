@@ -295,8 +295,12 @@ int tuch_winding_tree_work(const tuch_contact_model* model, const float* verts, 
 
 /* Measurement aid for the ray-crossing inside test (csrc/ray_winding.hip) that tuch_exterior_flags and
  * tuch_winding_points use when only the flags are wanted: out_host[4] = {strip elements stepped through by all
- * wavefronts (64 queries each), (ray, element) pairs whose ray passes the slabs of the element's leaf, 64 x elements
- * listed, wavefronts}: [1] / [2] is the share of lanes that can have a crossing at all.  Workspace as for tuch_exterior_flags.  Synchronises the stream. */
+ * passes, (ray, element) pairs whose ray passes the slabs of the element's leaf, 64 x elements listed, passes}: [1] /
+ * [2] is the share of lanes that can have a crossing at all.  A pass is one wavefront's walk of one leaf's strip for one
+ * tile of that leaf's rays, counted over all B bodies: a leaf with c >= 64 rays has c / 64 tiles, the last of which
+ * carries the c % 64 rays left over as a second ray set of the same pass; a leaf with 0 < c < 64 rays has one.  [0]
+ * counts a pass's strip once, whether the pass holds one ray set or two (a second set filters the strip once more
+ * without fetching or staging it again).  Workspace as for tuch_exterior_flags.  Synchronises the stream. */
 int tuch_ray_work(const tuch_contact_model* model, const float* verts, int B, void* workspace,
                   size_t workspace_bytes, unsigned long long* out_host, void* stream);
 /* FOR THE TESTS ONLY (tests/test_near_encode.py, tests/test_gpu_near_lists.py): the numbers and the lists of the inside

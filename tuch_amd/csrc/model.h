@@ -51,7 +51,7 @@ struct tuch_options {
     int winding_tree = 1;       // 0: flat strip walk instead of the cluster tree
     int tree_waves = 32768;     // frontier choice of the solid-angle walk (128-query blocks)
     int ray_pair_cap = 16;      // (ray, leaf) pairs per query the pair list has room for
-    int ray_waves = 32768;      // wavefronts of the crossing kernel
+    int ray_waves = 16384;      // wavefronts of the crossing kernel (ray_winding.hip: full_layout)
     int v2v_tree = 1;           // 0: all-rows nearest-vertex search (v2v_partial_kernel), the reference of the tests
     int v2v_waves = 0;          // frontier choice of the search (wavefronts aimed at; 0: the form's own default)
     int v2v_pairs = 24;         // scan: a leaf in reach of FEWER columns of the wavefront than this is not walked row by row for all 64 lanes; its (leaf, column) pairs are queued and evaluated one per lane (round 5); 0: every leaf row by row (round 4)
@@ -68,10 +68,13 @@ void tuch_options_from_env(tuch_options* o);
 // Inside test by signed ray crossings (ray_winding.hip): exterior flags of the model's own vertices / of arbitrary
 // points, identical to thresholding the winding-number sum wherever that sum is well separated from the threshold.
 bool tuch_ray_available(const tuch_contact_model* m);
-// (query block, leaf) entries -> the rays of every leaf, in tiles of 64 (ray_winding.hip: ray_near_kernel's lists regrouped
+// (query block, leaf) entries -> the rays of every leaf, in tiles (ray_winding.hip: ray_near_kernel's lists regrouped
 // by ray_tiles_fill_kernel)
 struct RayEntry { int32_t leaf, node; uint32_t mask_lo, mask_hi; };   // which of the block's 64 lanes
-struct RayTile { int32_t ex_off, ex_len, first, n; };                 // n <= 64 slots pairs[first ..] of one leaf
+// n slots pairs[first ..] of one leaf.  A leaf with c >= 64 rays has c / 64 tiles of 64, the last of which carries the
+// remainder as well (64 <= n <= 127: lanes hold pairs[first + l] and, for l < n - 64, pairs[first + 64 + l]); a leaf
+// with 0 < c < 64 rays has one tile of n = c (ray_tile_count)
+struct RayTile { int32_t ex_off, ex_len, first, n; };
 struct RayBody { int32_t tiles, overflow; };
 struct TreeNode;
 // computes the layout of tuch_ray_exterior_verts (Q = 0) / tuch_ray_exterior_points: for a recording tuch_ws_scope
