@@ -216,6 +216,30 @@ def test_captured_loop_equals_eager_loop(smpl, monkeypatch):
     assert torch.equal(target, kept[0]) and torch.equal(go, kept[1])            # inputs are never modified
 
 
+def test_at_most_four_captured_sessions_are_kept(smpl, monkeypatch):
+    """Five batch sizes are five sessions: the first one's goes when the fifth is stored.  A kept session only replays; an
+    evicted one is captured again (three eager iterations, two replays) and gives a fresh fitter's bits."""
+    monkeypatch.setenv('TUCH_GRAPH_STRICT', '1')
+    from tuch_amd.fit import MeshFitter
+    c = mc.fit_inputs()
+    target, go = _dev(c['target']), _dev(c['global_orient'])
+    assert target.shape[0] == mc.FIT_BATCH == 5
+    fitter = MeshFitter(smpl, num_iters=5)
+    assert fitter.graph_strict and fitter.keep_sessions
+    for k in range(1, 6):
+        fitter(target[:k], go[:k])
+        assert fitter.graph_replayed == {'fit': 2} and len(fitter._sessions) == min(k, 4)
+    assert [key[0] for key in fitter._sessions] == [2, 3, 4, 5]
+    fitter(target, go)
+    assert fitter.graph_replayed == {'fit': 5} and len(fitter._sessions) == 4              # kept: replays only
+    again = fitter(target[:1], go[:1])
+    assert fitter.graph_replayed == {'fit': 2}                                              # evicted: captured again
+    assert [key[0] for key in fitter._sessions] == [3, 4, 5, 1]
+    fresh = MeshFitter(smpl, num_iters=5)(target[:1], go[:1])
+    for name, a, b in zip(again._fields, again, fresh):
+        assert torch.equal(a, b), name
+
+
 def test_fit_global_orient(smpl):
     go = mc.perturbed_orient()
     _, start = _fit(smpl, 0, global_orient=go, fit_global_orient=True)

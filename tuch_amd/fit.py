@@ -6,69 +6,105 @@ The reference fits ``body_pose``, ``betas`` and ``transl`` of ONE body with Adam
 objective is the SUM of the bodies' terms, so every body's gradient -- and with Adam's element-wise update its whole
 trajectory -- is that of the reference's batch-1 loop.  One iteration is the body model's forward pass, the data term with
 its gradients as one launch (ops.vertex_fit), the backward pass from the cached unit seed (ops.backward_scalar) and Adam as
-one launch (optim.make_adam); the loop is run by the package's one loop runner (SMPLifyDC._Stage: three eager
+one launch (optim.make_adam); the loop is run by the package's one loop runner (fit_loop.Stage: three eager
 iterations, capture, replay as a hipGraph), and sessions -- the static tensors plus the captured loop -- are kept between
-calls like SMPLifyDC's.  ``TUCH_GRAPH_STRICT`` and ``TUCH_SMPLIFY_SESSIONS`` mean what they mean there.
+calls like SMPLifyDC's (fit_loop.LoopOwner).  ``TUCH_GRAPH_STRICT`` and ``TUCH_SMPLIFY_SESSIONS`` mean what they mean there.
+What the two fitters share -- the body's parameter buffers, their seeding and checks, the result clones -- is BodyFitter.
 
 Constructing needs no device; calling does.  There is no host fallback.
 """
 from __future__ import annotations
 
-import contextlib
-import os
 from collections import namedtuple
 
 import torch
 
 from . import ops
-from .smplify.smplifydc import SMPLifyDC
+from .fit_loop import LoopOwner, Stage
 
 MeshFit = namedtuple('MeshFit', ['global_orient', 'body_pose', 'betas', 'transl', 'vertices', 'loss'])
 
 
-class MeshFitter:
+def _posed(smpl, t):
+    """The body model's vertices [B,V,3] (without the translation) at a session's parameter tensors."""
+    return smpl(global_orient=t['global_orient'], body_pose=t['body_pose'], betas=t['betas']).vertices
+
+
+class BodyFitter(LoopOwner):
+    """What MeshFitter and ScanFitter share: a body model whose ``body_pose``, ``betas``, ``transl`` (and ``global_orient``
+    with ``fit_global_orient``) are fitted by one loop called 'fit'.  With ``record_history`` the objective and the
+    parameters *before* every update are kept in ``self.history['fit']``, the parameters in the optimiser's order:
+    body_pose, betas, transl (, global_orient)."""
+
+    def __init__(self, smpl, step_size, num_iters, fit_global_orient, use_graph, record_history):
+        self.smpl = smpl
+        self.fit_global_orient = fit_global_orient
+        self._init_loops(step_size, num_iters, use_graph, record_history)
+
+    def _check_shapes(self, *named):
+        """Each of ``named`` is (name, tensor or None, the shape it must have)."""
+        for name, value, shape in named:
+            if value is not None and tuple(value.shape) != shape:
+                raise ValueError('%s: %s has shape %s, expected %s' % (type(self).__name__, name, tuple(value.shape), shape))
+
+    def _to_device(self, device):
+        if device.type != 'cuda':
+            raise RuntimeError('%s runs on a HIP device (there is no host fallback); got tensors on %s'
+                               % (type(self).__name__, device))
+        if self.smpl.v_template.device != device:
+            self.smpl = self.smpl.to(device)
+
+    @staticmethod
+    def _parameters(batch, device):
+        """The static parameter tensors every session starts its ``t`` with."""
+        z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=device)
+        return dict(body_pose=z(batch, 69), betas=z(batch, 10), transl=z(batch, 3), global_orient=z(batch, 3))
+
+    def _stage(self, t, iteration):
+        """The 'fit' loop over the fitted parameters of ``t`` (smplxtosmpl_mtp.py:82-85)."""
+        params = [t['body_pose'], t['betas'], t['transl']] + ([t['global_orient']] if self.fit_global_orient else [])
+        for p in params:
+            p.requires_grad = True
+        return Stage(self, 'fit', params, iteration, {})
+
+    @staticmethod
+    def _seed(t, body_pose, betas):
+        for name, value in (('body_pose', body_pose), ('betas', betas)):
+            t[name].zero_() if value is None else t[name].copy_(value)
+
+    @staticmethod
+    def _fitted(t):
+        """The caller's own copies of the parameters, in the order the result tuples begin with."""
+        return tuple(t[name].detach().clone() for name in ('global_orient', 'body_pose', 'betas', 'transl'))
+
+
+class MeshFitter(BodyFitter):
     """``MeshFitter(smpl)(target_vertices, global_orient)`` -> MeshFit.  ``vertices`` [B,V,3] include the translation,
     ``loss`` [B] is every body's term after the last update.  ``global_orient`` is held fixed (the reference passes it in
     on every call, :95-98) unless ``fit_global_orient`` is set.  Inputs are never modified."""
 
     def __init__(self, smpl, step_size=1e-2, num_iters=5000, fit_global_orient=False, use_graph=True, record_history=False):
-        self.smpl = smpl
-        self.step_size = step_size
-        self.num_iters = num_iters
-        self.fit_global_orient = fit_global_orient
-        self.use_graph = use_graph
-        # measurement / test aid: the objective and the parameters *before* every update are kept in self.history['fit'],
-        # the parameters in the optimiser's order: body_pose, betas, transl (, global_orient)
-        self.record_history = record_history
-        self.graph_strict = os.environ.get('TUCH_GRAPH_STRICT', '0') == '1'
-        self.keep_sessions = os.environ.get('TUCH_SMPLIFY_SESSIONS', '1') != '0'
-        self.history = None
-        self.graph_replayed = {}
-        self._sessions = {}
+        super().__init__(smpl, step_size, num_iters, fit_global_orient, use_graph, record_history)
 
     def _session(self, batch, num_verts, vertex_weights, device):
-        """(key, session): the static tensors, the iteration closure and the loop of a fit with these constants."""
+        """(key, session) of a fit with these constants: the stored one, or a new one (``_build``)."""
         # everything the captured loop bakes in; the session keeps the weights alive, so their id cannot be reused
         key = (batch, num_verts, id(vertex_weights) if vertex_weights is not None else None, device.index,
                float(self.step_size), bool(self.fit_global_orient), bool(self.record_history))
-        sess = self._sessions.get(key)
-        if sess is not None:
-            return key, sess
-        z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=device)
-        t = dict(body_pose=z(batch, 69), betas=z(batch, 10), transl=z(batch, 3), global_orient=z(batch, 3),
-                 target=z(batch, num_verts, 3))
+        return key, self._session_for(key, self._build, batch, num_verts, vertex_weights, device)
+
+    def _build(self, batch, num_verts, vertex_weights, device):
+        """A session: the static tensors, the iteration closure and the loop."""
+        t = self._parameters(batch, device)
+        t['target'] = torch.zeros(batch, num_verts, 3, dtype=torch.float32, device=device)
         weights = None if vertex_weights is None else ops.fit_weights(vertex_weights, num_verts, device)
         smpl = self.smpl
 
         def iteration():
-            out = smpl(global_orient=t['global_orient'], body_pose=t['body_pose'], betas=t['betas'])
-            total, _ = ops.vertex_fit(out.vertices, t['transl'], t['target'], weights)
-            return total, out.vertices
-        params = [t['body_pose'], t['betas'], t['transl']] + ([t['global_orient']] if self.fit_global_orient else [])   # :82-85
-        for p in params:
-            p.requires_grad = True
-        sess = dict(t=t, weights=weights, keys_alive=(vertex_weights,), stage=SMPLifyDC._Stage(self, 'fit', params, iteration, {}))
-        return key, sess
+            verts = _posed(smpl, t)
+            total, _ = ops.vertex_fit(verts, t['transl'], t['target'], weights)
+            return total, verts
+        return dict(t=t, weights=weights, keys_alive=(vertex_weights,), stage=self._stage(t, iteration))
 
     def __call__(self, target_vertices, global_orient, body_pose=None, betas=None, transl=None, vertex_weights=None):
         smpl_verts = int(self.smpl.v_template.shape[0])
@@ -76,65 +112,46 @@ class MeshFitter:
             raise ValueError('MeshFitter: target_vertices must be [B,%d,3] (the body model\'s topology), got %s'
                              % (smpl_verts, tuple(target_vertices.shape)))
         batch = target_vertices.shape[0]
-        for name, value, width in (('global_orient', global_orient, 3), ('body_pose', body_pose, 69), ('betas', betas, 10),
-                                   ('transl', transl, 3)):
-            if value is not None and tuple(value.shape) != (batch, width):
-                raise ValueError('MeshFitter: %s has shape %s, expected %s' % (name, tuple(value.shape), (batch, width)))
+        self._check_shapes(('global_orient', global_orient, (batch, 3)), ('body_pose', body_pose, (batch, 69)),
+                           ('betas', betas, (batch, 10)), ('transl', transl, (batch, 3)))
         device = target_vertices.device
-        if device.type != 'cuda':
-            raise RuntimeError('MeshFitter runs on a HIP device (there is no host fallback); got tensors on %s' % device)
-        if self.smpl.v_template.device != device:
-            self.smpl = self.smpl.to(device)
-        on_gpu = bool(self.use_graph)
-        capture = on_gpu and self.num_iters > 4
-        if self.record_history:
-            self.history = {'fit': []}
-        # graph replays never run on the NULL stream (ops.py)
-        with ops.off_default_stream(device) if on_gpu else contextlib.nullcontext():
+        self._to_device(device)
+        with self._loops(device, bool(self.use_graph), 'fit') as capture:
             key, sess = self._session(batch, smpl_verts, vertex_weights, device)
             t, weights = sess['t'], sess['weights']
             with torch.no_grad():
                 t['target'].copy_(target_vertices)
                 t['global_orient'].copy_(global_orient)
-                for name, value in (('body_pose', body_pose), ('betas', betas)):
-                    t[name].zero_() if value is None else t[name].copy_(value)
+                self._seed(t, body_pose, betas)
                 if transl is not None:
                     t['transl'].copy_(transl)
                 else:                          # :70-71, over the vertices that carry weight (their targets may be non-finite)
-                    verts = self.smpl(global_orient=t['global_orient'], body_pose=t['body_pose'], betas=t['betas']).vertices
+                    verts = _posed(self.smpl, t)
                     if weights is None:
                         t['transl'].copy_(t['target'].mean(1) - verts.mean(1))
                     else:
                         used = (weights.tensor != 0)[None, :, None]
                         gap = torch.where(used, t['target'] - verts, torch.zeros_like(verts))
                         t['transl'].copy_(gap.sum(1) / used.sum())
-            captured = sess['stage'].run(self.num_iters, None, capture)
-            # a captured loop is kept for the next call; a session that ran eagerly (or lost its capture) is dropped
-            if not (captured and self.keep_sessions):
-                self._sessions.pop(key, None)
-            elif key not in self._sessions:
-                while len(self._sessions) >= 4:
-                    self._sessions.pop(next(iter(self._sessions)))
-                self._sessions[key] = sess
+            self._settle(key, sess, sess['stage'].run(self.num_iters, None, capture))
             with torch.no_grad():
-                verts = self.smpl(global_orient=t['global_orient'], body_pose=t['body_pose'], betas=t['betas']).vertices
+                verts = _posed(self.smpl, t)
                 _, loss = ops.vertex_fit(verts, t['transl'], t['target'], weights)
                 vertices = verts + t['transl'][:, None]
-            own = lambda x: x.detach().clone()
-            return MeshFit(own(t['global_orient']), own(t['body_pose']), own(t['betas']), own(t['transl']), vertices, loss)
+            return MeshFit(*self._fitted(t), vertices, loss)
 
 
 ScanFit = namedtuple('ScanFit', ['global_orient', 'body_pose', 'betas', 'transl', 'vertices', 'loss', 'face', 'bary'])
 CloudFit = namedtuple('CloudFit', ['loss', 'd2', 'index'])
 
 
-class ScanFitter:
+class ScanFitter(BodyFitter):
     """Fit SMPL to unregistered points -- a scan, a depth point cloud, a mesh of another topology: ``ScanFitter(smpl,
     model)(points [B,Q,3], global_orient)`` -> ScanFit.  ``model`` is a ``ContactModel`` over the body model's faces (no
     geodesic mask is needed).  The data term is ops.scan_fit: every real point's distance to the nearest point of the posed,
     translated mesh under ``rho`` ('distance', 'squared' or 'gmof' with ``sigma``), averaged per body with ``weights``
     [B,Q]; ``counts`` [B] marks how many points per body are real.  The loop is MeshFitter's: body model forward, the term
-    with its gradients as one call, backward from the cached unit seed, Adam as one launch, run by SMPLifyDC._Stage and kept
+    with its gradients as one call, backward from the cached unit seed, Adam as one launch, run by fit_loop.Stage and kept
     as a session (at most four; ``TUCH_GRAPH_STRICT`` and ``TUCH_SMPLIFY_SESSIONS`` as there).
 
     ``use_hint``: the session holds a [B,Q] int32 tensor that is both the search's hint and where it writes its faces, so
@@ -194,18 +211,13 @@ class ScanFitter:
                  use_hint=True, use_graph=True, record_history=False, model_to_scan=0.0, vertex_weights=None,
                  max_distance=None, resolution=64, max_normal_angle=None, estimate_normals=None,
                  model_to_scan_normals=False):
-        if rho not in ops.SCAN_RHO:
-            raise ValueError('ScanFitter: rho must be one of %s, got %r' % (sorted(ops.SCAN_RHO), rho))
-        if rho == 'gmof' and not (sigma is not None and float(sigma) > 0.0):
-            raise ValueError("ScanFitter: rho='gmof' needs sigma > 0, got %r" % (sigma,))
+        ops._rho_of('ScanFitter', rho, sigma)
         if not float(model_to_scan) >= 0.0:
             raise ValueError('ScanFitter: model_to_scan must be >= 0, got %r' % (model_to_scan,))
-        if max_distance is not None and not float(max_distance) > 0.0:
-            raise ValueError('ScanFitter: max_distance must be > 0 (or None), got %r' % (max_distance,))
-        if max_normal_angle is not None and not (0.0 < float(max_normal_angle) <= 90.0):
-            raise ValueError('ScanFitter: max_normal_angle must be in (0, 90] degrees (or None), got %r' % (max_normal_angle,))
-        if not (isinstance(resolution, int) and 1 <= resolution <= 256):
-            raise ValueError('ScanFitter: resolution must be an int in 1 .. 256, got %r' % (resolution,))
+        ops._tau_of('ScanFitter', max_distance)
+        if max_normal_angle is not None:
+            max_normal_angle = ops._angle_of('ScanFitter', 'max_normal_angle', max_normal_angle)
+        ops._resolution_of('ScanFitter', resolution)
         if estimate_normals is not None:
             ops._check_k('ScanFitter: estimate_normals', estimate_normals)
             if max_normal_angle is None:
@@ -216,33 +228,21 @@ class ScanFitter:
         if vertex_weights is not None and (not torch.is_tensor(vertex_weights) or vertex_weights.dim() not in (1, 2)
                                            or vertex_weights.shape[-1] != num_verts):
             raise ValueError('ScanFitter: vertex_weights must be a [%d] or [B,%d] tensor' % (num_verts, num_verts))
-        self.smpl = smpl
+        super().__init__(smpl, step_size, num_iters, fit_global_orient, use_graph, record_history)
         self.model = model
-        self.step_size = step_size
-        self.num_iters = num_iters
-        self.fit_global_orient = fit_global_orient
         self.rho, self.sigma = rho, sigma
         self.use_hint = use_hint
         self.model_to_scan = float(model_to_scan)
         self.vertex_weights = vertex_weights
         self.max_distance = None if max_distance is None else float(max_distance)
         self.resolution = resolution
-        self.max_normal_angle = None if max_normal_angle is None else float(max_normal_angle)
+        self.max_normal_angle = max_normal_angle
         self.estimate_normals = estimate_normals
         self.model_to_scan_normals = bool(model_to_scan_normals)
         self.model_to_scan_result = None
-        self.use_graph = use_graph
-        # as MeshFitter: the objective and the parameters *before* every update in self.history['fit'], the parameters in
-        # the optimiser's order: body_pose, betas, transl (, global_orient)
-        self.record_history = record_history
-        self.graph_strict = os.environ.get('TUCH_GRAPH_STRICT', '0') == '1'
-        self.keep_sessions = os.environ.get('TUCH_SMPLIFY_SESSIONS', '1') != '0'
-        self.history = None
-        self.graph_replayed = {}
-        self._sessions = {}
 
     def _session(self, batch, num_points, with_counts, with_weights, device, with_normals=False):
-        """(key, session): the static tensors, the iteration closure and the loop of a fit with these constants."""
+        """(key, session) of a fit with these constants: the stored one, or a new one (``_build``)."""
         key = (batch, num_points, bool(with_counts), bool(with_weights), device.index, float(self.step_size),
                bool(self.fit_global_orient), self.rho, None if self.sigma is None else float(self.sigma), bool(self.use_hint),
                bool(self.record_history), self.model_to_scan,
@@ -250,12 +250,13 @@ class ScanFitter:
                bool(with_normals), self.max_normal_angle if with_normals else None)
         if self.model_to_scan_normals:           # (with the flag off the key is the one it has always been)
             key += ('model_to_scan_normals',)
-        sess = self._sessions.get(key)
-        if sess is not None:
-            return key, sess
+        return key, self._session_for(key, self._build, batch, num_points, with_counts, with_weights, device, with_normals)
+
+    def _build(self, batch, num_points, with_counts, with_weights, device, with_normals):
+        """A session: the static tensors, the iteration closure and the loop."""
         z = lambda *shape, dtype=torch.float32: torch.zeros(*shape, dtype=dtype, device=device)
-        t = dict(body_pose=z(batch, 69), betas=z(batch, 10), transl=z(batch, 3), global_orient=z(batch, 3),
-                 points=z(batch, num_points, 3), hint=z(batch, num_points, dtype=torch.int32),
+        t = self._parameters(batch, device)
+        t.update(points=z(batch, num_points, 3), hint=z(batch, num_points, dtype=torch.int32),
                  counts=z(batch, dtype=torch.int32) if with_counts else None,
                  weights=z(batch, num_points) if with_weights else None,
                  normals=z(batch, num_points, 3) if with_normals else None)
@@ -280,62 +281,46 @@ class ScanFitter:
                                                                               device)) if self.model_to_scan_normals else {}
 
         def iteration():
-            out = smpl(global_orient=t['global_orient'], body_pose=t['body_pose'], betas=t['betas'])
+            verts = _posed(smpl, t)
             # (the hint tensor receives the new faces: the aliasing tuch_closest_point_hinted allows)
-            total, _, _ = ops.scan_fit(model, out.vertices, t['transl'], t['points'], t['counts'], t['weights'], hint,
+            total, _, _ = ops.scan_fit(model, verts, t['transl'], t['points'], t['counts'], t['weights'], hint,
                                        self.rho, self.sigma, face_out=hint, normals=t['normals'], max_angle=angle)
             if cloud is not None:
                 # the two vertex gradients meet in autograd's accumulation (one add of [B,V,3])
-                other, _, _ = ops.cloud_fit(cloud, out.vertices, t['transl'], vw, near, self.rho, self.sigma,
+                other, _, _ = ops.cloud_fit(cloud, verts, t['transl'], vw, near, self.rho, self.sigma,
                                             self.max_distance, self.model_to_scan, index_out=near, **oriented)
                 total = total + other
-            return total, out.vertices
-        params = [t['body_pose'], t['betas'], t['transl']] + ([t['global_orient']] if self.fit_global_orient else [])
-        for p in params:
-            p.requires_grad = True
-        sess = dict(t=t, cloud=cloud, normals_cloud=None, vertex_weights=vw, keys_alive=(self.vertex_weights,), oriented=oriented,
-                    stage=SMPLifyDC._Stage(self, 'fit', params, iteration, {}))
-        return key, sess
+            return total, verts
+        return dict(t=t, cloud=cloud, normals_cloud=None, vertex_weights=vw, keys_alive=(self.vertex_weights,), oriented=oriented,
+                    stage=self._stage(t, iteration))
 
     def __call__(self, points, global_orient, counts=None, weights=None, body_pose=None, betas=None, transl=None,
                  normals=None, viewpoint=None):
         if points.dim() != 3 or points.shape[2] != 3 or points.shape[0] == 0 or points.shape[1] == 0:
             raise ValueError('ScanFitter: points must be [B,Q,3], got %s' % (tuple(points.shape),))
         batch, num_points = points.shape[0], points.shape[1]
-        for name, value, shape in (('global_orient', global_orient, (batch, 3)), ('body_pose', body_pose, (batch, 69)),
-                                   ('betas', betas, (batch, 10)), ('transl', transl, (batch, 3)), ('counts', counts, (batch,)),
-                                   ('weights', weights, (batch, num_points))):
-            if value is not None and tuple(value.shape) != shape:
-                raise ValueError('ScanFitter: %s has shape %s, expected %s' % (name, tuple(value.shape), shape))
+        self._check_shapes(('global_orient', global_orient, (batch, 3)), ('body_pose', body_pose, (batch, 69)),
+                           ('betas', betas, (batch, 10)), ('transl', transl, (batch, 3)), ('counts', counts, (batch,)),
+                           ('weights', weights, (batch, num_points)))
         if normals is not None and self.max_normal_angle is None:
             raise ValueError('ScanFitter: normals need max_normal_angle (the fitter was created without it)')
-        if normals is not None and tuple(normals.shape) != (batch, num_points, 3):
-            raise ValueError('ScanFitter: normals has shape %s, expected %s' % (tuple(normals.shape), (batch, num_points, 3)))
+        self._check_shapes(('normals', normals, (batch, num_points, 3)))
         if self.estimate_normals is not None and normals is not None:
             raise ValueError('ScanFitter: normals were passed to a fitter that estimates them (estimate_normals=%d)'
                              % self.estimate_normals)
         if viewpoint is not None and self.estimate_normals is None:
             raise ValueError('ScanFitter: viewpoint needs estimate_normals (the fitter was created without it)')
-        if viewpoint is not None and tuple(viewpoint.shape) != (batch, 3):
-            raise ValueError('ScanFitter: viewpoint has shape %s, expected %s' % (tuple(viewpoint.shape), (batch, 3)))
+        self._check_shapes(('viewpoint', viewpoint, (batch, 3)))
         with_normals = normals is not None or self.estimate_normals is not None
         if self.model_to_scan_normals and not with_normals:
             raise ValueError('ScanFitter: model_to_scan_normals needs normals at the call (pass normals= or create the '
                              'fitter with estimate_normals)')
         device = points.device
-        if device.type != 'cuda':
-            raise RuntimeError('ScanFitter runs on a HIP device (there is no host fallback); got tensors on %s' % device)
+        self._to_device(device)
         if int(self.model.num_verts) != int(self.smpl.v_template.shape[0]):
             raise ValueError('ScanFitter: the ContactModel has %d vertices, the body model %d'
                              % (self.model.num_verts, self.smpl.v_template.shape[0]))
-        if self.smpl.v_template.device != device:
-            self.smpl = self.smpl.to(device)
-        on_gpu = bool(self.use_graph)
-        capture = on_gpu and self.num_iters > 4
-        if self.record_history:
-            self.history = {'fit': []}
-        # graph replays never run on the NULL stream (ops.py)
-        with ops.off_default_stream(device) if on_gpu else contextlib.nullcontext():
+        with self._loops(device, bool(self.use_graph), 'fit') as capture:
             key, sess = self._session(batch, num_points, counts is not None, weights is not None, device, with_normals)
             t = sess['t']
             with torch.no_grad():
@@ -348,12 +333,11 @@ class ScanFitter:
                     t['weights'].copy_(weights)
                 if normals is not None:
                     t['normals'].copy_(normals)
-                for name, value in (('body_pose', body_pose), ('betas', betas)):
-                    t[name].zero_() if value is None else t[name].copy_(value)
+                self._seed(t, body_pose, betas)
                 if transl is not None:
                     t['transl'].copy_(transl)
                 else:               # the centroid of each body's real, weighted points minus that of its initial vertices
-                    verts = self.smpl(global_orient=t['global_orient'], body_pose=t['body_pose'], betas=t['betas']).vertices
+                    verts = _posed(self.smpl, t)
                     w = torch.ones(batch, num_points, device=device) if weights is None else t['weights'].clone()
                     if counts is not None:
                         w = w * (torch.arange(num_points, device=device)[None] < t['counts'][:, None])
@@ -379,16 +363,9 @@ class ScanFitter:
                 if self.model_to_scan_normals:
                     # after the rebuild (which drops them) and after the buffer holds this call's normals
                     sess['cloud'].orient(t['normals'])
-            captured = sess['stage'].run(self.num_iters, None, capture)
-            # a captured loop is kept for the next call; a session that ran eagerly (or lost its capture) is dropped
-            if not (captured and self.keep_sessions):
-                self._sessions.pop(key, None)
-            elif key not in self._sessions:
-                while len(self._sessions) >= 4:
-                    self._sessions.pop(next(iter(self._sessions)))
-                self._sessions[key] = sess
+            self._settle(key, sess, sess['stage'].run(self.num_iters, None, capture))
             with torch.no_grad():
-                verts = self.smpl(global_orient=t['global_orient'], body_pose=t['body_pose'], betas=t['betas']).vertices
+                verts = _posed(self.smpl, t)
                 hint = t['hint'] if self.use_hint else None
                 _, loss, near = ops.scan_fit(self.model, verts, t['transl'], t['points'], t['counts'], t['weights'], hint,
                                              self.rho, self.sigma, normals=t['normals'],
@@ -400,6 +377,4 @@ class ScanFitter:
                                                     t['near'] if self.use_hint else None, self.rho, self.sigma,
                                                     self.max_distance, self.model_to_scan, **sess['oriented'])
                     self.model_to_scan_result = CloudFit(other, found.d2, found.index)
-            own = lambda x: x.detach().clone()
-            return ScanFit(own(t['global_orient']), own(t['body_pose']), own(t['betas']), own(t['transl']), vertices, loss,
-                           near.face, near.bary)
+            return ScanFit(*self._fitted(t), vertices, loss, near.face, near.bary)

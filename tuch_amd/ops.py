@@ -1561,14 +1561,9 @@ def _hint_of(hint, points, what):
 def _max_angle_cos(normals, max_angle, points, what):
     """None without normals and angle; otherwise the float32 cosine the C entry points take: cos(max_angle) in double,
     rounded once.  One of the two alone, an angle outside (0, 90] degrees or normals of another shape raise ValueError."""
-    if normals is None and max_angle is None:
+    if not _both(what, 'normals', normals, 'max_angle', max_angle):
         return None
-    if normals is None or max_angle is None:
-        raise ValueError('%s: normals and max_angle go together, got %s' % (what, 'normals only' if max_angle is None
-                                                                             else 'max_angle only'))
-    angle = float(max_angle)
-    if not (0.0 < angle <= 90.0):
-        raise ValueError('%s: max_angle must be in (0, 90] degrees, got %r' % (what, max_angle))
+    angle = _angle_of(what, 'max_angle', max_angle)
     if not torch.is_tensor(normals) or tuple(normals.shape) != tuple(points.shape) or normals.device != points.device:
         raise ValueError('%s: normals must be [B,Q,3] = %s on %s, got %s'
                          % (what, tuple(points.shape), points.device,
@@ -1638,6 +1633,42 @@ def _rho_of(what, rho, sigma):
     if rho == 'gmof' and not (sigma is not None and float(sigma) > 0.0):
         raise ValueError("%s: rho='gmof' needs sigma > 0, got %r" % (what, sigma))
     return SCAN_RHO[rho], float(sigma) if sigma is not None else 0.0
+
+
+def _angle_of(what, name, max_angle) -> float:
+    """The largest normal angle in degrees, in (0, 90]; ``name`` is what the caller's argument is called."""
+    angle = float(max_angle)
+    if not (0.0 < angle <= 90.0):
+        raise ValueError('%s: %s must be in (0, 90] degrees, got %r' % (what, name, max_angle))
+    return angle
+
+
+def _resolution_of(what, resolution) -> int:
+    """Cells of a PointCloud's grid along the longest extent."""
+    if not (isinstance(resolution, int) and 1 <= resolution <= 256):
+        raise ValueError('%s: resolution must be an int in 1 .. 256, got %r' % (what, resolution))
+    return resolution
+
+
+def _counts_of(what, counts, b):
+    """counts [B] (real entries per body) as the C entry points take it: int32, contiguous; None stays None."""
+    if counts is None:
+        return None
+    if tuple(counts.shape) != (b,):
+        raise ValueError('%s: counts must be [%d], got %s' % (what, b, tuple(counts.shape)))
+    return counts.to(torch.int32).contiguous()
+
+
+def _check_weights(what, weights, b, q):
+    if weights is not None and tuple(weights.shape) != (b, q):
+        raise ValueError('%s: weights must be [%d,%d], got %s' % (what, b, q, tuple(weights.shape)))
+
+
+def _both(what, name_a, a, name_b, b) -> bool:
+    """Two arguments that go together: False with neither, True with both; one alone raises."""
+    if (a is None) != (b is None):
+        raise ValueError('%s: %s and %s go together, got %s only' % (what, name_a, name_b, name_b if a is None else name_a))
+    return a is not None
 
 
 class _ScanFit(torch.autograd.Function):
@@ -1713,14 +1744,11 @@ def scan_fit(model: ContactModel, verts, transl, points, counts=None, weights=No
     if b == 0 or q == 0:
         raise ValueError('scan_fit: empty input %s' % (tuple(points.shape),))
     cos = _max_angle_cos(normals, max_angle, points, 'scan_fit')
-    if weights is not None and tuple(weights.shape) != (b, q):
-        raise ValueError('scan_fit: weights must be [%d,%d], got %s' % (b, q, tuple(weights.shape)))
-    if counts is not None and tuple(counts.shape) != (b,):
-        raise ValueError('scan_fit: counts must be [%d], got %s' % (b, tuple(counts.shape)))
+    _check_weights('scan_fit', weights, b, q)
+    counts = _counts_of('scan_fit', counts, b)
     _need_hip('scan_fit', verts, transl, points, weights, counts, hint, face_out, normals)
     if face_out is not None and (tuple(face_out.shape) != (b, q) or face_out.dtype != torch.int32 or not face_out.is_contiguous()):
         raise ValueError('scan_fit: face_out must be a contiguous int32 [%d,%d] tensor' % (b, q))
-    counts = None if counts is None else counts.to(torch.int32).contiguous()
     weights = None if weights is None else _f32(weights.detach())
     hint = _hint_of(hint, points, 'scan_fit')
     face = face_out if face_out is not None else torch.empty(b, q, dtype=torch.int32, device=points.device)
@@ -1817,9 +1845,7 @@ class PointCloud:
     are not copied): change them in place and call ``rebuild()``.  There is no host fallback."""
 
     def __init__(self, points, counts=None, weights=None, resolution=64):
-        if not (isinstance(resolution, int) and 1 <= resolution <= 256):
-            raise ValueError('PointCloud: resolution must be an int in 1 .. 256, got %r' % (resolution,))
-        self.resolution = resolution
+        self.resolution = _resolution_of('PointCloud', resolution)
         self._ws = None
         self.rebuild(points, counts, weights)
 
@@ -1829,13 +1855,11 @@ class PointCloud:
         if points.dim() != 3 or points.shape[2] != 3 or points.shape[0] == 0 or points.shape[1] == 0:
             raise ValueError('PointCloud: points must be [B,Q,3] with B, Q > 0, got %s' % (tuple(points.shape),))
         b, q = points.shape[0], points.shape[1]
-        if counts is not None and tuple(counts.shape) != (b,):
-            raise ValueError('PointCloud: counts must be [%d], got %s' % (b, tuple(counts.shape)))
-        if weights is not None and tuple(weights.shape) != (b, q):
-            raise ValueError('PointCloud: weights must be [%d,%d], got %s' % (b, q, tuple(weights.shape)))
+        counts = _counts_of('PointCloud', counts, b)
+        _check_weights('PointCloud', weights, b, q)
         _need_hip('PointCloud', points, counts, weights)
         self.points = _f32(points)
-        self.counts = None if counts is None else counts.detach().to(torch.int32).contiguous()
+        self.counts = counts
         self.weights = None if weights is None else _f32(weights)
         L = _C.lib()
         nbytes = L.tuch_point_cloud_workspace_bytes(b, q, self.resolution)
@@ -1913,14 +1937,11 @@ class PointCloud:
         what = 'PointCloud.nearest'
         self._check_queries(what, queries, shift, hint)
         b, n = queries.shape[0], queries.shape[1]
-        if counts is not None and tuple(counts.shape) != (b,):
-            raise ValueError('PointCloud.nearest: counts must be [%d], got %s' % (b, tuple(counts.shape)))
+        counts = _counts_of(what, counts, b)
         tau = _tau_of(what, max_distance)
         _need_hip(what, counts, index_out)
         extra = ()
-        if query_normals is not None or max_angle is not None:
-            if query_normals is None or max_angle is None:
-                raise ValueError('%s: query_normals and max_angle go together' % what)
+        if _both(what, 'query_normals', query_normals, 'max_angle', max_angle):
             if not torch.is_tensor(query_normals) or tuple(query_normals.shape) != (b, n, 3):
                 raise ValueError('%s: query_normals must be [%d,%d,3], got %s'
                                  % (what, b, n, tuple(query_normals.shape) if torch.is_tensor(query_normals) else
@@ -1928,7 +1949,6 @@ class PointCloud:
             _need_hip(what, query_normals)
             extra = (_f32(query_normals.detach()), self._oriented_cos(what, max_angle))
         index = _index_out(what, index_out, b, n, queries.device)
-        counts = None if counts is None else counts.to(torch.int32).contiguous()
         d2 = _CloudNearest.apply(queries, shift, self, counts, hint, tau, index, *extra)
         return NearestPoint(d2, index)
 
@@ -1939,9 +1959,7 @@ class PointCloud:
         if own:
             queries = self.points
         self._check_queries(what, queries, shift, None)
-        b = queries.shape[0]
-        if counts is not None and tuple(counts.shape) != (b,):
-            raise ValueError('%s: counts must be [%d], got %s' % (what, b, tuple(counts.shape)))
+        counts = _counts_of(what, counts, queries.shape[0])
         tau = _tau_of(what, max_distance)
         _need_hip(what, counts)
         qs = _f32(queries)
@@ -1952,7 +1970,6 @@ class PointCloud:
                 counts = self.counts
             if self.weights is not None:
                 qs = torch.where((self.weights != 0)[:, :, None], qs, torch.full_like(qs, float('nan')))
-        counts = None if counts is None else counts.to(torch.int32).contiguous()
         return qs, None if shift is None else _f32(shift), counts, tau
 
     def knn(self, queries=None, k=8, shift=None, counts=None, max_distance=None) -> KNearest:
@@ -2124,9 +2141,7 @@ def cloud_fit(cloud: PointCloud, verts, transl, vertex_weights=None, hint=None, 
     _need_hip('cloud_fit', index_out)
     index = _index_out('cloud_fit', index_out, b, n, verts.device)
     extra = ()
-    if max_angle is not None or normal_table is not None:
-        if max_angle is None or normal_table is None:
-            raise ValueError('cloud_fit: max_angle and normal_table go together')
+    if _both('cloud_fit', 'max_angle', max_angle, 'normal_table', normal_table):
         _check_normal_table('cloud_fit', normal_table, n, verts.device)
         extra = (cloud._oriented_cos('cloud_fit', max_angle), normal_table)
     total, per_body, d2 = _CloudFit.apply(verts, transl, cloud, vw, layout, hint, rho, sigma, tau, float(scale), index, *extra)

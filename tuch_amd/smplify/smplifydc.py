@@ -9,18 +9,12 @@ Same constructor and ``__call__`` signature / 7-tuple return as the reference
   * the contact term of every iteration is one batched pass over the HIP kernels.
 
 One driver (``__call__``): get a session for the call's constants (static tensors, the three iteration closures, the two
-loops), copy the inputs into it, run stage 1, run stage 2, evaluate, return clones.  One loop runner (``_Stage.run``) with
-three modes: eager launches (``use_graph=False``, not a HIP device, ``num_iters <= 4``), unrolled into an enclosing capture,
-or three eager iterations + capture + replay (replay only on later calls of a kept session).  ``record_history`` and
-``TUCH_SMPLIFY_SESSIONS`` do not select other code: the first adds clones around each iteration, the second decides whether
-the session outlives the call.  One fallback: a capture that fails (and ``TUCH_GRAPH_STRICT`` unset) is logged, and the rest
-of the fit runs eagerly through the same runner.
+loops), copy the inputs into it, run stage 1, run stage 2, evaluate, return clones.  The loops are run by the package's one
+loop runner (``fit_loop.Stage``; its three modes and its one fallback are described there), and the loop settings, the
+call prelude and the kept sessions are ``fit_loop.LoopOwner``'s, shared with the fitters of ``tuch_amd/fit.py``.
 """
 from __future__ import annotations
 
-import contextlib
-import gc
-import logging
 import os
 
 import numpy as np
@@ -28,10 +22,7 @@ import torch
 
 from .losses import body_fitting_loss, camera_fitting_loss, contact_model_for, stage2_objective
 from .prior import MaxMixturePrior
-from .. import ops
-from ..optim import make_adam
-
-log = logging.getLogger(__name__)
+from ..fit_loop import LoopOwner, Stage
 
 # smplifydc.py:46-47: joints ignored during the fit, by name; resolved through constants.JOINT_IDS when the
 # data folder is importable, else through SPIN's published table (models/smpl.py) -> [1, 9, 12, 27, 28]
@@ -44,7 +35,7 @@ def default_ignored_joints():
     return [ids[n] for n in IGNORED_JOINT_NAMES]
 
 
-class SMPLifyDC():
+class SMPLifyDC(LoopOwner):
     """SMPLify with discrete self-contact: stage 1 fits camera translation (+ betas when contact is
     used), stage 2 fits pose and global orientation against the contact objective."""
 
@@ -62,10 +53,11 @@ class SMPLifyDC():
         from ..assets import config_path
         self.device = device
         self.focal_length = focal_length
-        self.step_size = step_size
+        # (record_history is not in the reference: self.history = {'stage1': [...], 'stage2': [...]}; sessions are keyed
+        # by batch size and the call's constant arguments)
+        self._init_loops(step_size, num_iters, use_graph, record_history)
         self.ign_joints = list(default_ignored_joints() if ign_joints is None else ign_joints)
         self._ign_index = {}          # device -> index tensor (a Python list index is re-uploaded on every use)
-        self.num_iters = num_iters
         if pose_prior is None:             # smplifydc.py:50-52
             pose_prior = MaxMixturePrior(prior_folder=prior_folder or config_path('PRIOR_FOLDER'),
                                          num_gaussians=8, dtype=torch.float32)
@@ -81,125 +73,23 @@ class SMPLifyDC():
         self.geothres = geothres
         self.geomask = self.geodistssmpl > self.geothres            # smplifydc.py:65 (strict >)
         self.euclthres = euclthres
-        # replay each optimisation loop as a hipGraph after three eager iterations (same arithmetic,
-        # no per-kernel launch cost: at small batch the loop is launch-bound otherwise)
-        self.use_graph = use_graph
-        # measurement / test aid (not in the reference): with record_history the objective and the parameters
-        # *before* every update are kept per stage in self.history = {'stage1': [...], 'stage2': [...]}
-        self.record_history = record_history
-        # read once: TUCH_GRAPH_STRICT=1 turns a failed capture into an error (the tests set it), TUCH_SMPLIFY_SESSIONS=0
-        # makes every call build its session and capture its loops afresh
-        self.graph_strict = os.environ.get('TUCH_GRAPH_STRICT', '0') == '1'
-        self.keep_sessions = os.environ.get('TUCH_SMPLIFY_SESSIONS', '1') != '0'
         self.fused_adam = os.environ.get('TUCH_FUSED_ADAM', '1') != '0'      # 0: Adam as a launch of its own (A/B, tests)
-        self.history = None
-        self.graph_replayed = {}
-        # captured loops are kept between calls (keyed by batch size and the constant arguments): a training step
-        # with SMPLify-DC in the loop runs 10 + 10 iterations per call, far too few to pay for two captures each time
-        self._sessions = {}
 
-    class _Stage:
-        """One Adam loop on a session's static tensors, and the only loop runner: eager launches, unrolled into an enclosing
-        capture, or three eager iterations + capture the first time and replays afterwards."""
-
-        def __init__(self, owner, name, params, iteration, adam_kwargs, fuse_backward=False):
-            self.owner, self.name, self.params, self.iteration = owner, name, params, iteration
-            # fuse_backward (the contact stage 2: parameters = the body model's two pose tensors, objective = one root node):
-            # the body model's last backward kernel applies Adam's update itself, step() is then a no-op (optim.py)
-            self.optimizer = make_adam(params, owner.step_size, capturable=True, fuse_backward=fuse_backward, **adam_kwargs)
-            self.graph, self.verts, self.loss, self.before = None, None, None, None
-
-        def _one(self):
-            record = self.owner.record_history
-            if record:
-                self.before = [p.detach().clone() for p in self.params]
-            loss, verts = self.iteration()
-            self.optimizer.zero_grad(set_to_none=True)
-            ops.backward_scalar(loss)
-            self.optimizer.step()
-            self.verts, self.loss = verts, loss.detach().clone() if record else loss.detach()
-
-        def run(self, num_iters, collect, capture):
-            """Returns whether the loop ran captured (replayed or unrolled); False: eager launches, as asked for or because
-            the capture failed -- the caller then runs what is left of the fit eagerly and does not keep the session."""
-            owner = self.owner
-            for state in self.optimizer.state.values():            # a fresh optimiser per call (smplifydc.py:117,150)
-                for v in state.values():
-                    if torch.is_tensor(v):
-                        v.zero_()
-            history = owner.history[self.name] if owner.record_history else None
-
-            def iterate(count, step):
-                for _ in range(count):
-                    step()
-                    if collect is not None:
-                        collect.append(self.verts.detach().clone())
-                    if history is not None:
-                        history.append({'loss': self.loss.clone(), 'params': [p.clone() for p in self.before]})
-            if not capture:
-                iterate(num_iters, self._one)
-                return False
-            if torch.cuda.is_current_stream_capturing():
-                # an ENCLOSING capture is recording (TUCH.forward_train_step --run_smplify captured as one hipGraph: BASELINE
-                # config 5): a child graph cannot be replayed into it -- the iterations are unrolled into the enclosing graph
-                iterate(num_iters, self._one)
-                owner.graph_replayed[self.name] = 0
-                return True
-            done = 0
-            if self.graph is None:
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    iterate(3, self._one)
-                torch.cuda.current_stream().wait_stream(side)
-                done = 3
-                # Python's cycle collector must not run inside the capture.  A fitter and its stages refer to each other, so a
-                # dropped fitter's sessions -- captured graphs and their memory pools -- die only when the collector
-                # finds them, and destroying a graph while a stream is capturing aborts the process (seen in the test
-                # suite: which allocation triggers a collection depends on everything that ran before).  Dead sessions
-                # are collected here, before the capture, and the collector rests until the capture has ended.  (The
-                # collector's switch is process-wide: two threads capturing at once may re-enable it early for each
-                # other, which is then no worse than before.)
-                gc.collect()
-                collecting = gc.isenabled()
-                gc.disable()
-                try:
-                    graph = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(graph, capture_error_mode='thread_local'):
-                        self._one()
-                except Exception as exc:
-                    if collecting:
-                        gc.enable()
-                        collecting = False
-                    # a loop that cannot be captured still runs (eagerly), but never silently: TUCH_GRAPH_STRICT=1
-                    # (set by the tests) turns this into an error
-                    if owner.graph_strict:
-                        raise
-                    log.warning('SMPLifyDC: hipGraph capture of the %s loop failed (%r); finishing with eager launches',
-                                self.name, exc)
-                    torch.cuda.synchronize()
-                    self.optimizer.zero_grad()       # a half-recorded fused update must not swallow the next step()
-                    iterate(num_iters - done, self._one)
-                    return False
-                finally:
-                    if collecting:
-                        gc.enable()
-                self.graph = graph
-            iterate(num_iters - done, self.graph.replay)
-            owner.graph_replayed[self.name] = num_iters - done
-            return True
+    _Stage = Stage            # (the name the benchmark's comments and older notes use)
 
     def _session(self, batch, use_contact, contactlist, segments, contact_loss_weight, with_pairs, like):
-        """(key, session): the static tensors, the three iteration closures and the two loops of a fit with these constants."""
+        """(key, session) of a fit with these constants: the stored one, or a new one (``_build``)."""
         # everything a captured loop bakes in: the tables (the session keeps them alive, so their ids cannot be reused by
         # other objects) and the fitter's own settings -- changing one of those after a call starts a new session
         key = (batch, bool(use_contact), id(contactlist), id(segments), float(contact_loss_weight), bool(with_pairs),
                float(self.step_size), float(self.euclthres), float(self.focal_length), tuple(self.ign_joints),
                id(self.pose_prior), int(self.num_iters), bool(self.record_history), bool(self.fused_adam))
-        sess = self._sessions.get(key)
-        if sess is not None:
-            return key, sess
-        dev, f32 = like.device, torch.float32
+        return key, self._session_for(key, self._build, batch, use_contact, contactlist, segments, contact_loss_weight,
+                                      with_pairs, like.device)
+
+    def _build(self, batch, use_contact, contactlist, segments, contact_loss_weight, with_pairs, dev):
+        """A session: the static tensors, the three iteration closures and the two loops."""
+        f32 = torch.float32
         z = lambda *shape, dtype=f32: torch.zeros(*shape, dtype=dtype, device=dev)
         t = dict(body_pose=z(batch, 69), global_orient=z(batch, 3), betas=z(batch, 10), cam=z(batch, 3), init_cam=z(batch, 3),
                  centre=z(batch, 2), j2d=z(batch, 49, 2), conf1=z(batch, 49), conf2=z(batch, 49),
@@ -236,17 +126,17 @@ class SMPLifyDC():
         stage1_flags = (False, not use_contact, bool(use_contact), True)
         flags(*stage1_flags)
         sess = dict(t=t, flags=flags, stage1_flags=stage1_flags, stage2=None, keys_alive=(contactlist, segments, self.pose_prior),
-                    stage1=self._Stage(self, 'stage1', [betas, cam] if use_contact else [global_orient, cam], camera_iteration,
-                                       dict(betas=(0.9, 0.999))))
+                    stage1=Stage(self, 'stage1', [betas, cam] if use_contact else [global_orient, cam], camera_iteration,
+                                 dict(betas=(0.9, 0.999))))
         if use_contact:
             sess['stage2_flags'] = (True, True, False, False)
-            sess['make_stage2'] = lambda: self._Stage(self, 'stage2', [body_pose, global_orient], contact_iteration, {},
-                                                      fuse_backward=self.fused_adam)
+            sess['make_stage2'] = lambda: Stage(self, 'stage2', [body_pose, global_orient], contact_iteration, {},
+                                                fuse_backward=self.fused_adam)
         else:
             sess['stage2_flags'] = (True, True, True, False)
-            sess['make_stage2'] = lambda: self._Stage(self, 'stage2', [body_pose, betas, global_orient], body_iteration,
-                                                      dict(betas=(0.9, 0.999)))
-        return key, sess
+            sess['make_stage2'] = lambda: Stage(self, 'stage2', [body_pose, betas, global_orient], body_iteration,
+                                                dict(betas=(0.9, 0.999)))
+        return sess
 
     def __call__(self, init_pose, init_betas, init_cam_t,
                  camera_center, keypoints_2d, use_contact=False,
@@ -259,12 +149,7 @@ class SMPLifyDC():
         if use_contact and ignore_idxs is None:
             raise ValueError('SMPLifyDC: use_contact=True needs ignore_idxs, a [B] bool tensor (all False: every body gets '
                              'contact terms)')
-        on_gpu = self.use_graph and init_pose.is_cuda
-        capture = on_gpu and self.num_iters > 4
-        if self.record_history:
-            self.history = {'stage1': [], 'stage2': []}
-        # graph replays never run on the NULL stream (ops.py)
-        with ops.off_default_stream(init_pose.device) if on_gpu else contextlib.nullcontext():
+        with self._loops(init_pose.device, self.use_graph and init_pose.is_cuda, 'stage1', 'stage2') as capture:
             with_pairs = gt_contact is not None and gt_contact[0] is not None
             key, sess = self._session(init_pose.shape[0], use_contact, contactlist, segments, contact_loss_weight, with_pairs,
                                       init_pose)
@@ -289,13 +174,7 @@ class SMPLifyDC():
                 sess['stage2'] = sess['make_stage2']()
             optiverts = []
             capture = sess['stage2'].run(self.num_iters, optiverts, capture)
-            # captured loops are kept for the next call; a session that ran eagerly (or lost a capture) is dropped
-            if not (capture and self.keep_sessions):
-                self._sessions.pop(key, None)
-            elif key not in self._sessions:
-                while len(self._sessions) >= 4:
-                    self._sessions.pop(next(iter(self._sessions)))
-                self._sessions[key] = sess
+            self._settle(key, sess, capture)
             # ---- final evaluation
             with torch.no_grad():
                 out = self.smpl(global_orient=t['global_orient'], body_pose=t['body_pose'], betas=t['betas'], return_full_pose=True)
