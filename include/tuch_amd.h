@@ -409,29 +409,20 @@ int tuch_winding_points(const tuch_contact_model* model, const float* verts, con
  *   counts [B] device ints or NULL: real queries per body (clamped to [0, Q]); entries at or beyond counts[b] get
  * d2 = +inf, face = -1, bary = 0.  Every index read from the tables is clamped before it is used as an address.  A
  * body with NaN or Inf vertices or points changes no other body's bits and yields face indices in [-1, F).  B = 0 or
- * Q = 0: nothing is done.  No allocation, no synchronisation, capturable; the workspace (boxes [B,G,8] and the posed
- * corners in group order [B,F,9]) is guarded under option canary. */
-size_t tuch_closest_point_workspace_bytes(const tuch_contact_model* model, int B, int Q);
-int tuch_closest_point(const tuch_contact_model* model, const float* verts /* [B,V,3] */,
-                       const float* points /* [B,Q,3] */, const int32_t* counts /* [B] or NULL */, int B, int Q,
-                       float* d2 /* [B,Q] */, int32_t* face /* [B,Q] */, float* bary /* [B,Q,3] */,
-                       void* workspace, size_t workspace_bytes, void* stream);
-/* The same search with a hint: tuch_closest_point's arguments plus hint [B,Q] device ints or NULL (NULL: exactly
- * tuch_closest_point).  hint[b,q] names a face that is probably the answer -- in a fitting loop the face the previous
- * iteration returned.  It is only a bound: d2, face and bary equal tuch_closest_point's bit for bit for EVERY content
- * of hint (the right face, a wrong one, -1, F, INT32_MAX, INT32_MIN, any mix within a wavefront).  A hint in [0, F) --
- * checked before it is used as an address -- makes the query start from that face's exact distance and group instead
- * of from the walk over every box of the body; any other value, or a hinted face whose distance is not finite (NaN
- * vertices), takes tuch_closest_point's path.  hint may alias the face output: a lane reads its own hint before it
- * writes its face, so a loop can keep one [B,Q] tensor that is both.  Workspace as for tuch_closest_point. */
-int tuch_closest_point_hinted(const tuch_contact_model* model, const float* verts /* [B,V,3] */,
-                              const float* points /* [B,Q,3] */, const int32_t* counts /* [B] or NULL */,
-                              const int32_t* hint /* [B,Q] or NULL */, int B, int Q, float* d2 /* [B,Q] */,
-                              int32_t* face /* [B,Q] */, float* bary /* [B,Q,3] */, void* workspace,
-                              size_t workspace_bytes, void* stream);
-/* The normal-compatible search: tuch_closest_point_hinted's arguments plus normals [B,Q,3] (float32, any length, in
- * the frame of verts) and max_angle_cos = c, the float32 cosine of an angle in (0, 90] degrees (the caller computes the
- * cosine in double and rounds it once).  A query is (p, n); a face is a candidate only if it is ADMISSIBLE for n.
+ * Q = 0: nothing is done.  No allocation, no synchronisation, capturable; the workspace
+ * (tuch_closest_point_workspace_bytes: boxes [B,G,8] and the posed corners in group order [B,F,9]; with oriented != 0,
+ * which a call with normals needs, also the cones [B,G,8]) is guarded under option canary.
+ *   hint [B,Q] device ints or NULL.  hint[b,q] names a face that is probably the answer -- in a fitting loop the face the
+ * previous iteration returned.  It is only a bound: d2, face and bary equal those of the call with hint = NULL bit for bit
+ * for EVERY content of hint (the right face, a wrong one, -1, F, INT32_MAX, INT32_MIN, any mix within a wavefront).  A
+ * hint in [0, F) -- checked before it is used as an address -- makes the query start from that face's exact distance and
+ * group instead of from the walk over every box of the body; any other value, or a hinted face whose distance is not
+ * finite (NaN vertices), takes the unhinted path.  hint may alias the face output: a lane reads its own hint before it
+ * writes its face, so a loop can keep one [B,Q] tensor that is both.
+ *   normals (optional) [B,Q,3] or NULL (float32, any length, in the frame of verts): the normal-compatible search, with
+ * max_angle_cos = c, the float32 cosine of an angle in (0, 90] degrees (the caller computes the cosine in double and
+ * rounds it once); c outside [0, 1) or not finite is an argument error.  With normals = NULL max_angle_cos is ignored
+ * whatever it holds.  A query is (p, n); a face is a candidate only if it is ADMISSIBLE for n.
  *   The admissibility rule, one fixed float32 sequence, every product, sum and difference rounded on its own (nothing
  * fused), for a face with posed corners a, b, c (the bits of verts) and c2 = c * c formed once in float32:
  *     e1 = b - a, e2 = c - a                       (one subtraction per component)
@@ -440,24 +431,22 @@ int tuch_closest_point_hinted(const tuch_contact_model* model, const float* vert
  *     admissible  <=>  s > 0  and  s * s >= c2 * (mm * nn).
  * A face without area (mm = 0, s = 0) is never admissible for a constrained query; neither is one with NaN corners
  * (every comparison is false).  A query whose nn is 0 or not finite (a missing normal: a zero row, NaN, Inf, overflow)
- * is UNCONSTRAINED: every face is admissible and its three outputs have tuch_closest_point's bits.
+ * is UNCONSTRAINED: every face is admissible and its three outputs have the bits of the call without normals.
  *   The winner is the smallest packed key d2 bits << 32 | face over the admissible faces, d2 from the unchanged
  * distance sequence; a query without an admissible face gets d2 = +inf, face = -1, bary = 0.  A query gives the same
  * bits alone or in any batch, for any order of the queries, eager or replayed, for any grouping of the faces and for
  * every content of hint: the outputs equal an unpruned sweep over all faces under this rule, bit for bit (groups are
  * skipped by their boxes as before, and by per-group normal cones whose margins are conservative: derivation in the
  * source file).  A hinted query starts from its hint only if the face is in [0, F), admissible for it and at a finite
- * d2; any other hint takes the unhinted path.  hint may alias face.  counts, NaN bodies, B = 0 or Q = 0 as for
- * tuch_closest_point.  max_angle_cos outside [0, 1) or not finite is an argument error.  The workspace is
- * tuch_closest_point's plus the cones [B,G,8], guarded under option canary.  tuch_closest_point_bwd applies to the
- * outputs unchanged (face = -1 contributes nothing); normals are constants and get no gradient. */
-size_t tuch_closest_point_oriented_workspace_bytes(const tuch_contact_model* model, int B, int Q);
-int tuch_closest_point_oriented(const tuch_contact_model* model, const float* verts /* [B,V,3] */,
-                                const float* points /* [B,Q,3] */, const float* normals /* [B,Q,3] */,
-                                float max_angle_cos, const int32_t* counts /* [B] or NULL */,
-                                const int32_t* hint /* [B,Q] or NULL */, int B, int Q, float* d2 /* [B,Q] */,
-                                int32_t* face /* [B,Q] */, float* bary /* [B,Q,3] */, void* workspace,
-                                size_t workspace_bytes, void* stream);
+ * d2; any other hint takes the unhinted path.  counts, NaN bodies, B = 0 or Q = 0 and the aliasing of hint with face
+ * as above.  tuch_closest_point_bwd applies to the outputs unchanged (face = -1 contributes nothing); normals are
+ * constants and get no gradient. */
+size_t tuch_closest_point_workspace_bytes(const tuch_contact_model* model, int B, int Q, int oriented);
+int tuch_closest_point(const tuch_contact_model* model, const float* verts /* [B,V,3] */,
+                       const float* points /* [B,Q,3] */, const float* normals /* [B,Q,3] or NULL */, float max_angle_cos,
+                       const int32_t* counts /* [B] or NULL */, const int32_t* hint /* [B,Q] or NULL */, int B, int Q,
+                       float* d2 /* [B,Q] */, int32_t* face /* [B,Q] */, float* bary /* [B,Q,3] */, void* workspace,
+                       size_t workspace_bytes, void* stream);
 /* The face groups the search walks, as host copies (any may be NULL): *num_groups = G, group_off_host [G+1],
  * face_list_host [F] (the faces of group g are face_list[group_off[g] .. group_off[g+1])), face_group_host [F] (the
  * group of every face: the inverse of face_list, where a hinted query starts). */
@@ -477,7 +466,7 @@ int tuch_closest_point_bwd(const tuch_contact_model* model, const float* verts, 
 
 /* Point-to-surface data term of a fit to unregistered points (csrc/scan_fit.hip).  The queries are points[b,q] -
  * transl[b] (one float32 subtraction per component) against the model's mesh posed by verts[b]: d2, face, bary are
- * those of tuch_closest_point_hinted on these queries, bit for bit (counts, hint and its aliasing with face as there).
+ * those of tuch_closest_point on these queries, bit for bit (counts, hint and its aliasing with face as there).
  *   per_body[b] = sum_{q < counts[b]} w_q rho(d2_q) / sum_{q < counts[b]} w_q,   total[0] = sum_b per_body[b],
  * with weights [B,Q] or NULL (all ones) and rho = 0: d2;  1: sqrt(d2), derivative 0 at d2 = 0;  2: sigma^2 d2 /
  * (sigma^2 + d2) (sigma > 0; ignored otherwise).  A point of weight 0 is not computed from and may be non-finite; a
@@ -488,33 +477,23 @@ int tuch_closest_point_bwd(const tuch_contact_model* model, const float* verts, 
  * summed with float atomics, or, under tuch_set_deterministic(1), as 64-bit fixed-point integers in the workspace
  * (the same bits on every call); per_body, its normaliser, total and grad_transl are fixed-order sums in both modes.
  * ticket: one int, zero before the first call and left zero by every call.  No allocation, no synchronisation,
- * capturable; the workspace is guarded under option canary. */
-size_t tuch_scan_fit_workspace_bytes(const tuch_contact_model* model, int B, int Q);
+ * capturable; the workspace (tuch_scan_fit_workspace_bytes, with oriented != 0 for a call with normals) is guarded
+ * under option canary.
+ *   normals (optional) [B,Q,3] or NULL, and max_angle_cos, as in tuch_closest_point: the term over the normal-compatible
+ * search.  The queries are points - transl as above; normals are not translated and get no gradient.  d2, face, bary
+ * are those of tuch_closest_point with these normals on these queries, bit for bit.  A real point without an
+ * admissible face (face = -1) contributes 0 to the loss and to every gradient and KEEPS its weight in the normaliser:
+ * an unmatched point adds nothing and the denominator does not move. */
+size_t tuch_scan_fit_workspace_bytes(const tuch_contact_model* model, int B, int Q, int oriented);
 int tuch_scan_fit_terms(const tuch_contact_model* model, const float* verts /* [B,V,3] */,
                         const float* transl /* [B,3] */, const float* points /* [B,Q,3] */,
+                        const float* normals /* [B,Q,3] or NULL */, float max_angle_cos,
                         const int32_t* counts /* [B] or NULL */, const float* weights /* [B,Q] or NULL */,
                         const int32_t* hint /* [B,Q] or NULL */, int B, int Q, int rho, float sigma,
                         float* d2 /* [B,Q] */, int32_t* face /* [B,Q] */, float* bary /* [B,Q,3] */, int* ticket,
                         float* per_body /* [B] */, float* total /* [1] */, float* grad_verts /* [B,V,3] */,
                         float* grad_transl /* [B,3] */, float* grad_points /* [B,Q,3] or NULL */, void* workspace,
                         size_t workspace_bytes, void* stream);
-/* The same term over the normal-compatible search: tuch_scan_fit_terms plus normals [B,Q,3] and max_angle_cos as in
- * tuch_closest_point_oriented.  The queries are points - transl as above; normals are not translated and get no
- * gradient.  d2, face, bary are tuch_closest_point_oriented's on these queries, bit for bit.  A real point without an
- * admissible face (face = -1) contributes 0 to the loss and to every gradient and KEEPS its weight in the normaliser:
- * an unmatched point adds nothing and the denominator does not move.  Workspace:
- * tuch_scan_fit_oriented_workspace_bytes. */
-size_t tuch_scan_fit_oriented_workspace_bytes(const tuch_contact_model* model, int B, int Q);
-int tuch_scan_fit_terms_oriented(const tuch_contact_model* model, const float* verts /* [B,V,3] */,
-                                 const float* transl /* [B,3] */, const float* points /* [B,Q,3] */,
-                                 const float* normals /* [B,Q,3] */, float max_angle_cos,
-                                 const int32_t* counts /* [B] or NULL */, const float* weights /* [B,Q] or NULL */,
-                                 const int32_t* hint /* [B,Q] or NULL */, int B, int Q, int rho, float sigma,
-                                 float* d2 /* [B,Q] */, int32_t* face /* [B,Q] */, float* bary /* [B,Q,3] */,
-                                 int* ticket, float* per_body /* [B] */, float* total /* [1] */,
-                                 float* grad_verts /* [B,V,3] */, float* grad_transl /* [B,3] */,
-                                 float* grad_points /* [B,Q,3] or NULL */, void* workspace, size_t workspace_bytes,
-                                 void* stream);
 
 /* Nearest point of a static point cloud; the model -> scan term of a two-sided fit (csrc/point_cloud.hip).  No model
  * is involved: a cloud has no mesh.
@@ -548,12 +527,33 @@ size_t tuch_point_cloud_workspace_bytes(int B, int Q, int resolution);
 int tuch_point_cloud_build(const float* points /* [B,Q,3] */, const int32_t* counts /* [B] or NULL */,
                            const float* weights /* [B,Q] or NULL */, int B, int Q, int resolution, void* workspace,
                            size_t workspace_bytes, void* stream);
+/* normals (optional): the oriented query, the rule above over the ADMISSIBLE valid points.  normals [B,Q,3] belong to the
+ * points, in the caller's order; query_normals [B,N,3] to the queries (neither is translated by shift).  The two go
+ * together: both NULL is the plain query, which ignores max_angle_cos, cones and cones_bytes whatever they hold; one
+ * without the other is an argument error.  With c = max_angle_cos in [0, 1) (anything else is an argument error),
+ * c2 = c c formed once, for a query normal u and a point normal n, every operation rounded to float32 on its own:
+ *   uu = (ux ux + uy uy) + uz uz,  nn = (nx nx + ny ny) + nz nz,  s = (ux nx + uy ny) + uz nz,
+ *   admissible  <=>  s > 0  and  s s >= c2 (uu nn).
+ * A pair is unconstrained -- admissible -- when uu or nn is 0 or not finite: a missing normal, the zero rows of
+ * tuch_point_cloud_normals among them.  Valid points, q = x + shift, the squared distance, the packed key, max_distance,
+ * query_counts and the no-winner outputs (-1 / +inf) are the plain query's; the winner is the smallest key over
+ * the admissible valid points; a hint seeds the search only if it names a valid, admissible point within the limit.
+ * The outputs equal a float32 brute-force sweep under this rule bit for bit: for any batch, order of queries or points,
+ * resolution and hint content, eager or replayed, with cones or with cones NULL.
+ *   cones: per-block normal cones that let a lane pass by a block of the grid none of whose points is admissible for
+ * its normal (they may only skip, never decide; csrc/point_cloud.hip has the derivation).  A caller-provided buffer of
+ * tuch_point_cloud_cones_bytes(B, resolution) bytes, filled by tuch_point_cloud_build_cones AFTER tuch_point_cloud_build
+ * from the same normals (one launch, capturable) and stale after the next build; NULL: no block is skipped. */
+size_t tuch_point_cloud_cones_bytes(int B, int resolution);
+int tuch_point_cloud_build_cones(const void* workspace, size_t workspace_bytes, const float* normals /* [B,Q,3] */, int B,
+                                 int Q, int resolution, void* cones, size_t cones_bytes, void* stream);
 int tuch_point_cloud_nearest(const void* workspace, size_t workspace_bytes, const float* points /* [B,Q,3] */,
                              const int32_t* counts /* [B] or NULL */, const float* weights /* [B,Q] or NULL */,
-                             const float* queries /* [B,N,3] */, const float* shift /* [B,3] or NULL */,
+                             const float* normals /* [B,Q,3] or NULL */, const float* queries /* [B,N,3] */,
+                             const float* query_normals /* [B,N,3] or NULL */, const float* shift /* [B,3] or NULL */,
                              const int32_t* query_counts /* [B] or NULL */, const int32_t* hint /* [B,N] or NULL */,
-                             float max_distance, int B, int Q, int N, float* d2 /* [B,N] */, int32_t* index /* [B,N] */,
-                             void* stream);
+                             float max_distance, float max_angle_cos, const void* cones /* or NULL */, size_t cones_bytes,
+                             int B, int Q, int N, float* d2 /* [B,N] */, int32_t* index /* [B,N] */, void* stream);
 /* k nearest points, and PCA normals over them.  The rule above, verbatim -- the valid points, q = x + shift[b], THE
  * squared distance, the packed key d2 bits << 32 | index, max_distance, query_counts -- for the k (1 .. 32; anything
  * else is an argument error) smallest keys of a query, in ascending order: index [B,N,k], d2 [B,N,k].  With fewer than
@@ -575,7 +575,7 @@ int tuch_point_cloud_nearest(const void* workspace, size_t workspace_bytes, cons
  * neighbours), the sine of the normal's angle error is at most 2 E / (lambda1 - lambda0).  The row is ZERO when n < 3
  * or 2 E >= lambda1 - lambda0 --
  * collinear, coincident or isotropic neighbours, where the bound says nothing; also when T is not finite or below
- * 1e-30, or the solver's residual exceeds 2^-24 T -- which is what tuch_closest_point_oriented treats as unconstrained.
+ * 1e-30, or the solver's residual exceeds 2^-24 T -- which is what tuch_closest_point with normals treats as unconstrained.
  *   variation [B,N] = lambda0 / (lambda0 + lambda1 + lambda2), within 2 E / trace C + 2^-23 of the float64 value; 0 where
  * the normal is zero.  count [B,N] = n.
  *   Sign: first canonical -- the component of the largest magnitude is positive, the first among equals --; then with a
@@ -604,58 +604,28 @@ int tuch_point_cloud_normals(const void* workspace, size_t workspace_bytes, cons
  * g_v = scale w_v rho'(d2_v) / sum w (every row written, by the lane that owns it: no atomics), grad_transl[b] = sum_v
  * grad_verts[b,v].  per_body, its normaliser, total and grad_transl are fixed-order sums: the same bits in either mode
  * of tuch_set_deterministic, on every call, and for a body alone or in a batch.  ticket as for tuch_scan_fit_terms;
- * scratch: tuch_point_cloud_fit_scratch_bytes(B, V) bytes.  One launch; capturable. */
+ * scratch: tuch_point_cloud_fit_scratch_bytes(B, V) bytes.  One launch; capturable.
+ *   normals (optional) [B,Q,3] or NULL: the term with the oriented query.  The lane that owns vertex v forms the vertex's
+ * normal itself, from the UNTRANSLATED verts, by tuch_vertex_normals' sequence (faces [F,3], vf_off [V+1], vf_ids [3F]
+ * as there, all required, with F > 0 and 3F < 2^31; normalize = 0), so d2 / index have the bits of
+ * tuch_point_cloud_nearest called with these normals and tuch_vertex_normals' raw rows as query_normals, and the term
+ * stays one launch.  The term, a vertex without winner, the fixed-order sums and the gradients are as above; normals
+ * only decide the match and get no gradient.  max_angle_cos and cones as for tuch_point_cloud_nearest.  With normals =
+ * NULL the mesh, the cones and max_angle_cos are ignored whatever they hold. */
 size_t tuch_point_cloud_fit_scratch_bytes(int B, int V);
 int tuch_point_cloud_fit_terms(const void* workspace, size_t workspace_bytes, const float* points, const int32_t* counts,
-                               const float* weights, const float* verts /* [B,V,3] */, const float* transl /* [B,3] */,
-                               const int32_t* hint /* [B,V] or NULL */, float max_distance, int B, int Q, int V,
-                               const float* vertex_weights, int vertex_weight_layout, int rho, float sigma, float scale,
-                               float* d2 /* [B,V] */, int32_t* index /* [B,V] */, int* ticket, float* per_body /* [B] */,
-                               float* total /* [1] */, float* grad_verts /* [B,V,3] */, float* grad_transl /* [B,3] */,
-                               void* scratch, size_t scratch_bytes, void* stream);
-/* The oriented query: tuch_point_cloud_nearest's rule over the ADMISSIBLE valid points.  normals [B,Q,3] belong to the
- * points, in the caller's order; query_normals [B,N,3] to the queries (neither is translated by shift).  With
- * c = max_angle_cos in [0, 1), c2 = c c formed once, for a query normal u and a point normal n, every operation rounded
- * to float32 on its own:
- *   uu = (ux ux + uy uy) + uz uz,  nn = (nx nx + ny ny) + nz nz,  s = (ux nx + uy ny) + uz nz,
- *   admissible  <=>  s > 0  and  s s >= c2 (uu nn).
- * A pair is unconstrained -- admissible -- when uu or nn is 0 or not finite: a missing normal, the zero rows of
- * tuch_point_cloud_normals among them.  Valid points, q = x + shift, the squared distance, the packed key, max_distance,
- * query_counts and the no-winner outputs (-1 / +inf) are tuch_point_cloud_nearest's; the winner is the smallest key over
- * the admissible valid points; a hint seeds the search only if it names a valid, admissible point within the limit.
- * The outputs equal a float32 brute-force sweep under this rule bit for bit: for any batch, order of queries or points,
- * resolution and hint content, eager or replayed, with cones or with cones NULL.
- *   cones: per-block normal cones that let a lane pass by a block of the grid none of whose points is admissible for
- * its normal (they may only skip, never decide; csrc/point_cloud.hip has the derivation).  A caller-provided buffer of
- * tuch_point_cloud_cones_bytes(B, resolution) bytes, filled by tuch_point_cloud_build_cones AFTER tuch_point_cloud_build
- * from the same normals (one launch, capturable) and stale after the next build; NULL: no block is skipped. */
-size_t tuch_point_cloud_cones_bytes(int B, int resolution);
-int tuch_point_cloud_build_cones(const void* workspace, size_t workspace_bytes, const float* normals /* [B,Q,3] */, int B,
-                                 int Q, int resolution, void* cones, size_t cones_bytes, void* stream);
-int tuch_point_cloud_nearest_oriented(const void* workspace, size_t workspace_bytes, const float* points,
-                                      const int32_t* counts, const float* weights, const float* normals /* [B,Q,3] */,
-                                      const float* queries /* [B,N,3] */, const float* query_normals /* [B,N,3] */,
-                                      const float* shift, const int32_t* query_counts, const int32_t* hint,
-                                      float max_distance, float max_angle_cos, const void* cones /* or NULL */,
-                                      size_t cones_bytes, int B, int Q, int N, float* d2, int32_t* index, void* stream);
-/* The oriented term: tuch_point_cloud_fit_terms with the oriented query.  The lane that owns vertex v forms the vertex's
- * normal itself, from the UNTRANSLATED verts, by tuch_vertex_normals' sequence (faces [F,3], vf_off [V+1], vf_ids [3F]
- * as there; normalize = 0), so d2 / index have the bits of tuch_point_cloud_nearest_oriented called with
- * tuch_vertex_normals' raw rows, and the term stays one launch.  The term, a vertex without winner, the fixed-order sums
- * and the gradients are tuch_point_cloud_fit_terms'; normals only decide the match and get no gradient. */
-int tuch_point_cloud_fit_terms_oriented(const void* workspace, size_t workspace_bytes, const float* points,
-                                        const int32_t* counts, const float* weights, const float* normals /* [B,Q,3] */,
-                                        float max_angle_cos, const int32_t* faces, const int32_t* vf_off,
-                                        const int32_t* vf_ids, int F, const void* cones /* or NULL */, size_t cones_bytes,
-                                        const float* verts, const float* transl, const int32_t* hint, float max_distance,
-                                        int B, int Q, int V, const float* vertex_weights, int vertex_weight_layout, int rho,
-                                        float sigma, float scale, float* d2, int32_t* index, int* ticket, float* per_body,
-                                        float* total, float* grad_verts, float* grad_transl, void* scratch,
-                                        size_t scratch_bytes, void* stream);
+                               const float* weights, const float* normals /* [B,Q,3] or NULL */, float max_angle_cos,
+                               const int32_t* faces, const int32_t* vf_off, const int32_t* vf_ids, int F,
+                               const void* cones /* or NULL */, size_t cones_bytes, const float* verts /* [B,V,3] */,
+                               const float* transl /* [B,3] */, const int32_t* hint /* [B,V] or NULL */, float max_distance,
+                               int B, int Q, int V, const float* vertex_weights, int vertex_weight_layout, int rho,
+                               float sigma, float scale, float* d2 /* [B,V] */, int32_t* index /* [B,V] */, int* ticket,
+                               float* per_body /* [B] */, float* total /* [1] */, float* grad_verts /* [B,V,3] */,
+                               float* grad_transl /* [B,3] */, void* scratch, size_t scratch_bytes, void* stream);
 /* Posed vertex normals (csrc/vertex_normals.hip).  vf_off [V+1], vf_ids [3F]: the vertex -> faces lists of
  * tuch_render_mesh (vertex v is a corner of the faces vf_ids[vf_off[v] .. vf_off[v+1]), ascending).  One fixed float32
  * sequence, nothing fused: for vertex v, over its faces in that order, m = (b - a) x (c - a) exactly as
- * tuch_closest_point_oriented forms it, u_v = ((0 + m_1) + m_2) + ... per component: the area-weighted normal,
+ * tuch_closest_point with normals forms it, u_v = ((0 + m_1) + m_2) + ... per component: the area-weighted normal,
  * unnormalised.  normalize != 0: divided by sqrt(uu), uu = (ux ux + uy uy) + uz uz; a zero row where uu is 0 or not
  * finite.  out [B,V,3], every row written by the lane that owns it: no atomics, the same bits for a vertex alone or in
  * any batch, eager or replayed; table entries are clamped before they address anything; a body that holds NaN changes
@@ -890,13 +860,11 @@ int tuch_crop_batch(const void* buffer, size_t buffer_bytes, const tuch_crop_rec
  * library's business (the loss is a sum over the points): tuch_hd_model_info reports it (order_host[k] = caller's
  * index of the k-th point). */
 typedef struct tuch_hd_model tuch_hd_model;
-int tuch_hd_model_create(tuch_hd_model** out, const tuch_contact_model* contact_model, int N, const int32_t* hd_idx,
-                         const float* hd_w, const int32_t* hd_face);
-/* The same for a regressor with up to K (1..8) non-zeros per row: hd_idx / hd_w [N,K], rows with fewer non-zeros padded
- * with weight 0 (any valid vertex id).  The reference multiplies the DENSE matrix (loss.py:285): a regressor file that is
- * not a plain barycentric sampling (<= 3 non-zeros) still loads. */
-int tuch_hd_model_create_k(tuch_hd_model** out, const tuch_contact_model* contact_model, int N, int K,
-                           const int32_t* hd_idx, const float* hd_w, const int32_t* hd_face);
+/* A regressor with up to K (1..8) non-zeros per row: hd_idx / hd_w [N,K], rows with fewer non-zeros padded with weight 0
+ * (any valid vertex id); K = 3 is the plain barycentric sampling.  The reference multiplies the DENSE matrix
+ * (loss.py:285): a regressor file that is not a plain barycentric sampling (<= 3 non-zeros) still loads. */
+int tuch_hd_model_create(tuch_hd_model** out, const tuch_contact_model* contact_model, int N, int K,
+                         const int32_t* hd_idx, const float* hd_w, const int32_t* hd_face);
 void tuch_hd_model_destroy(tuch_hd_model* model);
 int tuch_hd_model_info(const tuch_hd_model* model, int* N, int32_t* order_host);
 /* One call = loss.py:274-315 for the whole batch: exterior [B,V] u8, min_d2 [B,V], partner [B,V] int32 are the

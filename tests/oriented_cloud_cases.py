@@ -2,7 +2,7 @@
 tests/test_gpu_oriented_cloud.py on the device).  No GPU here.
 
   vertex_normals32   tuch_vertex_normals' rule as an explicit numpy float32 loop in table order: m of every face by
-                     oriented_point_cases.face_normals32 (the sequence of tuch_closest_point_oriented), u = ((0 + m_1) +
+                     oriented_point_cases.face_normals32 (the sequence of tuch_closest_point with normals), u = ((0 + m_1) +
                      m_2) + ..., normalize: / sqrt(uu) with a zero row where uu is 0 or not finite
   vertex_normals64   the same sums in float64
   pair_rule32        THE admissibility of (query normal, point normal) pairs in numpy float32, op for op

@@ -79,12 +79,13 @@ def test_abi_symbols_and_argument_checks():
     L = _C.lib()
     for name in ('tuch_closest_point_workspace_bytes', 'tuch_closest_point', 'tuch_closest_point_bwd'):
         assert name in _C.exported_symbols() and hasattr(L, name)
-    assert L.tuch_abi_version() == 2                                # the change is additive
+    assert L.tuch_abi_version() == 3
     null = ctypes.c_void_p(0)
-    assert L.tuch_closest_point(null, null, null, null, 1, 1, null, null, null, null, 0, null) != 0
+    assert L.tuch_closest_point(null, null, null, null, 0.0, null, null, 1, 1, null, null, null, null, 0, null) != 0
     assert b'tuch_closest_point: null pointer' in L.tuch_last_error()
     assert L.tuch_closest_point_bwd(null, null, null, null, null, null, 1, 1, null, null, null, null) != 0
     assert b'tuch_closest_point_bwd: null pointer' in L.tuch_last_error()
-    assert L.tuch_closest_point_workspace_bytes(null, 0, 5) == 0
-    assert L.tuch_closest_point_workspace_bytes(null, 4, 5) == 0    # no model: nothing to size
+    for oriented in (0, 1):
+        assert L.tuch_closest_point_workspace_bytes(null, 0, 5, oriented) == 0
+        assert L.tuch_closest_point_workspace_bytes(null, 4, 5, oriented) == 0    # no model: nothing to size
 

@@ -130,20 +130,46 @@ def test_abi_symbols_and_argument_checks():
              'tuch_point_cloud_set_canary', 'tuch_point_cloud_canary_hits')
     for name in names:
         assert name in _C.exported_symbols() and hasattr(L, name) and name + '(' in header
-    assert L.tuch_abi_version() == 2                                    # the change is additive
+    assert L.tuch_abi_version() == 3
     null = ctypes.c_void_p(0)
+    some = ctypes.c_void_p(256)     # a non-null pointer that is never followed
     assert L.tuch_point_cloud_build(null, null, null, 1, 1, 1, null, 0, null) != 0
     assert b'tuch_point_cloud_build: null pointer' in L.tuch_last_error()
-    assert L.tuch_point_cloud_nearest(null, 0, *([null] * 7), 0.0, 1, 1, 1, null, null, null) != 0
-    assert b'tuch_point_cloud_nearest: null pointer' in L.tuch_last_error()
-    assert L.tuch_point_cloud_fit_terms(null, 0, *([null] * 6), 0.0, 1, 1, 1, null, 0, 1, 0.0, 1.0, *([null] * 8), 0, null) != 0
+
+    def nearest(normals, query_normals, cos):
+        return L.tuch_point_cloud_nearest(null, 0, null, null, null, normals, null, query_normals, null, null, null, 0.0, cos,
+                                          null, 0, 1, 1, 1, null, null, null)
+
+    def fit_terms(normals, cos, mesh, faces):
+        return L.tuch_point_cloud_fit_terms(null, 0, null, null, null, normals, cos, mesh, mesh, mesh, faces, null, 0, null,
+                                            null, null, 0.0, 1, 1, 1, null, 0, 1, 0.0, 1.0, *([null] * 8), 0, null)
+
+    # the one function reports under its own name with and without normals; without them the cosine is not read
+    for normals, cos in ((null, 0.0), (null, float('nan')), (null, 2.0), (some, 0.5)):
+        assert nearest(normals, normals, cos) != 0
+        assert b'tuch_point_cloud_nearest: null pointer' in L.tuch_last_error(), cos
+        assert fit_terms(normals, cos, normals, 1) != 0
+        assert b'tuch_point_cloud_fit_terms: null pointer' in L.tuch_last_error(), cos
+    # normals and query_normals go together
+    for normals, query_normals in ((some, null), (null, some)):
+        assert nearest(normals, query_normals, 0.5) == -1               # TUCH_ERR_ARG
+        message = L.tuch_last_error()
+        assert b'tuch_point_cloud_nearest: ' in message and b'normals' in message and b'query_normals' in message
+    # with normals: the cosine, the mesh and its size are asked for
+    for bad in (1.0, -0.1, float('nan')):
+        assert nearest(some, some, bad) != 0
+        assert b'tuch_point_cloud_nearest: max_angle_cos' in L.tuch_last_error(), bad
+        assert fit_terms(some, bad, some, 1) != 0
+        assert b'tuch_point_cloud_fit_terms: max_angle_cos' in L.tuch_last_error(), bad
+    assert fit_terms(some, 0.5, null, 1) != 0
     assert b'tuch_point_cloud_fit_terms: null pointer' in L.tuch_last_error()
+    assert fit_terms(some, 0.5, some, 0) != 0
+    assert b'tuch_point_cloud_fit_terms: bad sizes' in L.tuch_last_error()
     assert L.tuch_point_cloud_grid(null, 1, 1, null, null, null) != 0
     assert b'tuch_point_cloud_grid: null pointer' in L.tuch_last_error()
     assert L.tuch_point_cloud_canary_hits(null, None, 0) != 0
     assert b'tuch_point_cloud_canary_hits: null pointer' in L.tuch_last_error()
-    # bad sizes name the entry point too (a non-null pointer that is never followed)
-    some = ctypes.c_void_p(256)
+    # bad sizes name the entry point too
     assert L.tuch_point_cloud_build(some, null, null, 0, 5, 4, some, 1 << 20, null) != 0
     assert b'tuch_point_cloud_build: bad sizes' in L.tuch_last_error()
     assert L.tuch_point_cloud_build(some, null, null, 1, 5, 4, some, 16, null) != 0

@@ -373,6 +373,26 @@ def test_term_matches_float64(rho, weighted, tau):
         assert np.array_equal(got[key], again[key]), key
 
 
+@pytest.mark.parametrize('name', ['icosphere', 'body122'])
+def test_term_without_an_angle_has_the_plain_querys_bits(name):
+    """ops.cloud_fit without max_angle: the NearestPoint of PointCloud.nearest without query_normals, bit for bit -- on a
+    plain cloud, and on one that has been given normals, which neither call then reads."""
+    from tuch_amd import ops
+    c = cf.cloud_case(name, 3, 257, 257)
+    cloud = _cloud(c['points'])
+    verts, transl = _dev(c['queries']), _dev(c['shift'])
+    plain = cloud.nearest(verts, transl)
+    assert (plain.index >= 0).all()
+    normals = np.random.default_rng(7).standard_normal(c['points'].shape).astype(F32)
+    for oriented in (False, True):
+        if oriented:
+            cloud.orient(_dev(normals))
+            again = cloud.nearest(verts, transl)
+            assert torch.equal(again.index, plain.index) and torch.equal(again.d2, plain.d2)
+        _, _, near = ops.cloud_fit(cloud, verts, transl)
+        assert torch.equal(near.index, plain.index) and torch.equal(near.d2, plain.d2), oriented
+
+
 def test_term_at_batch_65_with_two_chunks_matches_float64():
     """65 bodies x 257 weighted vertices against clouds of 65 points: two workgroups per body (and two strides of the
     normaliser's sum), and 4 x 65 = 260 (body, component) sums for the 256 threads of the workgroup that arrives last --

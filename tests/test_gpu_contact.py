@@ -1467,7 +1467,7 @@ def test_hd_branch_selection_partners_and_graph_capture(tag):
 
 
 def test_hd_branch_with_a_general_sparse_regressor():
-    """HD regressor rows with up to FIVE non-zeros (tuch_hd_model_create_k; the reference multiplies the dense matrix,
+    """HD regressor rows with up to FIVE non-zeros (tuch_hd_model_create with K = 5; the reference multiplies the dense matrix,
     loss.py:285): RegressorLoss.contact_loss(use_hd=True) and its gradient against the oracle's HD branch fed with the
     same regressor as a dense matrix."""
     import types

@@ -1,5 +1,5 @@
-"""GPU: the normal-compatible closest point (csrc/closest_point.hip: tuch_closest_point_oriented), the data term over it
-(csrc/scan_fit.hip: tuch_scan_fit_terms_oriented) and fit.ScanFitter with scan normals, against the float32 rule and the
+"""GPU: the normal-compatible closest point (csrc/closest_point.hip: tuch_closest_point with normals), the data term over it
+(csrc/scan_fit.hip: tuch_scan_fit_terms with normals) and fit.ScanFitter with scan normals, against the float32 rule and the
 float64 admissible-set statement of tests/oriented_point_cases.py: answers, threshold queries, bit identity under
 batching, query order, replay, hints and face grouping, the reductions to the plain call, NaN bodies and normals, padding,
 the workspace guards, the SMPL-size case, the term with its gradients, the fitter.
@@ -187,16 +187,16 @@ def test_hint_may_alias_the_face_output(name):
     counts = _dev(np.array([257, 40, 130], np.int32))
     plain = m.closest_point(verts, points, counts, normals=normals, max_angle=60.0)
     L = _C.lib()
-    nbytes = L.tuch_closest_point_oriented_workspace_bytes(m._handle, 3, 257)
+    nbytes = L.tuch_closest_point_workspace_bytes(m._handle, 3, 257, 1)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=DEV)
     cosine = float(oc.cos32(60.0))
     for kind in HINT_KINDS:
         both = _dev(_hints(kind, c, plain.face.cpu().numpy()))
         d2, bary = torch.empty_like(plain.d2), torch.empty_like(plain.bary)
         for again in range(2):                                          # the second from what the first left: the loop's use
-            _C.check(L.tuch_closest_point_oriented(m._handle, _C.ptr(verts), _C.ptr(points), _C.ptr(normals), cosine,
-                                                   _C.ptr(counts), _C.ptr(both), 3, 257, _C.ptr(d2), _C.ptr(both), _C.ptr(bary),
-                                                   _C.ptr(ws), nbytes, _C.stream()))
+            _C.check(L.tuch_closest_point(m._handle, _C.ptr(verts), _C.ptr(points), _C.ptr(normals), cosine, _C.ptr(counts),
+                                          _C.ptr(both), 3, 257, _C.ptr(d2), _C.ptr(both), _C.ptr(bary), _C.ptr(ws), nbytes,
+                                          _C.stream()))
             _same(plain, (d2, both, bary), (name, kind, again))
 
 
@@ -267,6 +267,27 @@ def test_reductions_to_the_plain_call(name):
     assert not torch.equal(plain.face[1], got.face[1])                  # (the filter does change body 1)
     # with a hint, zero normals are still the plain call
     _same(plain, search(m, c['verts'], c['points'], zero, 60.0, hint=plain.face.cpu().numpy()), 'zero normals, hinted')
+
+
+@pytest.mark.parametrize('name', ['strip', 'body122'])
+def test_plain_form_ignores_the_cosine(name):
+    """The C call with normals = NULL, whatever max_angle_cos holds, through a workspace of the plain size (no cones): the
+    bits of ContactModel.closest_point without normals."""
+    from tuch_amd import _C
+    c = oc.case(name, 3, 257, 60.0)
+    m = model(name)
+    verts, points = _dev(c['verts']), _dev(c['points'])
+    counts = _dev(np.array([257, 40, 130], np.int32))
+    plain = m.closest_point(verts, points, counts)
+    L = _C.lib()
+    nbytes = L.tuch_closest_point_workspace_bytes(m._handle, 3, 257, 0)
+    assert 0 < nbytes < L.tuch_closest_point_workspace_bytes(m._handle, 3, 257, 1)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=DEV)
+    for cosine in (0.0, 0.5, float('nan')):
+        d2, face, bary = torch.empty_like(plain.d2), torch.empty_like(plain.face), torch.empty_like(plain.bary)
+        _C.check(L.tuch_closest_point(m._handle, _C.ptr(verts), _C.ptr(points), None, cosine, _C.ptr(counts), None, 3, 257,
+                                      _C.ptr(d2), _C.ptr(face), _C.ptr(bary), _C.ptr(ws), nbytes, _C.stream()))
+        _same(plain, (d2, face, bary), (name, cosine))
 
 
 # ---------------------------------------------------------------------------------------------------------- 7 robustness

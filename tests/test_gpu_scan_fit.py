@@ -1,5 +1,5 @@
 """GPU: fitting SMPL to unregistered points.  The hinted closest-point search (csrc/closest_point.hip:
-tuch_closest_point_hinted) against the unhinted one, bit for bit, for every kind of hint; the data term (csrc/scan_fit.hip)
+tuch_closest_point with a hint) against the unhinted one, bit for bit, for every kind of hint; the data term (csrc/scan_fit.hip)
 against the float64 statements of tests/scan_fit_cases.py; fit.ScanFitter against the float64 loop there.
 
 Observed on an MI355X (2026-10-19): term error / bound at most 0.022 ('squared'), 7.6e-5 ('distance'), 4.8e-4 ('gmof');
@@ -81,17 +81,17 @@ def test_hint_may_alias_the_face_output(name):
     verts, points, counts = _dev(c['verts']), _dev(c['points']), _dev(np.array([257, 40, 130], np.int32))
     plain = m.closest_point(verts, points, counts)
     L = _C.lib()
-    nbytes = L.tuch_closest_point_workspace_bytes(m._handle, 3, 257)
+    nbytes = L.tuch_closest_point_workspace_bytes(m._handle, 3, 257, 0)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=DEV)
     for kind in sc.HINT_KINDS:
         both = _dev(sc.hints(kind, c['points'], c['verts'], c['faces'], plain.face.cpu().numpy()))
         d2, bary = torch.empty_like(plain.d2), torch.empty_like(plain.bary)
-        _C.check(L.tuch_closest_point_hinted(m._handle, _C.ptr(verts), _C.ptr(points), _C.ptr(counts), _C.ptr(both), 3, 257,
-                                             _C.ptr(d2), _C.ptr(both), _C.ptr(bary), _C.ptr(ws), nbytes, _C.stream()))
+        _C.check(L.tuch_closest_point(m._handle, _C.ptr(verts), _C.ptr(points), None, 0.0, _C.ptr(counts), _C.ptr(both), 3, 257,
+                                      _C.ptr(d2), _C.ptr(both), _C.ptr(bary), _C.ptr(ws), nbytes, _C.stream()))
         _same(plain, ops.ClosestPoint(d2, both, bary), (name, kind))
         # and once more from what it left: the loop's own use
-        _C.check(L.tuch_closest_point_hinted(m._handle, _C.ptr(verts), _C.ptr(points), _C.ptr(counts), _C.ptr(both), 3, 257,
-                                             _C.ptr(d2), _C.ptr(both), _C.ptr(bary), _C.ptr(ws), nbytes, _C.stream()))
+        _C.check(L.tuch_closest_point(m._handle, _C.ptr(verts), _C.ptr(points), None, 0.0, _C.ptr(counts), _C.ptr(both), 3, 257,
+                                      _C.ptr(d2), _C.ptr(both), _C.ptr(bary), _C.ptr(ws), nbytes, _C.stream()))
         _same(plain, ops.ClosestPoint(d2, both, bary), (name, kind, 'again'))
 
 

@@ -281,4 +281,4 @@ def test_binding_declares_the_entry_point():
     from tuch_amd import _C, ops
     assert 'tuch_crop_batch' in _C.exported_symbols()
     assert ops.CROP_RECORD.itemsize == 120
-    assert _C.lib().tuch_abi_version() == _C.ABI_VERSION == 2
+    assert _C.lib().tuch_abi_version() == _C.ABI_VERSION == 3

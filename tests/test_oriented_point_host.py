@@ -93,22 +93,36 @@ def test_abi_symbols_and_argument_checks():
     from tuch_amd import _C
     L = _C.lib()
     header = open(os.path.join(ROOT, 'include', 'tuch_amd.h')).read()
-    for name in ('tuch_closest_point_oriented', 'tuch_closest_point_oriented_workspace_bytes', 'tuch_scan_fit_terms_oriented',
-                 'tuch_scan_fit_oriented_workspace_bytes'):
+    for name in ('tuch_closest_point', 'tuch_closest_point_workspace_bytes', 'tuch_scan_fit_terms',
+                 'tuch_scan_fit_workspace_bytes'):
         assert name in _C.exported_symbols() and hasattr(L, name) and name + '(' in header
-    assert L.tuch_abi_version() == 2                                # the change is additive
+    assert L.tuch_abi_version() == 3
     null = ctypes.c_void_p(0)
-    assert L.tuch_closest_point_oriented(null, null, null, null, 0.5, null, null, 1, 1, null, null, null, null, 0, null) != 0
-    assert b'tuch_closest_point_oriented: null pointer' in L.tuch_last_error()
-    assert L.tuch_scan_fit_terms_oriented(*([null] * 5), 0.5, *([null] * 3), 1, 1, 1, 0.0, *([null] * 10), 0, null) != 0
-    assert b'tuch_scan_fit_terms_oriented: null pointer' in L.tuch_last_error()
+    some = ctypes.c_void_p(64)      # normals that are not NULL and never read: the model is NULL
+
+    def closest_point(normals, cos):
+        return L.tuch_closest_point(null, null, null, normals, cos, null, null, 1, 1, null, null, null, null, 0, null)
+
+    def scan_fit_terms(normals, cos):
+        return L.tuch_scan_fit_terms(*([null] * 4), normals, cos, *([null] * 3), 1, 1, 1, 0.0, *([null] * 10), 0, null)
+
+    assert closest_point(some, 0.5) != 0
+    assert b'tuch_closest_point: null pointer' in L.tuch_last_error()
+    assert scan_fit_terms(some, 0.5) != 0
+    assert b'tuch_scan_fit_terms: null pointer' in L.tuch_last_error()
     for bad in (1.0, 1.5, -0.1, float('nan'), float('inf')):
-        assert L.tuch_closest_point_oriented(null, null, null, null, bad, null, null, 1, 1, null, null, null, null, 0, null) != 0
-        assert b'tuch_closest_point_oriented: max_angle_cos' in L.tuch_last_error(), bad
-        assert L.tuch_scan_fit_terms_oriented(*([null] * 5), bad, *([null] * 3), 1, 1, 1, 0.0, *([null] * 10), 0, null) != 0
-        assert b'tuch_scan_fit_terms_oriented: max_angle_cos' in L.tuch_last_error(), bad
-    assert L.tuch_closest_point_oriented_workspace_bytes(null, 4, 5) == 0      # no model: nothing to size
-    assert L.tuch_scan_fit_oriented_workspace_bytes(null, 4, 5) == 0
+        assert closest_point(some, bad) != 0
+        assert b'tuch_closest_point: max_angle_cos' in L.tuch_last_error(), bad
+        assert scan_fit_terms(some, bad) != 0
+        assert b'tuch_scan_fit_terms: max_angle_cos' in L.tuch_last_error(), bad
+    # without normals the cosine is not read: garbage in it is no error of its own
+    for garbage in (float('nan'), 2.0):
+        assert closest_point(null, garbage) != 0
+        assert b'tuch_closest_point: null pointer' in L.tuch_last_error(), garbage
+        assert scan_fit_terms(null, garbage) != 0
+        assert b'tuch_scan_fit_terms: null pointer' in L.tuch_last_error(), garbage
+    assert L.tuch_closest_point_workspace_bytes(null, 4, 5, 1) == 0      # no model: nothing to size
+    assert L.tuch_scan_fit_workspace_bytes(null, 4, 5, 1) == 0
 
 
 def test_wrapper_argument_checks():

@@ -87,21 +87,24 @@ def test_abi_symbols_and_argument_checks():
     from tuch_amd import _C
     L = _C.lib()
     header = open(os.path.join(ROOT, 'include', 'tuch_amd.h')).read()
-    for name in ('tuch_closest_point_hinted', 'tuch_contact_model_face_groups', 'tuch_scan_fit_workspace_bytes',
+    for name in ('tuch_closest_point', 'tuch_contact_model_face_groups', 'tuch_scan_fit_workspace_bytes',
                  'tuch_scan_fit_terms'):
         assert name in _C.exported_symbols() and hasattr(L, name) and name + '(' in header
-    assert L.tuch_abi_version() == 2                                # the change is additive
+    assert L.tuch_abi_version() == 3
     null = ctypes.c_void_p(0)
-    assert L.tuch_closest_point_hinted(null, null, null, null, null, 1, 1, null, null, null, null, 0, null) != 0
-    assert b'tuch_closest_point_hinted: null pointer' in L.tuch_last_error()
-    assert L.tuch_closest_point(null, null, null, null, 1, 1, null, null, null, null, 0, null) != 0
-    assert b'tuch_closest_point: null pointer' in L.tuch_last_error()      # (each entry point names itself)
-    assert L.tuch_scan_fit_terms(*([null] * 7), 1, 1, 1, 0.0, *([null] * 10), 0, null) != 0
-    assert b'tuch_scan_fit_terms: null pointer' in L.tuch_last_error()
+    some = ctypes.c_void_p(64)      # not NULL, never read: the model is NULL, which every call reports first
+    # the one function reports under its own name for the plain, the hinted and the oriented argument set
+    for normals, cos, hint in ((null, 0.0, null), (null, 0.0, some), (some, 0.5, some)):
+        assert L.tuch_closest_point(null, null, null, normals, cos, null, hint, 1, 1, null, null, null, null, 0, null) != 0
+        assert b'tuch_closest_point: null pointer' in L.tuch_last_error()
+        assert L.tuch_scan_fit_terms(null, null, null, null, normals, cos, null, null, hint, 1, 1, 1, 0.0, *([null] * 10), 0,
+                                     null) != 0
+        assert b'tuch_scan_fit_terms: null pointer' in L.tuch_last_error()
     assert L.tuch_contact_model_face_groups(null, None, null, null, null) != 0
     assert b'tuch_contact_model_face_groups: null model' in L.tuch_last_error()
-    assert L.tuch_scan_fit_workspace_bytes(null, 4, 5) == 0         # no model: nothing to size
-    assert L.tuch_scan_fit_workspace_bytes(null, 0, 5) == 0
+    for oriented in (0, 1):
+        assert L.tuch_scan_fit_workspace_bytes(null, 4, 5, oriented) == 0         # no model: nothing to size
+        assert L.tuch_scan_fit_workspace_bytes(null, 0, 5, oriented) == 0
 
 
 _CHILD = r'''

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Timing of the normal-compatible model -> scan term (csrc/point_cloud.hip: tuch_point_cloud_fit_terms_oriented;
+"""Timing of the normal-compatible model -> scan term (csrc/point_cloud.hip: tuch_point_cloud_fit_terms with normals;
 ops.cloud_fit with max_angle) against the unoriented term, and of a whole two-sided ScanFitter iteration with and
 without model_to_scan_normals, DESIGN.md §3:
 

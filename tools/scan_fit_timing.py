@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Timing of the fit to unregistered points (tuch_amd/fit.py: ScanFitter, csrc/scan_fit.hip) and of the hinted
-closest-point search (csrc/closest_point.hip: tuch_closest_point_hinted), DESIGN.md §3:
+closest-point search (csrc/closest_point.hip: tuch_closest_point with a hint), DESIGN.md §3:
 
     python tools/scan_fit_timing.py                 # all of it, one JSON line each
     python tools/scan_fit_timing.py --only search   # the search alone
@@ -22,7 +22,7 @@ pose + a translation: its vertices in vertex order (Q = 6890) and three points p
   closest_point + torch ops for rho + torch.optim.Adam(capturable=True), eager on the device.
 * --normals ANGLE: the scan carries the true body's normals (area-weighted vertex normals for the vertex scan, the face's
   normal for the face samples, computed with torch).  On the same two states the oriented search
-  (tuch_closest_point_oriented) against the unoriented one, unhinted and hinted, the versions alternating; the share of
+  (tuch_closest_point with normals) against the unoriented one, unhinted and hinted, the versions alternating; the share of
   matched points, the share of answers the filter changed, the group visits of both searches (the oriented ones: the box
   test under the lane's final d2 -- +inf for an unmatched lane -- and the group's normal cone, restated here, not proving
   the group inadmissible); `ScanFitter` per iteration with and without normals.

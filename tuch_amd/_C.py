@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('TUCH_AMD_LIB') or os.path.join(_HERE, 'libtuch_amd.so')
 _lib = None
 
-ABI_VERSION = 2      # tuch_abi_version() of the library _SIGNATURES was written for
+ABI_VERSION = 3      # tuch_abi_version() of the library _SIGNATURES was written for
 
 # name -> (restype, argtypes); mirrors include/tuch_amd.h
 _SIGNATURES = {
@@ -89,8 +89,7 @@ _SIGNATURES = {
     'tuch_estimate_translation': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_void_p, c_void_p]),
     'tuch_rotmat_to_angle_axis': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     'tuch_winding_tree_work': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
-    'tuch_hd_model_create': (c_int, [POINTER(c_void_p), c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
-    'tuch_hd_model_create_k': (c_int, [POINTER(c_void_p), c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'tuch_hd_model_create': (c_int, [POINTER(c_void_p), c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'tuch_hd_model_destroy': (None, [c_void_p]),
     'tuch_hd_model_info': (c_int, [c_void_p, POINTER(c_int), c_void_p]),
     'tuch_hd_contact_saved_bytes': (c_size_t, [c_void_p, c_int]),
@@ -114,40 +113,29 @@ _SIGNATURES = {
     'tuch_winding_points_workspace_bytes': (c_size_t, [c_void_p, c_int, c_int]),
     'tuch_winding_points': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p,
                                     c_void_p, c_size_t, c_void_p]),
-    'tuch_closest_point_workspace_bytes': (c_size_t, [c_void_p, c_int, c_int]),
-    'tuch_closest_point': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+    'tuch_closest_point_workspace_bytes': (c_size_t, [c_void_p, c_int, c_int, c_int]),
+    'tuch_closest_point': (c_int, [c_void_p] * 4 + [c_float, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_size_t, c_void_p]),
     'tuch_closest_point_bwd': (c_int, [c_void_p] * 6 + [c_int, c_int] + [c_void_p] * 4),
-    'tuch_closest_point_hinted': (c_int, [c_void_p] * 5 + [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
-                                          c_void_p]),
-    'tuch_closest_point_oriented_workspace_bytes': (c_size_t, [c_void_p, c_int, c_int]),
-    'tuch_closest_point_oriented': (c_int, [c_void_p] * 4 + [c_float, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
-                                            c_void_p, c_void_p, c_size_t, c_void_p]),
     'tuch_contact_model_face_groups': (c_int, [c_void_p, POINTER(c_int), c_void_p, c_void_p, c_void_p]),
-    'tuch_scan_fit_workspace_bytes': (c_size_t, [c_void_p, c_int, c_int]),
-    'tuch_scan_fit_terms': (c_int, [c_void_p] * 7 + [c_int, c_int, c_int, c_float] + [c_void_p] * 10 + [c_size_t, c_void_p]),
-    'tuch_scan_fit_oriented_workspace_bytes': (c_size_t, [c_void_p, c_int, c_int]),
-    'tuch_scan_fit_terms_oriented': (c_int, [c_void_p] * 5 + [c_float] + [c_void_p] * 3 + [c_int, c_int, c_int, c_float]
-                                     + [c_void_p] * 10 + [c_size_t, c_void_p]),
+    'tuch_scan_fit_workspace_bytes': (c_size_t, [c_void_p, c_int, c_int, c_int]),
+    'tuch_scan_fit_terms': (c_int, [c_void_p] * 5 + [c_float] + [c_void_p] * 3 + [c_int, c_int, c_int, c_float]
+                            + [c_void_p] * 10 + [c_size_t, c_void_p]),
     'tuch_point_cloud_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
     'tuch_point_cloud_build': (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_void_p, c_size_t, c_void_p]),
-    'tuch_point_cloud_nearest': (c_int, [c_void_p, c_size_t] + [c_void_p] * 7 + [c_float, c_int, c_int, c_int] + [c_void_p] * 3),
+    'tuch_point_cloud_nearest': (c_int, [c_void_p, c_size_t] + [c_void_p] * 9 + [c_float, c_float, c_void_p, c_size_t,
+                                         c_int, c_int, c_int] + [c_void_p] * 3),
     'tuch_point_cloud_knn': (c_int, [c_void_p, c_size_t] + [c_void_p] * 6 + [c_float, c_int, c_int, c_int, c_int]
                              + [c_void_p] * 3),
     'tuch_point_cloud_normals': (c_int, [c_void_p, c_size_t] + [c_void_p] * 6 + [c_float, c_int, c_int, c_int, c_int, c_void_p,
                                          c_int] + [c_void_p] * 5),
     'tuch_point_cloud_fit_scratch_bytes': (c_size_t, [c_int, c_int]),
-    'tuch_point_cloud_fit_terms': (c_int, [c_void_p, c_size_t] + [c_void_p] * 6 + [c_float, c_int, c_int, c_int, c_void_p, c_int,
-                                           c_int, c_float, c_float] + [c_void_p] * 8 + [c_size_t, c_void_p]),
+    'tuch_point_cloud_fit_terms': (c_int, [c_void_p, c_size_t] + [c_void_p] * 4 + [c_float] + [c_void_p] * 3
+                                   + [c_int, c_void_p, c_size_t] + [c_void_p] * 3
+                                   + [c_float, c_int, c_int, c_int, c_void_p, c_int, c_int, c_float, c_float] + [c_void_p] * 8
+                                   + [c_size_t, c_void_p]),
     'tuch_point_cloud_cones_bytes': (c_size_t, [c_int, c_int]),
     'tuch_point_cloud_build_cones': (c_int, [c_void_p, c_size_t, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    'tuch_point_cloud_nearest_oriented': (c_int, [c_void_p, c_size_t] + [c_void_p] * 9 + [c_float, c_float, c_void_p, c_size_t,
-                                                  c_int, c_int, c_int] + [c_void_p] * 3),
-    'tuch_point_cloud_fit_terms_oriented': (c_int, [c_void_p, c_size_t] + [c_void_p] * 4 + [c_float] + [c_void_p] * 3
-                                            + [c_int, c_void_p, c_size_t] + [c_void_p] * 3 + [c_float, c_int, c_int, c_int,
-                                                                                           c_void_p, c_int, c_int, c_float,
-                                                                                           c_float] + [c_void_p] * 8
-                                            + [c_size_t, c_void_p]),
     'tuch_vertex_normals': (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 2),
     'tuch_point_cloud_grid': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'tuch_point_cloud_set_canary': (c_int, [c_int]),

@@ -1,5 +1,5 @@
-// Closest point on the posed surface for arbitrary query points (tuch_closest_point and tuch_closest_point_hinted,
-// include/tuch_amd.h; tuch_cp_search for scan_fit.hip), its adjoint and the face groups it walks.
+// Closest point on the posed surface for arbitrary query points (tuch_closest_point, include/tuch_amd.h; tuch_cp_search
+// for scan_fit.hip), its adjoint and the face groups it walks.
 //
 // Two launches:
 //   cp_group_bounds_kernel  per (body, group): the posed corners of the group's faces, gathered in group order
@@ -30,7 +30,7 @@
 // and a group is skipped for a lane only when lb(g) - 64 u far(g) is GREATER than the lane's bound (the best computed
 // d2 so far, at the start min_g far(g) (1 + 64 u)): no face of it can produce a key that is smaller or equal.
 //
-// The hinted start (tuch_closest_point_hinted).  hint [B,Q] names, per query, a face that is probably the answer -- in
+// The hinted start (tuch_closest_point with a hint).  hint [B,Q] names, per query, a face that is probably the answer -- in
 // a fitting loop the previous iteration's.  The hint is only a bound: a lane whose hint is a face index in [0, F)
 // (checked before it addresses anything) runs cp_eval on that face's posed corners and enters the result as an
 // ordinary key; its bound starts at that exact d2, its seed is the face's group (cp_face_group, the inverse of
@@ -43,7 +43,7 @@
 // call's bit for bit for every content of hint.  hint may alias the face output: a lane reads only its own entry, and
 // before it writes its face (a wholly padded block writes without reading).
 //
-// The oriented search (tuch_closest_point_oriented; cp_search_kernel<*, true>, cp_group_bounds_kernel<true>).  A query
+// The oriented search (tuch_closest_point with normals; cp_search_kernel<*, true>, cp_group_bounds_kernel<true>).  A query
 // is (p, n).  cp_admissible below is THE admissibility of a (normal, triangle) pair, stated in include/tuch_amd.h: with
 // m = (b - a) x (c - a), mm = |m|^2, nn = |n|^2, s = m . n, every operation rounded to float32 on its own,
 //     admissible  <=>  s > 0  and  s s >= c2 (mm nn),      c2 = c c,  c = (float)cos(max_angle).
@@ -623,34 +623,36 @@ __global__ __launch_bounds__(256) void cp_bwd_kernel(const float* __restrict__ v
 
 }  // namespace
 
-extern "C" size_t tuch_closest_point_workspace_bytes(const tuch_contact_model* m, int B, int Q)
+extern "C" size_t tuch_closest_point_workspace_bytes(const tuch_contact_model* m, int B, int Q, int oriented)
 {
     if (!m || B <= 0 || Q <= 0) return 0;
     tuch_ws_scope scope(m->opt.canary != 0);
-    return cp_layout(m, B, false).total;
+    return cp_layout(m, B, oriented != 0).total;
 }
 
-extern "C" size_t tuch_closest_point_oriented_workspace_bytes(const tuch_contact_model* m, int B, int Q)
+// what the searching entry points ask of max_angle_cos before anything else: with normals, a cosine in [0, 1)
+int tuch_cp_check_cos(const char* name, const float* normals, float max_angle_cos)
 {
-    if (!m || B <= 0 || Q <= 0) return 0;
-    tuch_ws_scope scope(m->opt.canary != 0);
-    return cp_layout(m, B, true).total;
+    TUCH_REQUIRE(!normals || (max_angle_cos >= 0.0f && max_angle_cos < 1.0f),
+                 "%s: max_angle_cos %g is not in [0, 1) (the cosine of an angle in (0, 90] degrees)", name, (double)max_angle_cos);
+    return TUCH_OK;
 }
 
 // every entry point that searches (scan_fit.hip's too): `name` is the one the errors speak of; hint == nullptr launches
 // the unhinted instantiation, shift == nullptr leaves the points as they are; normals != nullptr launches the oriented
-// forms with max_angle_cos (the workspace is then tuch_closest_point_oriented_workspace_bytes)
+// forms with max_angle_cos (the workspace then holds the cones); without normals max_angle_cos is not read
 int tuch_cp_search(const char* name, const tuch_contact_model* m, const float* verts, const float* points, const float* shift,
                    const float* normals, float max_angle_cos, const int32_t* counts, const int32_t* hint, int B, int Q,
                    float* d2, int32_t* face, float* bary, void* workspace, size_t workspace_bytes, void* stream)
 {
+    const bool oriented = normals != nullptr;
+    if (!oriented) max_angle_cos = 0.0f;
     TUCH_REQUIRE(m && verts && points && d2 && face && bary, "%s: null pointer", name);
     TUCH_REQUIRE(B >= 0 && B <= 65535 && Q >= 0, "%s: bad sizes B=%d Q=%d", name, B, Q);
-    const bool oriented = normals != nullptr;
     if (B == 0 || Q == 0) return TUCH_OK;
     TUCH_REQUIRE(m->cp_groups > 0 && m->cp_group_off && m->cp_face_list && m->cp_face_group, "%s: the model has no face groups",
                  name);
-    const size_t need = oriented ? tuch_closest_point_oriented_workspace_bytes(m, B, Q) : tuch_closest_point_workspace_bytes(m, B, Q);
+    const size_t need = tuch_closest_point_workspace_bytes(m, B, Q, oriented);
     if (!workspace || workspace_bytes < need) {
         tuch_set_error("%s: workspace %zu < %zu bytes", name, workspace_bytes, need);
         return TUCH_ERR_WORKSPACE;
@@ -677,33 +679,14 @@ int tuch_cp_search(const char* name, const tuch_contact_model* m, const float* v
     return tuch_check_launch(name);
 }
 
-extern "C" int tuch_closest_point(const tuch_contact_model* m, const float* verts, const float* points, const int32_t* counts,
-                                  int B, int Q, float* d2, int32_t* face, float* bary, void* workspace, size_t workspace_bytes,
-                                  void* stream)
+extern "C" int tuch_closest_point(const tuch_contact_model* m, const float* verts, const float* points, const float* normals,
+                                  float max_angle_cos, const int32_t* counts, const int32_t* hint, int B, int Q, float* d2,
+                                  int32_t* face, float* bary, void* workspace, size_t workspace_bytes, void* stream)
 {
-    return tuch_cp_search("tuch_closest_point", m, verts, points, nullptr, nullptr, 0.0f, counts, nullptr, B, Q, d2, face, bary,
-                          workspace, workspace_bytes, stream);
-}
-
-extern "C" int tuch_closest_point_hinted(const tuch_contact_model* m, const float* verts, const float* points,
-                                         const int32_t* counts, const int32_t* hint, int B, int Q, float* d2, int32_t* face,
-                                         float* bary, void* workspace, size_t workspace_bytes, void* stream)
-{
-    return tuch_cp_search("tuch_closest_point_hinted", m, verts, points, nullptr, nullptr, 0.0f, counts, hint, B, Q, d2, face, bary,
-                          workspace, workspace_bytes, stream);
-}
-
-extern "C" int tuch_closest_point_oriented(const tuch_contact_model* m, const float* verts, const float* points,
-                                           const float* normals, float max_angle_cos, const int32_t* counts, const int32_t* hint,
-                                           int B, int Q, float* d2, int32_t* face, float* bary, void* workspace,
-                                           size_t workspace_bytes, void* stream)
-{
-    TUCH_REQUIRE(max_angle_cos >= 0.0f && max_angle_cos < 1.0f,
-                 "tuch_closest_point_oriented: max_angle_cos %g is not in [0, 1) (the cosine of an angle in (0, 90] degrees)",
-                 (double)max_angle_cos);
-    TUCH_REQUIRE(normals, "tuch_closest_point_oriented: null pointer");
-    return tuch_cp_search("tuch_closest_point_oriented", m, verts, points, nullptr, normals, max_angle_cos, counts, hint, B, Q, d2,
-                          face, bary, workspace, workspace_bytes, stream);
+    const int rc = tuch_cp_check_cos("tuch_closest_point", normals, max_angle_cos);
+    if (rc != TUCH_OK) return rc;
+    return tuch_cp_search("tuch_closest_point", m, verts, points, nullptr, normals, max_angle_cos, counts, hint, B, Q, d2, face,
+                          bary, workspace, workspace_bytes, stream);
 }
 
 extern "C" int tuch_closest_point_bwd(const tuch_contact_model* m, const float* verts, const float* points, const int32_t* face,

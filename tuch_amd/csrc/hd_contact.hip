@@ -442,11 +442,10 @@ extern "C" void tuch_hd_model_destroy(tuch_hd_model* hm)
     delete hm;
 }
 
-// hd_idx / hd_w [N,3]: the three non-zeros of every row of the HD vertex regressor; hd_face [N]: the face each point
-// was sampled from.  The contact model must outlive the HD model.
-// K <= 8 non-zeros per row (hd_idx / hd_w [N,K]; rows with fewer: weight 0, any valid id).
-extern "C" int tuch_hd_model_create_k(tuch_hd_model** out, const tuch_contact_model* cm, int N, int K, const int32_t* hd_idx,
-                                      const float* hd_w, const int32_t* hd_face)
+// hd_idx / hd_w [N,K]: the K <= 8 non-zeros of every row of the HD vertex regressor (rows with fewer: weight 0, any valid
+// id); hd_face [N]: the face each point was sampled from.  The contact model must outlive the HD model.
+extern "C" int tuch_hd_model_create(tuch_hd_model** out, const tuch_contact_model* cm, int N, int K, const int32_t* hd_idx,
+                                    const float* hd_w, const int32_t* hd_face)
 {
     TUCH_REQUIRE(out && cm && hd_idx && hd_w && hd_face && N > 0, "tuch_hd_model_create: bad arguments");
     TUCH_REQUIRE(K >= 1 && K <= 8, "tuch_hd_model_create: %d non-zeros per row (1..8)", K);
@@ -536,12 +535,6 @@ extern "C" int tuch_hd_model_create_k(tuch_hd_model** out, const tuch_contact_mo
     *out = rc == TUCH_OK ? hm : nullptr;
     if (rc != TUCH_OK) tuch_hd_model_destroy(hm);
     return rc;
-}
-
-extern "C" int tuch_hd_model_create(tuch_hd_model** out, const tuch_contact_model* cm, int N, const int32_t* hd_idx,
-                                    const float* hd_w, const int32_t* hd_face)
-{
-    return tuch_hd_model_create_k(out, cm, N, 3, hd_idx, hd_w, hd_face);
 }
 
 extern "C" int tuch_hd_model_info(const tuch_hd_model* hm, int* N, int32_t* order_host)

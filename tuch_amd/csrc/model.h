@@ -115,9 +115,10 @@ extern "C" int tuch_winding_points(const tuch_contact_model* m, const float* ver
 
 // The closest-point search behind every entry point that needs it (closest_point.hip): queries points [B,Q,3] - shift[b]
 // (shift [B,3] or nullptr), hint [B,Q] or nullptr (may alias face); `name` is the entry point the errors speak of.
-// normals [B,Q,3] or nullptr: with them the oriented search under max_angle_cos, whose workspace is the oriented size.
-extern "C" size_t tuch_closest_point_workspace_bytes(const tuch_contact_model* m, int B, int Q);
-extern "C" size_t tuch_closest_point_oriented_workspace_bytes(const tuch_contact_model* m, int B, int Q);
+// normals [B,Q,3] or nullptr: with them the oriented search under max_angle_cos, which tuch_cp_check_cos has passed and
+// whose workspace is the oriented size.
+extern "C" size_t tuch_closest_point_workspace_bytes(const tuch_contact_model* m, int B, int Q, int oriented);
+int tuch_cp_check_cos(const char* name, const float* normals, float max_angle_cos);
 int tuch_cp_search(const char* name, const tuch_contact_model* m, const float* verts, const float* points, const float* shift,
                    const float* normals, float max_angle_cos, const int32_t* counts, const int32_t* hint, int B, int Q,
                    float* d2, int32_t* face, float* bary, void* workspace, size_t workspace_bytes, void* stream);

@@ -42,8 +42,7 @@
 //                       walk.  kOriented chooses the sink and nothing else.
 //   pc_nearest_kernel<kOriented>, pc_fit_kernel<kOriented>   the query for an entry of `queries` and for a vertex with
 //                       the term as its epilogue; the <false> instantiations do not read what only the oriented sink
-//                       needs, and each entry point pair has one launcher (pc_nearest, pc_fit_terms: normals == nullptr
-//                       is the plain form).
+//                       needs; each has one entry point (normals == nullptr is the plain form).
 // Keys are made and read by pc_key / pc_won / pc_key_d2 / pc_key_index alone; pc_entries and pc_entry say which
 // entries of a body are queries and what the query of an entry is.
 //
@@ -111,7 +110,7 @@
 // when tau is given and the cloud is not empty, else 0, with a zero gradient row; a body with an empty cloud or without
 // weight has loss 0.
 //
-// The oriented query (tuch_point_cloud_nearest_oriented / _fit_terms_oriented / _build_cones) is the query above with
+// The oriented query (tuch_point_cloud_nearest / _fit_terms with normals, _build_cones) is the query above with
 // another sink, PcOriented: the same key, pc_d2, walk, margin, hint and outputs, over the ADMISSIBLE valid points only.
 // Points carry normals n (caller's order, never filed), a query a normal u: an entry of query_normals, or, in the
 // term, what the lane that owns vertex v forms itself from the UNTRANSLATED verts by vn_vertex_normal (face_normal.h;
@@ -627,7 +626,7 @@ static __device__ __forceinline__ unsigned long long pc_query(const PcTables& w,
     return pc_walk(w, b, Q, qx, qy, qz, sink).best;
 }
 
-// tuch_point_cloud_nearest (kOriented = false: orient and query_normals are not read) and _nearest_oriented
+// tuch_point_cloud_nearest; kOriented: with normals (kOriented = false: orient and query_normals are not read)
 template <bool kOriented>
 __global__ __launch_bounds__(kBlock) void pc_nearest_kernel(PcTables w, PcOrient orient, const float* __restrict__ points,
                                                            const int32_t* __restrict__ counts,
@@ -991,7 +990,7 @@ struct PcMesh {
     int F;
 };
 
-// The term (tuch_point_cloud_fit_terms; kOriented: _fit_terms_oriented).  kOriented: the query is the oriented one, with
+// The term (tuch_point_cloud_fit_terms; kOriented: with normals).  kOriented: the query is the oriented one, with
 // the raw vertex normal of the UNTRANSLATED verts (tuch_vertex_normals' row, normalize = 0); nothing else differs, and
 // the plain form reads neither orient nor mesh.  (The arguments stay a list: as one struct by value they are all loaded
 // at entry, and this kernel, which is at its SGPR limit, then spills them to VGPR lanes and reloads them inside the
@@ -1107,32 +1106,54 @@ PcOrient pc_orient(const float* normals, float max_angle_cos, const void* cones,
     return o;
 }
 
-// both nearest entry points: `name` is the one the errors speak of; normals == nullptr is tuch_point_cloud_nearest
-int pc_nearest(const char* name, const void* workspace, size_t workspace_bytes, const float* points, const int32_t* counts,
-               const float* weights, const float* normals, const float* queries, const float* query_normals, const float* shift,
-               const int32_t* query_counts, const int32_t* hint, float max_distance, float max_angle_cos, const void* cones,
-               size_t cones_bytes, int B, int Q, int N, float* d2, int32_t* index, void* stream)
+}  // namespace
+
+// the query and the term: normals == nullptr is the plain form of each
+extern "C" int tuch_point_cloud_nearest(const void* workspace, size_t workspace_bytes, const float* points,
+                                        const int32_t* counts, const float* weights, const float* normals,
+                                        const float* queries, const float* query_normals, const float* shift,
+                                        const int32_t* query_counts, const int32_t* hint, float max_distance,
+                                        float max_angle_cos, const void* cones, size_t cones_bytes, int B, int Q, int N,
+                                        float* d2, int32_t* index, void* stream)
 {
+    const char* name = "tuch_point_cloud_nearest";
+    TUCH_REQUIRE(!normals == !query_normals, "%s: normals and query_normals go together (%p, %p)", name, (const void*)normals,
+                 (const void*)query_normals);
+    const bool oriented = normals != nullptr;
+    TUCH_REQUIRE(!oriented || (max_angle_cos >= 0.0f && max_angle_cos < 1.0f), "%s: max_angle_cos %g (in [0, 1))", name,
+                 (double)max_angle_cos);
     TUCH_REQUIRE(workspace && points && queries && d2 && index, "%s: null pointer", name);
     TUCH_REQUIRE(pc_sizes_ok(B, Q, N), "%s: bad sizes B=%d Q=%d N=%d", name, B, Q, N);
     tuch_ws_scope scope(g_pc_canary != 0);
     const int rc = pc_workspace_check(name, workspace_bytes, B, Q);
     if (rc != TUCH_OK) return rc;
-    hipLaunchKernelGGL(normals ? pc_nearest_kernel<true> : pc_nearest_kernel<false>, dim3(ceil_div(N, kBlock), B), dim3(kBlock), 0,
-                       (hipStream_t)stream, pc_tables((void*)workspace, workspace_bytes, B, Q),
-                       pc_orient(normals, max_angle_cos, cones, cones_bytes), points, counts, weights, queries, query_normals,
-                       shift, query_counts, hint, pc_limit(max_distance), Q, N, d2, index);
+    // (not oriented: the cosine and the cones are not read)
+    const PcOrient orient = oriented ? pc_orient(normals, max_angle_cos, cones, cones_bytes) : pc_orient(nullptr, 0.0f, nullptr, 0);
+    hipLaunchKernelGGL(oriented ? pc_nearest_kernel<true> : pc_nearest_kernel<false>, dim3(ceil_div(N, kBlock), B), dim3(kBlock), 0,
+                       (hipStream_t)stream, pc_tables((void*)workspace, workspace_bytes, B, Q), orient, points, counts, weights,
+                       queries, query_normals, shift, query_counts, hint, pc_limit(max_distance), Q, N, d2, index);
     return tuch_check_launch(name);
 }
 
-// both term entry points: normals == nullptr is tuch_point_cloud_fit_terms (no mesh, no cones)
-int pc_fit_terms(const char* name, const void* workspace, size_t workspace_bytes, const float* points, const int32_t* counts,
-                 const float* weights, const float* normals, float max_angle_cos, const PcMesh& mesh, const void* cones,
-                 size_t cones_bytes, const float* verts, const float* transl, const int32_t* hint, float max_distance, int B, int Q,
-                 int V, const float* vertex_weights, int vertex_weight_layout, int rho, float sigma, float scale, float* d2,
-                 int32_t* index, int* ticket, float* per_body, float* total, float* grad_verts, float* grad_transl, void* scratch,
-                 size_t scratch_bytes, void* stream)
+extern "C" int tuch_point_cloud_fit_terms(const void* workspace, size_t workspace_bytes, const float* points,
+                                          const int32_t* counts, const float* weights, const float* normals,
+                                          float max_angle_cos, const int32_t* faces, const int32_t* vf_off,
+                                          const int32_t* vf_ids, int F, const void* cones, size_t cones_bytes,
+                                          const float* verts, const float* transl, const int32_t* hint, float max_distance,
+                                          int B, int Q, int V, const float* vertex_weights, int vertex_weight_layout, int rho,
+                                          float sigma, float scale, float* d2, int32_t* index, int* ticket, float* per_body,
+                                          float* total, float* grad_verts, float* grad_transl, void* scratch,
+                                          size_t scratch_bytes, void* stream)
 {
+    const char* name = "tuch_point_cloud_fit_terms";
+    const bool oriented = normals != nullptr;
+    if (oriented) {
+        TUCH_REQUIRE(faces && vf_off && vf_ids, "%s: null pointer", name);
+        TUCH_REQUIRE(pc_sizes_ok(B, Q, V) && F > 0 && (long long)F * 3 < (1ll << 31), "%s: bad sizes B=%d Q=%d V=%d F=%d", name, B,
+                     Q, V, F);
+        TUCH_REQUIRE(max_angle_cos >= 0.0f && max_angle_cos < 1.0f, "%s: max_angle_cos %g (in [0, 1))", name,
+                     (double)max_angle_cos);
+    }
     TUCH_REQUIRE(workspace && points && verts && transl && d2 && index && ticket && per_body && total && grad_verts &&
                      grad_transl && scratch,
                  "%s: null pointer", name);
@@ -1149,15 +1170,15 @@ int pc_fit_terms(const char* name, const void* workspace, size_t workspace_bytes
     hipStream_t s = (hipStream_t)stream;
     const PcTables w = pc_tables((void*)workspace, workspace_bytes, B, Q);
     scope.arm(scratch, (int32_t*)w.head, s);
-    hipLaunchKernelGGL(normals ? pc_fit_kernel<true> : pc_fit_kernel<false>, dim3(ceil_div(V, kBlock), B), dim3(kBlock), 0, s, w,
-                       pc_orient(normals, max_angle_cos, cones, cones_bytes), mesh, points, counts, weights, verts, transl, hint,
-                       pc_limit(max_distance), max_distance > 0.0f ? 1 : 0, B, Q, V, vertex_weights, vertex_weight_layout, rho,
-                       sigma * sigma, scale, d2, index, (float*)((char*)scratch + sl.partial), ticket, per_body, total,
-                       grad_verts, grad_transl);
+    // (not oriented: no mesh, no cones, and the cosine is not read)
+    const PcOrient orient = oriented ? pc_orient(normals, max_angle_cos, cones, cones_bytes) : pc_orient(nullptr, 0.0f, nullptr, 0);
+    const PcMesh mesh = oriented ? PcMesh{faces, vf_off, vf_ids, F} : PcMesh{};
+    hipLaunchKernelGGL(oriented ? pc_fit_kernel<true> : pc_fit_kernel<false>, dim3(ceil_div(V, kBlock), B), dim3(kBlock), 0, s, w,
+                       orient, mesh, points, counts, weights, verts, transl, hint, pc_limit(max_distance),
+                       max_distance > 0.0f ? 1 : 0, B, Q, V, vertex_weights, vertex_weight_layout, rho, sigma * sigma, scale, d2,
+                       index, (float*)((char*)scratch + sl.partial), ticket, per_body, total, grad_verts, grad_transl);
     return tuch_check_launch(name);
 }
-
-}  // namespace
 
 extern "C" int tuch_point_cloud_set_canary(int on)
 {
@@ -1210,15 +1231,6 @@ extern "C" int tuch_point_cloud_build(const float* points, const int32_t* counts
     hipLaunchKernelGGL(pc_file_kernel<true>, grid, dim3(kBlock), 0, s, points, counts, weights, Q, resolution,
                        (const uint32_t*)head, tables, sorted);
     return tuch_check_launch("tuch_point_cloud_build");
-}
-
-extern "C" int tuch_point_cloud_nearest(const void* workspace, size_t workspace_bytes, const float* points,
-                                        const int32_t* counts, const float* weights, const float* queries,
-                                        const float* shift, const int32_t* query_counts, const int32_t* hint,
-                                        float max_distance, int B, int Q, int N, float* d2, int32_t* index, void* stream)
-{
-    return pc_nearest("tuch_point_cloud_nearest", workspace, workspace_bytes, points, counts, weights, nullptr, queries, nullptr,
-                      shift, query_counts, hint, max_distance, 0.0f, nullptr, 0, B, Q, N, d2, index, stream);
 }
 
 namespace {
@@ -1277,20 +1289,7 @@ extern "C" int tuch_point_cloud_normals(const void* workspace, size_t workspace_
     return tuch_check_launch("tuch_point_cloud_normals");
 }
 
-extern "C" int tuch_point_cloud_fit_terms(const void* workspace, size_t workspace_bytes, const float* points,
-                                          const int32_t* counts, const float* weights, const float* verts,
-                                          const float* transl, const int32_t* hint, float max_distance, int B, int Q, int V,
-                                          const float* vertex_weights, int vertex_weight_layout, int rho, float sigma,
-                                          float scale, float* d2, int32_t* index, int* ticket, float* per_body, float* total,
-                                          float* grad_verts, float* grad_transl, void* scratch, size_t scratch_bytes,
-                                          void* stream)
-{
-    return pc_fit_terms("tuch_point_cloud_fit_terms", workspace, workspace_bytes, points, counts, weights, nullptr, 0.0f, PcMesh{},
-                        nullptr, 0, verts, transl, hint, max_distance, B, Q, V, vertex_weights, vertex_weight_layout, rho, sigma,
-                        scale, d2, index, ticket, per_body, total, grad_verts, grad_transl, scratch, scratch_bytes, stream);
-}
-
-// ------------------------------------------------------------------------------------------ the oriented entry points
+// -------------------------------------------------------------------------------------------------------- the cones
 extern "C" size_t tuch_point_cloud_cones_bytes(int B, int resolution)
 {
     if (B <= 0 || resolution <= 0 || resolution > kMaxRes) return 0;
@@ -1314,43 +1313,6 @@ extern "C" int tuch_point_cloud_build_cones(const void* workspace, size_t worksp
     hipLaunchKernelGGL(pc_cones_kernel, dim3(cres * cres * cres, B), dim3(64), 0, (hipStream_t)stream,
                        pc_tables((void*)workspace, workspace_bytes, B, Q), normals, Q, resolution, (uint32_t*)cones);
     return tuch_check_launch("tuch_point_cloud_build_cones");
-}
-
-extern "C" int tuch_point_cloud_nearest_oriented(const void* workspace, size_t workspace_bytes, const float* points,
-                                                 const int32_t* counts, const float* weights, const float* normals,
-                                                 const float* queries, const float* query_normals, const float* shift,
-                                                 const int32_t* query_counts, const int32_t* hint, float max_distance,
-                                                 float max_angle_cos, const void* cones, size_t cones_bytes, int B, int Q,
-                                                 int N, float* d2, int32_t* index, void* stream)
-{
-    TUCH_REQUIRE(normals && query_normals, "tuch_point_cloud_nearest_oriented: null pointer");
-    TUCH_REQUIRE(max_angle_cos >= 0.0f && max_angle_cos < 1.0f, "tuch_point_cloud_nearest_oriented: max_angle_cos %g (in [0, 1))",
-                 (double)max_angle_cos);
-    return pc_nearest("tuch_point_cloud_nearest_oriented", workspace, workspace_bytes, points, counts, weights, normals, queries,
-                      query_normals, shift, query_counts, hint, max_distance, max_angle_cos, cones, cones_bytes, B, Q, N, d2,
-                      index, stream);
-}
-
-extern "C" int tuch_point_cloud_fit_terms_oriented(const void* workspace, size_t workspace_bytes, const float* points,
-                                                   const int32_t* counts, const float* weights, const float* normals,
-                                                   float max_angle_cos, const int32_t* faces, const int32_t* vf_off,
-                                                   const int32_t* vf_ids, int F, const void* cones, size_t cones_bytes,
-                                                   const float* verts, const float* transl, const int32_t* hint,
-                                                   float max_distance, int B, int Q, int V, const float* vertex_weights,
-                                                   int vertex_weight_layout, int rho, float sigma, float scale, float* d2,
-                                                   int32_t* index, int* ticket, float* per_body, float* total,
-                                                   float* grad_verts, float* grad_transl, void* scratch, size_t scratch_bytes,
-                                                   void* stream)
-{
-    TUCH_REQUIRE(normals && faces && vf_off && vf_ids, "tuch_point_cloud_fit_terms_oriented: null pointer");
-    TUCH_REQUIRE(pc_sizes_ok(B, Q, V) && F > 0 && (long long)F * 3 < (1ll << 31),
-                 "tuch_point_cloud_fit_terms_oriented: bad sizes B=%d Q=%d V=%d F=%d", B, Q, V, F);
-    TUCH_REQUIRE(max_angle_cos >= 0.0f && max_angle_cos < 1.0f,
-                 "tuch_point_cloud_fit_terms_oriented: max_angle_cos %g (in [0, 1))", (double)max_angle_cos);
-    return pc_fit_terms("tuch_point_cloud_fit_terms_oriented", workspace, workspace_bytes, points, counts, weights, normals,
-                        max_angle_cos, PcMesh{faces, vf_off, vf_ids, F}, cones, cones_bytes, verts, transl, hint, max_distance, B,
-                        Q, V, vertex_weights, vertex_weight_layout, rho, sigma, scale, d2, index, ticket, per_body, total,
-                        grad_verts, grad_transl, scratch, scratch_bytes, stream);
 }
 
 extern "C" int tuch_point_cloud_grid(const void* workspace, int B, int resolution, float* origin_host, float* cell_host,

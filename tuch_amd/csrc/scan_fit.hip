@@ -35,8 +35,7 @@ ScanLayout scan_layout(const tuch_contact_model* m, int B, int Q, bool oriented)
     ScanLayout l;
     size_t o = 0;
     // (the search guards its own regions: its layout is recorded by its own scope at this offset)
-    l.search = tuch_ws_take(o, oriented ? tuch_closest_point_oriented_workspace_bytes(m, B, Q)
-                                        : tuch_closest_point_workspace_bytes(m, B, Q), false);
+    l.search = tuch_ws_take(o, tuch_closest_point_workspace_bytes(m, B, Q, oriented), false);
     l.fixed = tuch_ws_take(o, (size_t)B * m->V * 3 * sizeof(long long));
     l.partial = tuch_ws_take(o, (size_t)B * ceil_div(Q, kBlock) * kFitPart * sizeof(float));
     l.total = o;
@@ -100,27 +99,23 @@ __global__ __launch_bounds__(kBlock) void scan_term_kernel(
 
 }  // namespace
 
-extern "C" size_t tuch_scan_fit_workspace_bytes(const tuch_contact_model* m, int B, int Q)
+extern "C" size_t tuch_scan_fit_workspace_bytes(const tuch_contact_model* m, int B, int Q, int oriented)
 {
     if (!m || B <= 0 || Q <= 0) return 0;
     tuch_ws_scope scope(m->opt.canary != 0);
-    return scan_layout(m, B, Q, false).total;
+    return scan_layout(m, B, Q, oriented != 0).total;
 }
 
-extern "C" size_t tuch_scan_fit_oriented_workspace_bytes(const tuch_contact_model* m, int B, int Q)
+extern "C" int tuch_scan_fit_terms(const tuch_contact_model* m, const float* verts, const float* transl, const float* points,
+                                   const float* normals, float max_angle_cos, const int32_t* counts, const float* weights,
+                                   const int32_t* hint, int B, int Q, int rho, float sigma, float* d2, int32_t* face,
+                                   float* bary, int* ticket, float* per_body, float* total, float* grad_verts,
+                                   float* grad_transl, float* grad_points, void* workspace, size_t workspace_bytes,
+                                   void* stream)
 {
-    if (!m || B <= 0 || Q <= 0) return 0;
-    tuch_ws_scope scope(m->opt.canary != 0);
-    return scan_layout(m, B, Q, true).total;
-}
-
-// both entry points: normals == nullptr is tuch_scan_fit_terms
-static int scan_fit_terms(const char* name, const tuch_contact_model* m, const float* verts, const float* transl, const float* points,
-                          const float* normals, float max_angle_cos, const int32_t* counts, const float* weights,
-                          const int32_t* hint, int B, int Q, int rho, float sigma, float* d2, int32_t* face, float* bary,
-                          int* ticket, float* per_body, float* total, float* grad_verts, float* grad_transl, float* grad_points,
-                          void* workspace, size_t workspace_bytes, void* stream)
-{
+    const char* name = "tuch_scan_fit_terms";
+    int rc = tuch_cp_check_cos(name, normals, max_angle_cos);
+    if (rc != TUCH_OK) return rc;
     TUCH_REQUIRE(m && verts && transl && points && d2 && face && bary && ticket && per_body && total && grad_verts && grad_transl,
                  "%s: null pointer", name);
     TUCH_REQUIRE(B > 0 && B <= 65535 && Q > 0 && (long long)B * ceil_div(Q, kBlock) < (1ll << 30), "%s: bad sizes B=%d Q=%d", name,
@@ -128,7 +123,7 @@ static int scan_fit_terms(const char* name, const tuch_contact_model* m, const f
     TUCH_REQUIRE(rho == TUCH_SCAN_RHO_SQUARED || rho == TUCH_SCAN_RHO_DISTANCE || (rho == TUCH_SCAN_RHO_GMOF && sigma > 0.0f),
                  "%s: rho %d (0 squared, 1 distance, 2 gmof with sigma > 0; sigma = %g)", name, rho, (double)sigma);
     const bool oriented = normals != nullptr;
-    const size_t need = oriented ? tuch_scan_fit_oriented_workspace_bytes(m, B, Q) : tuch_scan_fit_workspace_bytes(m, B, Q);
+    const size_t need = tuch_scan_fit_workspace_bytes(m, B, Q, oriented);
     if (!workspace || workspace_bytes < need) {
         tuch_set_error("%s: workspace %zu < %zu bytes", name, workspace_bytes, need);
         return TUCH_ERR_WORKSPACE;
@@ -137,10 +132,8 @@ static int scan_fit_terms(const char* name, const tuch_contact_model* m, const f
     tuch_ws_scope scope(m->opt.canary != 0);
     const ScanLayout l = scope.record(0, [&] { return scan_layout(m, B, Q, oriented); });
     scope.arm(workspace, m->canary_hits, s);
-    const int rc = tuch_cp_search(name, m, verts, points, transl, normals, max_angle_cos, counts, hint, B, Q, d2, face, bary,
-                                  (char*)workspace + l.search,
-                                  oriented ? tuch_closest_point_oriented_workspace_bytes(m, B, Q)
-                                           : tuch_closest_point_workspace_bytes(m, B, Q), stream);
+    rc = tuch_cp_search(name, m, verts, points, transl, normals, max_angle_cos, counts, hint, B, Q, d2, face, bary,
+                        (char*)workspace + l.search, tuch_closest_point_workspace_bytes(m, B, Q, oriented), stream);
     if (rc != TUCH_OK) return rc;
     long long* fixed = (long long*)((char*)workspace + l.fixed);
     float* partial = (float*)((char*)workspace + l.partial);
@@ -161,31 +154,4 @@ static int scan_fit_terms(const char* name, const tuch_contact_model* m, const f
                            grad_transl);
     }
     return tuch_check_launch(name);
-}
-
-extern "C" int tuch_scan_fit_terms(const tuch_contact_model* m, const float* verts, const float* transl, const float* points,
-                                   const int32_t* counts, const float* weights, const int32_t* hint, int B, int Q, int rho,
-                                   float sigma, float* d2, int32_t* face, float* bary, int* ticket, float* per_body,
-                                   float* total, float* grad_verts, float* grad_transl, float* grad_points, void* workspace,
-                                   size_t workspace_bytes, void* stream)
-{
-    return scan_fit_terms("tuch_scan_fit_terms", m, verts, transl, points, nullptr, 0.0f, counts, weights, hint, B, Q, rho, sigma,
-                          d2, face, bary, ticket, per_body, total, grad_verts, grad_transl, grad_points, workspace,
-                          workspace_bytes, stream);
-}
-
-extern "C" int tuch_scan_fit_terms_oriented(const tuch_contact_model* m, const float* verts, const float* transl,
-                                            const float* points, const float* normals, float max_angle_cos,
-                                            const int32_t* counts, const float* weights, const int32_t* hint, int B, int Q,
-                                            int rho, float sigma, float* d2, int32_t* face, float* bary, int* ticket,
-                                            float* per_body, float* total, float* grad_verts, float* grad_transl,
-                                            float* grad_points, void* workspace, size_t workspace_bytes, void* stream)
-{
-    TUCH_REQUIRE(max_angle_cos >= 0.0f && max_angle_cos < 1.0f,
-                 "tuch_scan_fit_terms_oriented: max_angle_cos %g is not in [0, 1) (the cosine of an angle in (0, 90] degrees)",
-                 (double)max_angle_cos);
-    TUCH_REQUIRE(normals, "tuch_scan_fit_terms_oriented: null pointer");
-    return scan_fit_terms("tuch_scan_fit_terms_oriented", m, verts, transl, points, normals, max_angle_cos, counts, weights, hint,
-                          B, Q, rho, sigma, d2, face, bary, ticket, per_body, total, grad_verts, grad_transl, grad_points,
-                          workspace, workspace_bytes, stream);
 }

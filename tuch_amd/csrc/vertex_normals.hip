@@ -2,7 +2,7 @@
 // m = (b - a) x (c - a) of the faces around it -- the area-weighted normal -- in the order of the vertex -> faces table
 // (ops.vertex_face_table: ascending face ids), optionally normalised.
 //
-// The rule is one fixed float32 sequence (face_normal.h: cp_face_normal, the m of tuch_closest_point_oriented's
+// The rule is one fixed float32 sequence (face_normal.h: cp_face_normal, the m of tuch_closest_point's
 // admissibility rule, and vn_vertex_normal, the left-to-right sum from 0), nothing fused.  normalize != 0 divides by
 // sqrt(uu), uu = (ux ux + uy uy) + uz uz, and writes a zero row where uu is 0 or not finite (a vertex without faces,
 // faces without area, a non-finite corner).  One lane owns one row: it reads the corners of its vertex's faces and

@@ -156,7 +156,7 @@ class ScanFitter(BodyFitter):
 
     ``use_hint``: the session holds a [B,Q] int32 tensor that is both the search's hint and where it writes its faces, so
     every iteration starts each point from the face it found last time; the tensor is reset to -1 at the start of every
-    call.  The hint changes no bit of any result (tuch_closest_point_hinted).
+    call.  The hint changes no bit of any result (tuch_closest_point with a hint).
 
     ``model_to_scan`` lambda > 0 makes the fit two-sided: the iteration's objective is the scan -> model term plus
     lambda times the model -> scan term (ops.cloud_fit: every vertex's distance to the nearest real point of the scan
@@ -282,7 +282,7 @@ class ScanFitter(BodyFitter):
 
         def iteration():
             verts = _posed(smpl, t)
-            # (the hint tensor receives the new faces: the aliasing tuch_closest_point_hinted allows)
+            # (the hint tensor receives the new faces: the aliasing tuch_closest_point allows)
             total, _, _ = ops.scan_fit(model, verts, t['transl'], t['points'], t['counts'], t['weights'], hint,
                                        self.rho, self.sigma, face_out=hint, normals=t['normals'], max_angle=angle)
             if cloud is not None:

@@ -1454,8 +1454,8 @@ class ContactModel:
         hint [B,Q] int32: per query a face that is probably the answer (a fitting loop passes the previous iteration's
         ``face``).  It changes no bit of the result, whatever it holds (wrong faces and indices out of range included);
         a valid one lets the query start from that face's exact distance instead of from a walk over every box of the
-        body (tuch_closest_point_hinted).
-        normals [B,Q,3] with max_angle in degrees, in (0, 90]: the normal-compatible search (tuch_closest_point_oriented).
+        body (tuch_closest_point with a hint).
+        normals [B,Q,3] with max_angle in degrees, in (0, 90]: the normal-compatible search (tuch_closest_point with normals).
         A face is a candidate for a query only if its normal (b - a) x (c - a) is within max_angle of the query's normal
         (any length, in the frame of verts) -- decided by one fixed float32 sequence (include/tuch_amd.h), so the same
         bits hold alone or in a batch, for any order, any hint and any grouping of the faces.  A query with a zero or
@@ -1469,9 +1469,8 @@ class ContactModel:
         if counts is not None:
             counts = counts.to(torch.int32).contiguous()
         hint = _hint_of(hint, points, 'closest_point')
-        if cos is not None:
-            return ClosestPoint(*_ClosestPoint.apply(verts, points, self, counts, hint, _f32(normals.detach()), cos))
-        return ClosestPoint(*_ClosestPoint.apply(verts, points, self, counts, hint))
+        normals = None if cos is None else _f32(normals.detach())
+        return ClosestPoint(*_ClosestPoint.apply(verts, points, self, counts, hint, normals, cos))
 
     def face_groups(self):
         """The face groups the closest-point search walks, as host arrays: (group_off [G+1], face_list [F], face_group
@@ -1574,29 +1573,23 @@ def _max_angle_cos(normals, max_angle, points, what):
 
 
 class _ClosestPoint(torch.autograd.Function):
-    """ContactModel.closest_point: tuch_closest_point_hinted forward (hint None: tuch_closest_point's search),
-    tuch_closest_point_bwd (the envelope form) backward.  With normals and the cosine: tuch_closest_point_oriented."""
+    """ContactModel.closest_point: tuch_closest_point forward (hint, and normals with their cosine, or None),
+    tuch_closest_point_bwd (the envelope form) backward."""
 
     @staticmethod
-    def forward(ctx, verts, points, model: ContactModel, counts, hint, normals=None, cos=None):
+    def forward(ctx, verts, points, model: ContactModel, counts, hint, normals, cos):
         v, pts = _f32(verts), _f32(points)
         b, q, _ = pts.shape
         L = _C.lib()
         d2 = torch.empty(b, q, dtype=torch.float32, device=pts.device)
         face = torch.empty(b, q, dtype=torch.int32, device=pts.device)
         bary = torch.empty(b, q, 3, dtype=torch.float32, device=pts.device)
-        if normals is not None:
-            nbytes = L.tuch_closest_point_oriented_workspace_bytes(model._handle, b, q)
-        else:
-            nbytes = L.tuch_closest_point_workspace_bytes(model._handle, b, q)
+        nbytes = L.tuch_closest_point_workspace_bytes(model._handle, b, q, normals is not None)
         ws = _workspace(nbytes, pts.device)
-        if b and q and normals is not None:
-            _C.check(L.tuch_closest_point_oriented(model._handle, _C.ptr(v), _C.ptr(pts), _C.ptr(normals), cos, _C.ptr(counts),
-                                                   _C.ptr(hint), b, q, _C.ptr(d2), _C.ptr(face), _C.ptr(bary), _C.ptr(ws),
-                                                   nbytes, _C.stream()))
-        elif b and q:
-            _C.check(L.tuch_closest_point_hinted(model._handle, _C.ptr(v), _C.ptr(pts), _C.ptr(counts), _C.ptr(hint), b, q,
-                                                 _C.ptr(d2), _C.ptr(face), _C.ptr(bary), _C.ptr(ws), nbytes, _C.stream()))
+        if b and q:
+            _C.check(L.tuch_closest_point(model._handle, _C.ptr(v), _C.ptr(pts), _C.ptr(normals), cos or 0.0, _C.ptr(counts),
+                                          _C.ptr(hint), b, q, _C.ptr(d2), _C.ptr(face), _C.ptr(bary), _C.ptr(ws), nbytes,
+                                          _C.stream()))
         ctx.save_for_backward(v, pts, face, bary)
         ctx.model = model
         ctx.mark_non_differentiable(face, bary)
@@ -1607,9 +1600,9 @@ class _ClosestPoint(torch.autograd.Function):
         v, pts, face, bary = ctx.saved_tensors
         b, q, _ = pts.shape
         want_v, want_p = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        extra = (None,) * (len(ctx.needs_input_grad) - 2)
+        rest = (None,) * 5
         if b == 0 or q == 0 or not (want_v or want_p):
-            return ((torch.zeros_like(v) if want_v else None), (torch.zeros_like(pts) if want_p else None)) + extra
+            return ((torch.zeros_like(v) if want_v else None), (torch.zeros_like(pts) if want_p else None)) + rest
         g = grad_d2.to(torch.float32).contiguous()
         gp = torch.empty_like(pts) if want_p else None
         gv = fixed = None
@@ -1620,7 +1613,7 @@ class _ClosestPoint(torch.autograd.Function):
             gv = torch.zeros_like(v)
         _C.check(_C.lib().tuch_closest_point_bwd(ctx.model._handle, _C.ptr(v), _C.ptr(pts), _C.ptr(face), _C.ptr(bary),
                                                  _C.ptr(g), b, q, _C.ptr(gp), _C.ptr(fixed), _C.ptr(gv), _C.stream()))
-        return (gv, gp) + extra
+        return (gv, gp) + rest
 
 
 SCAN_RHO = {'squared': 0, 'distance': 1, 'gmof': 2}
@@ -1677,8 +1670,7 @@ class _ScanFit(torch.autograd.Function):
     unless the upstream gradient is the cached unit seed of ops.backward_scalar)."""
 
     @staticmethod
-    def forward(ctx, verts, transl, points, model: ContactModel, counts, weights, hint, rho, sigma, face, normals=None,
-                cos=None):
+    def forward(ctx, verts, transl, points, model: ContactModel, counts, weights, hint, rho, sigma, face, normals, cos):
         v, tr, pts = _f32(verts), _f32(transl), _f32(points)
         b, q, _ = pts.shape
         dev = pts.device
@@ -1690,19 +1682,12 @@ class _ScanFit(torch.autograd.Function):
         gv = torch.empty_like(v)
         gt = torch.empty(b, 3, dtype=torch.float32, device=dev)
         gp = torch.empty_like(pts) if ctx.needs_input_grad[2] else None
-        # the oriented entry point takes (normals, cos) behind the points and is otherwise the plain one
-        oriented = normals is not None
-        sizer, entry = ((L.tuch_scan_fit_oriented_workspace_bytes, L.tuch_scan_fit_terms_oriented) if oriented else
-                        (L.tuch_scan_fit_workspace_bytes, L.tuch_scan_fit_terms))
-        nbytes = sizer(model._handle, b, q)
+        nbytes = L.tuch_scan_fit_workspace_bytes(model._handle, b, q, normals is not None)
         ws = _workspace(nbytes, dev)
-        args = [model._handle, _C.ptr(v), _C.ptr(tr), _C.ptr(pts), _C.ptr(counts), _C.ptr(weights), _C.ptr(hint), b, q, rho,
-                sigma, _C.ptr(d2), _C.ptr(face), _C.ptr(bary), _C.ptr(_ticket(dev)), _C.ptr(per_body), _C.ptr(out), _C.ptr(gv),
-                _C.ptr(gt), _C.ptr(gp), _C.ptr(ws), nbytes, _C.stream()]
-        if oriented:
-            args[4:4] = [_C.ptr(normals), cos]
-        _C.check(entry(*args))
-        ctx.num_inputs = 10 if normals is None else 12
+        _C.check(L.tuch_scan_fit_terms(
+            model._handle, _C.ptr(v), _C.ptr(tr), _C.ptr(pts), _C.ptr(normals), cos or 0.0, _C.ptr(counts), _C.ptr(weights),
+            _C.ptr(hint), b, q, rho, sigma, _C.ptr(d2), _C.ptr(face), _C.ptr(bary), _C.ptr(_ticket(dev)), _C.ptr(per_body),
+            _C.ptr(out), _C.ptr(gv), _C.ptr(gt), _C.ptr(gp), _C.ptr(ws), nbytes, _C.stream()))
         ctx.save_for_backward(gv, gt, gp)
         ctx.in_dtypes = (verts.dtype, transl.dtype, points.dtype)
         ctx.mark_non_differentiable(per_body, d2, bary)
@@ -1712,7 +1697,7 @@ class _ScanFit(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, g, *_others):
-        return _hand_over(ctx, g, ctx.num_inputs)
+        return _hand_over(ctx, g, 12)
 
 
 def scan_fit(model: ContactModel, verts, transl, points, counts=None, weights=None, hint=None, rho='distance', sigma=None,
@@ -1729,7 +1714,7 @@ def scan_fit(model: ContactModel, verts, transl, points, counts=None, weights=No
     hint [B,Q] int32 as in ``closest_point``; face_out: a contiguous int32 [B,Q] tensor to receive the faces -- it may be
     the hint tensor itself (a loop's memory of its last answer).
     normals [B,Q,3] with max_angle in degrees, in (0, 90], as in ``closest_point``: the search is the normal-compatible
-    one (tuch_scan_fit_terms_oriented); normals are not translated and get no gradient.  A real point without an
+    one (tuch_scan_fit_terms with normals); normals are not translated and get no gradient.  A real point without an
     admissible face (face = -1) adds 0 to the loss and to every gradient and keeps its weight in the normaliser.  Both or
     neither must be given; with neither the call is the plain one.  There is no host fallback."""
     rho, sigma = _rho_of('scan_fit', rho, sigma)
@@ -1752,8 +1737,8 @@ def scan_fit(model: ContactModel, verts, transl, points, counts=None, weights=No
     weights = None if weights is None else _f32(weights.detach())
     hint = _hint_of(hint, points, 'scan_fit')
     face = face_out if face_out is not None else torch.empty(b, q, dtype=torch.int32, device=points.device)
-    extra = () if cos is None else (_f32(normals.detach()), cos)
-    total, per_body, d2, bary = _ScanFit.apply(verts, transl, points, model, counts, weights, hint, rho, sigma, face, *extra)
+    normals = None if cos is None else _f32(normals.detach())
+    total, per_body, d2, bary = _ScanFit.apply(verts, transl, points, model, counts, weights, hint, rho, sigma, face, normals, cos)
     return total, per_body, ClosestPoint(d2, face, bary)
 
 
@@ -1801,22 +1786,17 @@ class _CloudNearest(torch.autograd.Function):
     use cloud_fit, whose gradients come out of the kernel)."""
 
     @staticmethod
-    def forward(ctx, queries, shift, cloud, counts, hint, tau, index, query_normals=None, cos=None):
+    def forward(ctx, queries, shift, cloud, counts, hint, tau, index, query_normals, cos):
         qs = _f32(queries)
         sh = None if shift is None else _f32(shift)
         b, n, _ = qs.shape
         d2 = torch.empty(b, n, dtype=torch.float32, device=qs.device)
-        if query_normals is not None:              # the oriented query: the same call with the normals, the cosine, the cones
-            _C.check(_C.lib().tuch_point_cloud_nearest_oriented(
-                _C.ptr(cloud._ws), cloud._nbytes, _C.ptr(cloud.points), _C.ptr(cloud.counts), _C.ptr(cloud.weights),
-                _C.ptr(cloud.point_normals), _C.ptr(qs), _C.ptr(query_normals), _C.ptr(sh), _C.ptr(counts), _C.ptr(hint), tau,
-                cos, _C.ptr(cloud._cones), cloud._cones_bytes(), b, cloud.num_points, n, _C.ptr(d2), _C.ptr(index),
-                _C.stream()))
-        else:
-            _C.check(_C.lib().tuch_point_cloud_nearest(
-                _C.ptr(cloud._ws), cloud._nbytes, _C.ptr(cloud.points), _C.ptr(cloud.counts), _C.ptr(cloud.weights),
-                _C.ptr(qs), _C.ptr(sh), _C.ptr(counts), _C.ptr(hint), tau, b, cloud.num_points, n, _C.ptr(d2), _C.ptr(index),
-                _C.stream()))
+        # (the points' normals go with the queries': an oriented cloud asked without them answers the plain query)
+        normals = None if query_normals is None else cloud.point_normals
+        _C.check(_C.lib().tuch_point_cloud_nearest(
+            _C.ptr(cloud._ws), cloud._nbytes, _C.ptr(cloud.points), _C.ptr(cloud.counts), _C.ptr(cloud.weights),
+            _C.ptr(normals), _C.ptr(qs), _C.ptr(query_normals), _C.ptr(sh), _C.ptr(counts), _C.ptr(hint), tau, cos or 0.0,
+            _C.ptr(cloud._cones), cloud._cones_bytes(), b, cloud.num_points, n, _C.ptr(d2), _C.ptr(index), _C.stream()))
         ctx.save_for_backward(qs, sh, index)
         ctx.cloud_points = cloud.points
         ctx.in_dtypes = (queries.dtype, None if shift is None else shift.dtype)
@@ -1833,8 +1813,7 @@ class _CloudNearest(torch.autograd.Function):
         gq = torch.where(won[:, :, None], 2.0 * g.to(torch.float32)[:, :, None] * (q - s), zero)
         dq, ds = ctx.in_dtypes
         return (gq.to(dq) if ctx.needs_input_grad[0] else None,
-                gq.sum(1).to(ds) if sh is not None and ctx.needs_input_grad[1] else None) + (None,) * (
-                    len(ctx.needs_input_grad) - 2)
+                gq.sum(1).to(ds) if sh is not None and ctx.needs_input_grad[1] else None) + (None,) * 7
 
 
 class PointCloud:
@@ -1931,7 +1910,7 @@ class PointCloud:
         indices are written to); max_distance tau > 0: only points with d2 <= f32(tau)^2 can win.  d2 is differentiable
         w.r.t. queries and shift with the index held fixed.
         query_normals [B,N,3] with max_angle in degrees, in (0, 90], on an oriented cloud (``orient``): the nearest valid
-        point whose normal is within the angle of the query's (tuch_point_cloud_nearest_oriented; a query or a point
+        point whose normal is within the angle of the query's (tuch_point_cloud_nearest with normals; a query or a point
         whose normal is a zero or non-finite row is unconstrained; normals are not shifted and get no gradient).  Both
         or neither must be given; with neither the call is the plain one."""
         what = 'PointCloud.nearest'
@@ -1940,16 +1919,16 @@ class PointCloud:
         counts = _counts_of(what, counts, b)
         tau = _tau_of(what, max_distance)
         _need_hip(what, counts, index_out)
-        extra = ()
+        cos = None
         if _both(what, 'query_normals', query_normals, 'max_angle', max_angle):
             if not torch.is_tensor(query_normals) or tuple(query_normals.shape) != (b, n, 3):
                 raise ValueError('%s: query_normals must be [%d,%d,3], got %s'
                                  % (what, b, n, tuple(query_normals.shape) if torch.is_tensor(query_normals) else
                                     type(query_normals)))
             _need_hip(what, query_normals)
-            extra = (_f32(query_normals.detach()), self._oriented_cos(what, max_angle))
+            query_normals, cos = _f32(query_normals.detach()), self._oriented_cos(what, max_angle)
         index = _index_out(what, index_out, b, n, queries.device)
-        d2 = _CloudNearest.apply(queries, shift, self, counts, hint, tau, index, *extra)
+        d2 = _CloudNearest.apply(queries, shift, self, counts, hint, tau, index, query_normals, cos)
         return NearestPoint(d2, index)
 
     def _knn_args(self, what, queries, k, shift, counts, max_distance):
@@ -2066,7 +2045,7 @@ class _CloudFit(torch.autograd.Function):
     _ScanFit's."""
 
     @staticmethod
-    def forward(ctx, verts, transl, cloud, vw, layout, hint, rho, sigma, tau, scale, index, cos=None, table=None):
+    def forward(ctx, verts, transl, cloud, vw, layout, hint, rho, sigma, tau, scale, index, cos, table):
         v, tr = _f32(verts), _f32(transl)
         b, n, _ = v.shape
         dev = v.device
@@ -2078,18 +2057,15 @@ class _CloudFit(torch.autograd.Function):
         gt = torch.empty(b, 3, dtype=torch.float32, device=dev)
         nbytes = L.tuch_point_cloud_fit_scratch_bytes(b, n)
         scratch = _workspace(nbytes, dev)
-        args = [_C.ptr(cloud._ws), cloud._nbytes, _C.ptr(cloud.points), _C.ptr(cloud.counts), _C.ptr(cloud.weights), _C.ptr(v),
-                _C.ptr(tr), _C.ptr(hint), tau, b, cloud.num_points, n, _C.ptr(vw), layout, rho, sigma, scale, _C.ptr(d2),
-                _C.ptr(index), _C.ptr(_ticket(dev)), _C.ptr(per_body), _C.ptr(out), _C.ptr(gv), _C.ptr(gt), _C.ptr(scratch),
-                nbytes, _C.stream()]
-        entry = L.tuch_point_cloud_fit_terms
-        if cos is not None:
-            # the oriented entry point takes the normals, the cosine, the mesh and the cones behind the cloud's triple
-            args[5:5] = [_C.ptr(cloud.point_normals), cos, _C.ptr(table.faces), _C.ptr(table.off), _C.ptr(table.ids),
-                         int(table.faces.shape[0]), _C.ptr(cloud._cones), cloud._cones_bytes()]
-            entry = L.tuch_point_cloud_fit_terms_oriented
-        _C.check(entry(*args))
-        ctx.num_inputs = 11 if cos is None else 13
+        # (the cosine and the table select the form: an oriented cloud asked without them answers the plain term)
+        normals = None if cos is None else cloud.point_normals
+        faces, off, ids = table or (None, None, None)
+        _C.check(L.tuch_point_cloud_fit_terms(
+            _C.ptr(cloud._ws), cloud._nbytes, _C.ptr(cloud.points), _C.ptr(cloud.counts), _C.ptr(cloud.weights),
+            _C.ptr(normals), cos or 0.0, _C.ptr(faces), _C.ptr(off), _C.ptr(ids), 0 if faces is None else int(faces.shape[0]),
+            _C.ptr(cloud._cones), cloud._cones_bytes(), _C.ptr(v), _C.ptr(tr), _C.ptr(hint), tau, b, cloud.num_points, n,
+            _C.ptr(vw), layout, rho, sigma, scale, _C.ptr(d2), _C.ptr(index), _C.ptr(_ticket(dev)), _C.ptr(per_body),
+            _C.ptr(out), _C.ptr(gv), _C.ptr(gt), _C.ptr(scratch), nbytes, _C.stream()))
         ctx.save_for_backward(gv, gt)
         ctx.in_dtypes = (verts.dtype, transl.dtype)
         ctx.mark_non_differentiable(per_body, d2)
@@ -2099,7 +2075,7 @@ class _CloudFit(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, g, *_others):
-        return _hand_over(ctx, g, ctx.num_inputs)
+        return _hand_over(ctx, g, 13)
 
 
 def cloud_fit(cloud: PointCloud, verts, transl, vertex_weights=None, hint=None, rho='distance', sigma=None,
@@ -2114,7 +2090,7 @@ def cloud_fit(cloud: PointCloud, verts, transl, vertex_weights=None, hint=None, 
     either mode of ``deterministic()``, for a body alone or in a batch.  hint / index_out as in ``PointCloud.nearest``.
     max_angle (degrees, in (0, 90]) with normal_table (``vertex_normal_table`` of the mesh the vertices belong to), on an
     oriented cloud: a vertex is matched only to points whose normal is within the angle of the vertex's own
-    (tuch_point_cloud_fit_terms_oriented, still one launch: the kernel forms the posed vertex normals itself).  The
+    (tuch_point_cloud_fit_terms with normals, still one launch: the kernel forms the posed vertex normals itself).  The
     NearestPoint then has the bits of ``cloud.nearest(verts, transl, ..., query_normals=vertex_normals(verts,
     normal_table), max_angle=max_angle)``; a vertex without an admissible point is one without winner (index -1).
     Normals only decide the match: they get no gradient.  Both or neither must be given.
@@ -2140,11 +2116,12 @@ def cloud_fit(cloud: PointCloud, verts, transl, vertex_weights=None, hint=None, 
     tau = _tau_of('cloud_fit', max_distance)
     _need_hip('cloud_fit', index_out)
     index = _index_out('cloud_fit', index_out, b, n, verts.device)
-    extra = ()
+    cos = None
     if _both('cloud_fit', 'max_angle', max_angle, 'normal_table', normal_table):
         _check_normal_table('cloud_fit', normal_table, n, verts.device)
-        extra = (cloud._oriented_cos('cloud_fit', max_angle), normal_table)
-    total, per_body, d2 = _CloudFit.apply(verts, transl, cloud, vw, layout, hint, rho, sigma, tau, float(scale), index, *extra)
+        cos = cloud._oriented_cos('cloud_fit', max_angle)
+    total, per_body, d2 = _CloudFit.apply(verts, transl, cloud, vw, layout, hint, rho, sigma, tau, float(scale), index, cos,
+                                          normal_table)
     return total, per_body, NearestPoint(d2, index)
 
 
@@ -2173,9 +2150,9 @@ class HDModel:
             handle = ctypes.c_void_p(0)
             cm = self.contact_model._handle
             with _C.create_context(self.contact_model.device):
-                _C.check(_C.lib().tuch_hd_model_create_k(ctypes.byref(handle), cm, self.num_points, self.row_nnz,
-                                                         idx.ctypes.data_as(ctypes.c_void_p), w.ctypes.data_as(ctypes.c_void_p),
-                                                         face.ctypes.data_as(ctypes.c_void_p)))
+                _C.check(_C.lib().tuch_hd_model_create(ctypes.byref(handle), cm, self.num_points, self.row_nnz,
+                                                       idx.ctypes.data_as(ctypes.c_void_p), w.ctypes.data_as(ctypes.c_void_p),
+                                                       face.ctypes.data_as(ctypes.c_void_p)))
             self._h = handle
         return self._h
 
