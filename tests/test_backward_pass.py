@@ -1,7 +1,7 @@
 """CPU: the bookkeeping of tuch_amd.backward_pass (pass ids, unit seeds, root nodes, the hand-over between two autograd
 nodes) driven by two toy autograd functions -- no kernels.  The consumer is y = 2 x; the producer is the scalar
 sum(y) + 3 sum(x) + sum(c): it finds the consumer's node through y.grad_fn and leaves its own gradient for x there, as
-ops._Stage2Tail does with the pose prior's gradient and lbs._SmplLBS's node.  d/dx is 5 however it travels."""
+ops.objectives._Stage2Tail does with the pose prior's gradient and lbs._SmplLBS's node.  d/dx is 5 however it travels."""
 import pytest
 import torch
 

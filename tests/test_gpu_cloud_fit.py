@@ -433,6 +433,7 @@ def test_gradients_against_central_differences(rho):
 
 def test_equal_bits_twice_alone_and_in_both_modes():
     from tuch_amd import ops
+    from tuch_amd.ops._base import _ticket
     results = []
     for rho in ('distance', 'gmof'):
         c = cf.term_case('body122', rho, 'BV', True)
@@ -450,7 +451,7 @@ def test_equal_bits_twice_alone_and_in_both_modes():
             results.append(first)
         for key in results[-1]:                                             # the two modes
             assert np.array_equal(results[-1][key], results[-2][key]), key
-    assert int(ops._ticket(torch.device(DEV)).item()) == 0
+    assert int(_ticket(torch.device(DEV)).item()) == 0
 
 
 def test_zero_weight_vertices_and_bodies_without_weight_or_points():

@@ -368,7 +368,7 @@ def test_contact_fitting_loss_vs_reference(tag, eu, sg, full, fused_tail, monkey
 
 @pytest.mark.parametrize('det', [True, False])
 def test_stage2_tail_value_float_and_fixed_paths(det):
-    """The three forms of the fused stage-2 tail (ops._Stage2Tail: value only, float atomics, fixed-point sums) on the
+    """The three forms of the fused stage-2 tail (ops.objectives._Stage2Tail: value only, float atomics, fixed-point sums) on the
     full objective of `small` (V = 122: 16 points per block, eight blocks per body; region pairs, segments, real prior
     and confidences).  No golden of SMALL lists an ignored body, so the bit-for-bit properties are checked twice: with
     the golden's ignore_idxs and with body 1 ignored; the comparison with the golden uses its own ignore_idxs."""
@@ -1437,7 +1437,7 @@ def test_hd_branch_selection_partners_and_graph_capture(tag):
         got = np.sort(sel[b, :counts[b]])
         assert (sel[b, counts[b]:] == -1).all()
         assert np.array_equal(got, want), (b, len(got), len(want))
-    # hipGraph capture of forward + backward (replays never on the NULL stream: tuch_amd/ops.py:off_default_stream)
+    # hipGraph capture of forward + backward (replays never on the NULL stream: tuch_amd/ops/_base.py:off_default_stream)
     from tuch_amd.ops import off_default_stream
     static_v = torch.tensor(g['verts'], device=d, requires_grad=True)
     with off_default_stream(d):

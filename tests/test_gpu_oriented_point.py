@@ -483,6 +483,7 @@ def test_gradients_against_central_differences(name, rho):
 
 def test_deterministic_mode_gives_equal_bits_twice():
     from tuch_amd import ops
+    from tuch_amd.ops._base import _ticket
     for rho in ('distance', 'gmof'):
         c = oc.term_case('body122', 3, 257, rho, 5.0)
         m = model('body122')
@@ -490,7 +491,7 @@ def test_deterministic_mode_gives_equal_bits_twice():
             first, second, third = _term(m, c)[0], _term(m, c)[0], _term(m, c)[0]
         for key in first:
             assert np.array_equal(first[key], second[key]) and np.array_equal(first[key], third[key]), key
-    assert int(ops._ticket(torch.device(DEV)).item()) == 0
+    assert int(_ticket(torch.device(DEV)).item()) == 0
 
 
 def test_term_workspace_guards_stay_intact():

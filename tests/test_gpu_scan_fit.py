@@ -277,6 +277,7 @@ def test_bodies_without_weight_or_points_give_zero():
 
 def test_deterministic_mode_gives_equal_bits_twice_and_alone():
     from tuch_amd import ops
+    from tuch_amd.ops._base import _ticket
     for rho in ('distance', 'gmof'):
         c = sc.term_case('body122', 3, 257, rho, weighted=True)
         m = model('body122')
@@ -291,7 +292,7 @@ def test_deterministic_mode_gives_equal_bits_twice_and_alone():
                 assert alone['per'][0] == first['per'][b] and alone['total'] == first['per'][b]
                 assert np.array_equal(alone['gv'][0], first['gv'][b]) and np.array_equal(alone['gt'][0], first['gt'][b])
                 assert np.array_equal(alone['gp'][0], first['gp'][b])
-    assert int(ops._ticket(torch.device(DEV)).item()) == 0
+    assert int(_ticket(torch.device(DEV)).item()) == 0
 
 
 def test_term_workspace_guards_and_capture():

@@ -530,7 +530,7 @@ def test_fused_adam_only_when_the_stage2_objective_is_the_root_of_the_pass():
 
 @pytest.mark.parametrize('shape_w', [1.0, 0.0])
 def test_stage1_objective_in_one_launch_vs_reference_and_torch_ops(shape_w):
-    """camera_fitting_loss (losses.py:125-152) on a HIP device is ONE kernel (ops._Stage1Objective): the value against the
+    """camera_fitting_loss (losses.py:125-152) on a HIP device is ONE kernel (ops.objectives._Stage1Objective): the value against the
     reference's own golden (shape_prior_weight = 1) and, value + gradients w.r.t. joints / camera translation / betas,
     against the torch-op form of the same function (autograd), also under a non-unit upstream gradient."""
     import types

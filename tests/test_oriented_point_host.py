@@ -143,10 +143,10 @@ def test_wrapper_argument_checks():
             call(normals=normals[:, :6], max_angle=60.0)
         with pytest.raises(ValueError, match='normals'):
             call(normals=normals[:, :, :2], max_angle=60.0)
-    assert ops._max_angle_cos(None, None, points, 'x') is None
-    assert ops._max_angle_cos(normals, 60.0, points, 'x') == float(oc.cos32(60.0))
-    assert 0.0 <= ops._max_angle_cos(normals, 90.0, points, 'x') < 1e-7
-    assert ops._max_angle_cos(normals, 1e-3, points, 'x') < 1.0
+    assert ops.args.max_angle_cos(None, None, points, 'x') is None
+    assert ops.args.max_angle_cos(normals, 60.0, points, 'x') == float(oc.cos32(60.0))
+    assert 0.0 <= ops.args.max_angle_cos(normals, 90.0, points, 'x') < 1e-7
+    assert ops.args.max_angle_cos(normals, 1e-3, points, 'x') < 1.0
     for bad in (0.0, 91.0, -1.0):
         with pytest.raises(ValueError, match='max_normal_angle'):
             ScanFitter(None, None, max_normal_angle=bad)

@@ -44,7 +44,7 @@ print('%-62s %7.1f us' % ('one after the other', res['one after the other']))
 
 # what each side costs beside the other: the pair with one side on fewer bodies
 model.set_option('overlap', 1)
-from tuch_amd.ops import _side_stream
+from tuch_amd.ops._base import _side_stream
 
 
 def pair(bi, bs):

@@ -4,7 +4,7 @@ import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch, bench
 from tuch_amd import _C
-from tuch_amd.ops import _workspace
+from tuch_amd.ops._base import _workspace
 from tuch_amd.smplify.losses import contact_model_for
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 64
 dev = torch.device('cuda:0')

@@ -221,7 +221,7 @@ def main():
                 print(json.dumps(line), flush=True)
                 if a.normals is not None:
                     found = graphs['oriented unhinted'][1]
-                    cosine = ops._max_angle_cos(nrm, a.normals, queries[1], 'scan_fit_timing')
+                    cosine = ops.args.max_angle_cos(nrm, a.normals, queries[1], 'scan_fit_timing')
                     ov, ot, _ = oriented_group_visits(model, verts[1], queries[1], nrm, found.d2, cosine)
                     print(json.dumps({'what': 'oriented search at %g degrees, %s' % (a.normals, name),
                                       'matched': round(float((found.face >= 0).float().mean()), 5),

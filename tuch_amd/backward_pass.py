@@ -1,6 +1,6 @@
 """Which backward pass is running, and the one hand-over between two autograd nodes of the same pass.
 
-ops._Stage2Tail (the producer: the stage-2 objective) leaves a Handover on the node of lbs._SmplLBS (the consumer: the body
+ops.objectives._Stage2Tail (the producer: the stage-2 objective) leaves a Handover on the node of lbs._SmplLBS (the consumer: the body
 model that made its vertices), whose backward runs later in the same pass and takes it.  The rules:
 
 | decision | condition |

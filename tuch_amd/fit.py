@@ -211,15 +211,15 @@ class ScanFitter(BodyFitter):
                  use_hint=True, use_graph=True, record_history=False, model_to_scan=0.0, vertex_weights=None,
                  max_distance=None, resolution=64, max_normal_angle=None, estimate_normals=None,
                  model_to_scan_normals=False):
-        ops._rho_of('ScanFitter', rho, sigma)
+        ops.args.rho_of('ScanFitter', rho, sigma)
         if not float(model_to_scan) >= 0.0:
             raise ValueError('ScanFitter: model_to_scan must be >= 0, got %r' % (model_to_scan,))
-        ops._tau_of('ScanFitter', max_distance)
+        ops.args.tau_of('ScanFitter', max_distance)
         if max_normal_angle is not None:
-            max_normal_angle = ops._angle_of('ScanFitter', 'max_normal_angle', max_normal_angle)
-        ops._resolution_of('ScanFitter', resolution)
+            max_normal_angle = ops.args.angle_of('ScanFitter', 'max_normal_angle', max_normal_angle)
+        ops.args.resolution_of('ScanFitter', resolution)
         if estimate_normals is not None:
-            ops._check_k('ScanFitter: estimate_normals', estimate_normals)
+            ops.args.check_k('ScanFitter: estimate_normals', estimate_normals)
             if max_normal_angle is None:
                 raise ValueError('ScanFitter: estimate_normals needs max_normal_angle')
         if model_to_scan_normals and not (float(model_to_scan) > 0.0 and max_normal_angle is not None):

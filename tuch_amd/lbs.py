@@ -75,7 +75,7 @@ class _SmplLBS(torch.autograd.Function):
                                            int(pose2rot), b, _C.ptr(verts), _C.ptr(joints), _C.ptr(ws), nbytes, _C.stream()))
         ctx.dm, ctx.pose2rot = dm, bool(pose2rot)
         ctx.shapes = (global_orient.shape, body_pose.shape)
-        # A later node that holds ANOTHER gradient for the same body_pose (ops._Stage2Tail: the pose prior) may leave it in
+        # A later node that holds ANOTHER gradient for the same body_pose (ops.objectives._Stage2Tail: the pose prior) may leave it in
         # `handover` (backward_pass) instead of returning it: backward() adds it inside its last kernel, one add launch less.
         # pose_ref: how that node recognises the tensor -- by IDENTITY (an alias with the same address and shape is another leaf)
         ctx.pose_ref = weakref.ref(body_pose) if ctx.needs_input_grad[2] else None
@@ -107,7 +107,7 @@ class _SmplLBS(torch.autograd.Function):
             return g_betas, None, None, None, None, g_full
         g_go = torch.empty(go.shape, dtype=torch.float32, device=go.device)
         g_bp = torch.empty(bp.shape, dtype=torch.float32, device=go.device)
-        # what ops._Stage2Tail left in THIS backward pass (backward_pass: the table of rules).  extra: the prior's gradient,
+        # what ops.objectives._Stage2Tail left in THIS backward pass (backward_pass: the table of rules).  extra: the prior's gradient,
         # added to g_bp.  fixed: that node's vertex gradient as 64-bit fixed-point sums (deterministic mode), read by the
         # skinning adjoint itself, added to g_verts (zeros from that node, plus whatever else flows into the vertices)
         left = backward_pass.take(ctx)

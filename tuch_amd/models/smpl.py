@@ -206,7 +206,7 @@ class SMPL(nn.Module):
         from .. import lbs
         w = 3 if pose2rot else 9
         rows = lambda t, n: t if (t.dim() == 2 and t.shape[1] == n) else t.reshape(-1, n)
-        # (a tensor that already has the row shape is passed on AS THE SAME OBJECT: ops._Stage2Tail recognises the pose tensor
+        # (a tensor that already has the row shape is passed on AS THE SAME OBJECT: ops.objectives._Stage2Tail recognises the pose tensor
         # it shares with this node by identity)
         global_orient_rows = rows(global_orient, w)
         body_pose_rows = rows(body_pose, 23 * w)

@@ -15,10 +15,10 @@ import torch
 from .. import ops
 from ..utils.geometry import perspective_projection
 
-# one autograd node for everything behind the body model (ops._Stage2Tail) instead of separate nodes; read from the
+# one autograd node for everything behind the body model (ops.objectives._Stage2Tail) instead of separate nodes; read from the
 # environment once, at import (TUCH_FUSED_TAIL=0: A/B measurements; the tests flip the attribute)
 FUSED_TAIL = os.environ.get('TUCH_FUSED_TAIL', '1') != '0'
-# camera_fitting_loss (the stage-1 objective) as one launch on HIP devices (ops._Stage1Objective); 0: the torch-op form
+# camera_fitting_loss (the stage-1 objective) as one launch on HIP devices (ops.objectives._Stage1Objective); 0: the torch-op form
 STAGE1_FUSED = os.environ.get('TUCH_STAGE1_FUSED', '1') != '0'
 
 _MODEL_CACHE: Dict[tuple, tuple] = {}
@@ -113,7 +113,7 @@ def stage2_objective(model, valid, select, body_pose, betas, model_joints, euclt
              and model_joints.dtype == torch.float32 and body_pose.dtype == torch.float32)
 
     if fused and camera_t.shape == (body_pose.shape[0], 3) and FUSED_TAIL:
-        # one autograd node for everything behind the body model (ops._Stage2Tail): the same kernels, less glue
+        # one autograd node for everything behind the body model (ops.objectives._Stage2Tail): the same kernels, less glue
         return ops.smplify_stage2_tail(
             verts, model_joints, camera_t, body_pose, model, valid,
             select.to(torch.uint8).contiguous() if select is not None else None,
